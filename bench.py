@@ -12,6 +12,10 @@ through the reference network): forward through ERGB2DepthRecu
 Inputs are synthetic (device-generated event lists -> HIP voxel scatter-add -> nonzero normalisation; U[0,1) frames;
 log-depth targets) and resident in HBM before the timed region.  Weights: seeded random init (no checkpoints offline).
 
+A plain run sets up, warms up, times the --steps steps and prints the result line (`ms_per_step` = milliseconds per timed step).
+`--full` adds everything else below: per-kernel timing and the roofline, the extras and the CPU oracle baseline.
+`--dump-outputs DIR` writes what the last timed step computed (seeded inputs: the same arguments give the same inputs) as DIR/*.npy.
+
 Roofline accounting.  The convolutions are MFMA-bound.  Every MFMA launch is classified by the kernel the
 library reports (ramnet_last_kernel) and carries two FLOP counts: ALGORITHMIC (2*B*Ho*Wo*taps*Cin*Cout of the layer it
 stands for) and EXECUTED (what the MFMA pipe really multiplies: Winograd F(2x2,3x3) 16/36 of the 3x3 taps —
@@ -111,13 +115,23 @@ def parse():
     ap.add_argument("--input-stream", dest="input_inline", action="store_false",
                     help="A/B: the next step's voxelisation on a low-priority input stream beside the compute (round 5's schedule) instead of the "
                          "step's own stream, in front of its forward pass (default since round 6: a fourth stream of 160 KB-LDS workgroups beside "
-                         "the three compute streams cost 1.6 % — 229.7 / 230.8 against 233.6 / 234.2 samples/s on one box, "
-                         "profiles/r06_sched_ab.txt — and 2.7 % with split operands, whose workgroups need a whole CU)")
+                         "the three compute streams cost 1.6 %% — 229.7 / 230.8 against 233.6 / 234.2 samples/s on one box, "
+                         "profiles/r06_sched_ab.txt — and 2.7 %% with split operands, whose workgroups need a whole CU)")
     ap.add_argument("--graph", action="store_true",
                     help="train: the timed step replays ONE hipGraph (gradient zero-fill, forward, loss, BPTT backward, gradient fold; "
                          "rpg_ramnet_amd.graph.GraphedTrainStep) instead of ~7000 eager launches; per-kernel HIP events are then "
                          "unavailable (no roofline object).  stream / infer modes always report both eager and graph replay")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-kernel HIP-event timing, roofline / traffic / HBM-kernel tables, the shader "
+                         "clock, the extras (other schedules, runtimes and workloads, some in processes of their own) and the CPU oracle baseline "
+                         "(--no-kernel-timing / --no-extras / --no-cpu-baseline / --cpu-infer-baseline select among them).  Without it a run sets "
+                         "up, warms up, times --steps steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_kernel_timing = args.no_extras = args.no_cpu_baseline = True
+    return args
 
 
 def subprocess_measure(extra, note, steps=2, warmup=1, timeout=240):
@@ -191,6 +205,22 @@ def synth_sequence(model, B, L, H, W, K, bins, n_events, seed, keep_events=None)
             item["depth_" + key] = torch.clamp(1.0 + torch.log(u) / 3.70378, 0.0, 1.0)
         seq.append(item)
     return seq
+
+
+DUMP_MAX_ELEMS = 7000000        # per array (28 MB of float32): a run dumps one array, < 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as <path>/<name>.npy, float64 if it is float64, else float32.  An array of more than DUMP_MAX_ELEMS
+    elements is flattened and replaced by a fixed sample: the elements at DUMP_MAX_ELEMS sorted positions drawn without replacement by
+    numpy.random.default_rng(0), the same positions in every run of the same shape."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------------------------- timing
@@ -881,6 +911,7 @@ def main():
         ranks_seen = sorted(int(v.item()) for v in got)
 
     graphed = {}
+    outputs = {}        # infer / stream: the predictions the last step returned (--dump-outputs)
     if args.mode == "train":
         model.train()
         reducer = FlatGradReducer(model, always_collective=args.force_collective)
@@ -953,7 +984,8 @@ def main():
                 for k in range(sched[l]):
                     tb.push_events(item["events%d" % (k % K)])
                 pred = tb.push_image(item["image"])
-            return tb.wait(pred).mean()
+            outputs["pred"] = tb.wait(pred)
+            return outputs["pred"].mean()
         graphed["eager"] = eager_step
         graphed["graph_serial"] = lambda: run_stream(gs_serial)
         graphed["graph_two_stage"] = lambda: run_stream(gs_two)
@@ -986,7 +1018,8 @@ def main():
                 for k in range(K):
                     tbi.push_events(item["events%d" % k])
                 out = tbi.push_image(item["image"])
-            return tbi.wait(out)[K].mean()
+            outputs["pred"] = tbi.wait(out)
+            return outputs["pred"][K].mean()
         graphed["eager"] = eager_step
         if gp is not None:
             graphed["graph_per_package"] = package_step
@@ -1005,7 +1038,8 @@ def main():
     # FLOP accounting comes from one eager pass below)
     timer.on = timer.hbm = not args.no_kernel_timing and args.mode == "train"
     # (the clock is sampled over the WARM-UP steps — the same workload, untimed: nothing polls the driver inside the timed region)
-    with ClockSampler() if (rank == 0 and args.mode == "train" and args.warmup > 0) else contextlib.nullcontext() as clock:
+    # (only the roofline quotes it: off without kernel timing)
+    with ClockSampler() if (rank == 0 and args.mode == "train" and args.warmup > 0 and not args.no_kernel_timing) else contextlib.nullcontext() as clock:
         for _ in range(args.warmup):
             last = step()
         fence()
@@ -1048,6 +1082,14 @@ def main():
                             "early buckets for later folds"}
     loss_val = float(last.detach())
     assert np.isfinite(loss_val), "non-finite loss"
+    if args.dump_outputs and rank == 0:      # (before the extras below run further steps on the same model)
+        # train: the loss the step returns.  (Not the weights or gradients: the head and decoder backward-weights join partial sums by
+        # atomic adds, and over several steps Adam turns their last-bit differences into O(lr) moves of parameters that the scale-invariant
+        # loss barely sees — run-to-run noise, not a property of the inputs.)
+        if args.mode == "train":
+            dump_outputs(args.dump_outputs, {"loss": last.detach().double().reshape(1)})
+        else:                                # the predictions the last step returned ([updates + 1, B, 1, H, W] of its last group)
+            dump_outputs(args.dump_outputs, {"pred": outputs["pred"]})
 
     # ---- extras (outside the timed region that defines `value`): the same step with every launch on ONE stream — per-kernel
     # durations without co-scheduled neighbours (dominant kernel, and the ConvGRU state update per scale).  2 steps, 1 warm-up.

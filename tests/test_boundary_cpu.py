@@ -903,3 +903,35 @@ def test_bench_traffic_is_requests_times_64_bytes_plus_writes():
     assert bench.traffic_of(pmc, "conv_wino_r6_kernel<4,0>", fetch_x2=True) == pytest.approx((3 * 250.0 + 90.0) * 1024 / 4)
     assert bench.traffic_of(pmc, "no_such_kernel") is None
     assert bench.pmc_launches_of(pmc, "conv_wino_r6_kernel<4,0>") == 4
+
+
+def test_bench_plain_run_is_lean_and_full_keeps_everything(monkeypatch):
+    """A plain `bench.py --steps N --warmup W` times the steps and nothing else; --full restores kernel timing, extras and the CPU baseline,
+    and its --no-* options still select among them."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_kernel_timing and a.no_extras and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-extras", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and a.no_extras and not a.no_kernel_timing and not a.no_cpu_baseline
+
+
+def test_bench_dump_outputs_types_and_fixed_sample(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files; an array above the cap becomes the same seeded sample of positions in every run."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMS + 1000, dtype=torch.float32)
+    small = torch.arange(24, dtype=torch.float16).view(2, 3, 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"loss": np.array([0.5]), "big": big, "small": small})
+    loss, a, b, s = (np.load(str(tmp_path / p)) for p in ("a/loss.npy", "a/big.npy", "b/big.npy", "a/small.npy"))
+    assert loss.dtype == np.float64 and loss.tolist() == [0.5]
+    assert s.dtype == np.float32 and s.shape == (2, 3, 4) and np.array_equal(s, small.float().numpy())
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_ELEMS,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a.max() < big.numel()       # distinct positions, in order, from the array itself
+    assert os.path.getsize(str(tmp_path / "a" / "big.npy")) < 64e6      # a capped array stays under 64 MB

@@ -10,10 +10,10 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $ROOT/bench.py --steps $STEPS --warmup $WARM > $OUT/bench.json 2> $OUT/bench.err
+python $ROOT/bench.py --full --steps $STEPS --warmup $WARM > $OUT/bench.json 2> $OUT/bench.err
 echo "bench rc=$?"; tail -c 400 $OUT/bench.json
 rm -rf /tmp/prof_stats && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o s -- \
-    python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/rocprof.err
+    python $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras > $OUT/bench_under_rocprof.json 2> $OUT/rocprof.err
 cp $(find /tmp/prof_stats -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats.csv 2>/dev/null
 for C in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/pmc_$C && timeout 1200 rocprofv3 --pmc $C --output-format csv -d /tmp/pmc_$C -o c -- \

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $ROOT/bench.py --mode stream --batch 1 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/stream_bench.json 2> $OUT/stream_bench.err
+python $ROOT/bench.py --full --mode stream --batch 1 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/stream_bench.json 2> $OUT/stream_bench.err
 echo "stream bench rc=$?"; head -c 600 $OUT/stream_bench.json; echo
 rm -rf /tmp/prof_stream && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stream -o s -- \
     python $ROOT/bench.py --mode stream --batch 1 --steps 3 --warmup 1 --no-cpu-baseline --no-extras --no-kernel-timing > $OUT/stream_bench_under_rocprof.json 2> $OUT/stream_rocprof.err

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define RAMNET_ABI_VERSION 24      /* 24: ramnet_cat_batch_add_masked (the gradient of a time-batched ReLU feature leaves its fan-in already masked), ramnet_pred_sigmoid_si_bwd takes the forward's scratch (fixed-order join of the weight / bias partial sums); 23: ramnet_wgrad_desc.algo = RAMNET_ALGO_DIRECT_SPLIT (direct 3x3 backward-weights on the bf16 matrix pipe, split operands: csrc/conv_wgrad_dsplit.hip) + ramnet_wgrad_dsplit_slabs; 22: RAMNET_ALGO_WINOGRAD_2X4_SPLIT + ramnet_conv_wino_split_ok / ramnet_pack_weight_wino2x4_split (split bf16 operands on the F(2x4,3x3) forward / backward-data launches); 21: RAMNET_EPI_SIGMOID_HR (the ConvGRU gates launch also writes h.r: the candidate convolution and its backward-weights read a plain concatenation); 20 (never released on its own: shipped together with 21): ramnet_wgrad_desc.nseg / segs (multi-segment backward-weights launches: deferred ConvGRU cell updates); 19: ramnet_cat_batch_add (gradient of a time-batched feature); 18: RAMNET_EPI_GRU_BWD (stage B of the ConvGRU backward in the epilogue of the candidate convolution's backward-data launch) + ramnet_gru_bwd_a2; 17: ramnet_wgrad_desc.algo = RAMNET_ALGO_WINOGRAD_2X4 (F(2x4,3x3) backward-weights, csrc/conv_wgrad_wino6.hip) + ramnet_wgrad_wino2x4_slabs / ramnet_unpack_wgrad_wino2x4, option "wgrad_wino_nf"; 16: ramnet_conv_desc.splitk_ws / splitk_floats + ramnet_conv_splitk_floats (split channel reduction of latency-bound Winograd launches), option "wino_ksplit"; 15: ramnet_si_loss_from_stats (data-parallel exact loss), ramnet_si_log_loss_* / ramnet_mse_loss_*, ramnet_reflect_pad, ramnet_wgrad_desc.dw_slabs + ramnet_reduce_slabs, ramnet_set_option (environment knobs removed), fold weight-algebra kernels, RAMNET_ALGO_WINOGRAD_2X4 + ramnet_conv_wino_variant / ramnet_pack_weight_wino2x4; 14: ramnet_norm_* (BatchNorm / InstanceNorm); 13: pair layout of ramnet_pack_weight_fold_wino, head kernel for 10 input channels */
+#define RAMNET_ABI_VERSION 25      /* 25: ramnet_conv_desc.active (per-sample update masks of the cell epilogues: batched irregular packages) + ramnet_lstm_bwd_masked; 24: ramnet_cat_batch_add_masked (the gradient of a time-batched ReLU feature leaves its fan-in already masked), ramnet_pred_sigmoid_si_bwd takes the forward's scratch (fixed-order join of the weight / bias partial sums); 23: ramnet_wgrad_desc.algo = RAMNET_ALGO_DIRECT_SPLIT (direct 3x3 backward-weights on the bf16 matrix pipe, split operands: csrc/conv_wgrad_dsplit.hip) + ramnet_wgrad_dsplit_slabs; 22: RAMNET_ALGO_WINOGRAD_2X4_SPLIT + ramnet_conv_wino_split_ok / ramnet_pack_weight_wino2x4_split (split bf16 operands on the F(2x4,3x3) forward / backward-data launches); 21: RAMNET_EPI_SIGMOID_HR (the ConvGRU gates launch also writes h.r: the candidate convolution and its backward-weights read a plain concatenation); 20 (never released on its own: shipped together with 21): ramnet_wgrad_desc.nseg / segs (multi-segment backward-weights launches: deferred ConvGRU cell updates); 19: ramnet_cat_batch_add (gradient of a time-batched feature); 18: RAMNET_EPI_GRU_BWD (stage B of the ConvGRU backward in the epilogue of the candidate convolution's backward-data launch) + ramnet_gru_bwd_a2; 17: ramnet_wgrad_desc.algo = RAMNET_ALGO_WINOGRAD_2X4 (F(2x4,3x3) backward-weights, csrc/conv_wgrad_wino6.hip) + ramnet_wgrad_wino2x4_slabs / ramnet_unpack_wgrad_wino2x4, option "wgrad_wino_nf"; 16: ramnet_conv_desc.splitk_ws / splitk_floats + ramnet_conv_splitk_floats (split channel reduction of latency-bound Winograd launches), option "wino_ksplit"; 15: ramnet_si_loss_from_stats (data-parallel exact loss), ramnet_si_log_loss_* / ramnet_mse_loss_*, ramnet_reflect_pad, ramnet_wgrad_desc.dw_slabs + ramnet_reduce_slabs, ramnet_set_option (environment knobs removed), fold weight-algebra kernels, RAMNET_ALGO_WINOGRAD_2X4 + ramnet_conv_wino_variant / ramnet_pack_weight_wino2x4; 14: ramnet_norm_* (BatchNorm / InstanceNorm); 13: pair layout of ramnet_pack_weight_fold_wino, head kernel for 10 input channels */
 #define RAMNET_E_BADARG 10001
 #define RAMNET_E_UNSUPPORTED 10002
 
@@ -130,6 +130,16 @@ typedef struct ramnet_conv_desc {
                                      * here, the last arrival sums them in split order (bit-reproducible) and runs the epilogue, and leaves
                                      * the arrival counters at zero.  NULL: never split.                                               */
     size_t splitk_floats;
+    const int *active;              /* ABI 25, optional: [B] device flags (int32), NULL = every sample active.  Only the cell epilogues accept it
+                                     * (any other epilogue: RAMNET_E_BADARG).  For a sample with active[b] == 0 the state passes through
+                                     * bit for bit (copies, no arithmetic) and what the backward reads is zero:
+                                     *   RAMNET_EPI_SIGMOID / _SIGMOID_HR: u = r = 0 (and h.r = 0);
+                                     *   RAMNET_EPI_GRU_BLEND: out <- h (e1; NULL: 0), o1 <- 0;
+                                     *   RAMNET_EPI_LSTM: e0 = h (required, lde0), out <- h, o1 <- c (e1; NULL: 0), o2 <- 0.
+                                     * With u = r = o = 0 the unmasked ConvGRU backward gives dh = dh', zero pre-activation gradients and
+                                     * no contribution to dx or dW for those samples; the ConvLSTM uses ramnet_lstm_bwd_masked.  Every
+                                     * family a cell launch can take honours it (DIRECT, WINOGRAD incl. its split reduction, WINOGRAD_2X4,
+                                     * WINOGRAD_2X4_SPLIT); the others refuse the descriptor.                                          */
 } ramnet_conv_desc;
 
 /* Weight-gradient launch: dW[t][c][n] += sum_{b,a,b'} in(a*stride+dy[t], b'*stride+dx[t], c) * g(a,b',n)
@@ -382,6 +392,12 @@ int ramnet_gru_bwd_b(const float *dxhr, const float *ur, const float *h, float *
  * dgates_pre [npix,4C], dc_prev.                                                                   */
 int ramnet_lstm_bwd(const float *gates, const float *cprev, const float *cnew, const float *dhn,
                     const float *dcn, float *dpre, float *dcprev, size_t npix, int C, void *stream);
+/* The same for a cell launch with a per-sample mask (ABI 25; ramnet_conv_desc.active [B] device flags, hw = pixels per sample): active
+ * pixels as ramnet_lstm_bwd; inactive ones get dpre = 0 and dc_prev = dc' (NULL: 0).  Also fills dxh [npix][2C] (leading dimension 2C)
+ * for a backward-data launch of the cell convolution with beta = 1: dxh = 0 except the h half of inactive pixels, which gets dh' (NULL:
+ * 0) — the identity path of an inactive sample.                                                                                    */
+int ramnet_lstm_bwd_masked(const float *gates, const float *cprev, const float *cnew, const float *dhn, const float *dcn,
+                           const int *active, float *dpre, float *dcprev, float *dxh, size_t npix, int hw, int C, void *stream);
 /* db[C] += sum_pixels dy * (mask > 0): bias gradient of the transposed-conv decoder (submodules.py:38-66). */
 int ramnet_bias_grad(const float *dy, const float *mask, float *db, size_t npix, int C, void *stream);
 /* ---- BatchNorm / InstanceNorm of `norm: "BN" | "IN"` layers: submodules.py:13-24, 29-30, 52-62, 82-94, 188-193, 203-210 ------

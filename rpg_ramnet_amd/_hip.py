@@ -37,6 +37,7 @@ class ConvDesc(C.Structure):
         ("head_cin", C.c_int),
         ("s2d_5x5", C.c_int),
         ("splitk_ws", C.c_void_p), ("splitk_floats", C.c_size_t),
+        ("active", _fp),                 # ABI 25: [B] int32 per-sample update mask of a cell launch, NULL = all active
     ]
 
 
@@ -136,6 +137,7 @@ _SIGS = {
     "ramnet_gru_bwd_a2": (C.c_int, [_fp] * 7 + [C.c_size_t, C.c_int, C.c_int, C.c_int, _fp]),
     "ramnet_gru_bwd_b": (C.c_int, [_fp] * 5 + [C.c_size_t, C.c_int, _fp]),
     "ramnet_lstm_bwd": (C.c_int, [_fp] * 7 + [C.c_size_t, C.c_int, _fp]),
+    "ramnet_lstm_bwd_masked": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, C.c_int, C.c_int, _fp]),
     "ramnet_norm_slabs": (C.c_int, [C.c_int, C.c_long, C.c_int]),
     "ramnet_norm_partial": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, _fp, _fp]),
     "ramnet_norm_finalize": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_long, C.c_double, _fp, _fp, _fp, _fp, C.c_double, C.c_int, C.c_int,
@@ -211,7 +213,7 @@ def lib():
         for name, (res, args) in _SIGS.items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
-        if l.ramnet_abi_version() != 24:
+        if l.ramnet_abi_version() != 25:
             raise RuntimeError("ABI version mismatch in %s" % LIB_PATH)
         _lib = l
     return _lib if _tracer is None else _Traced(_lib)

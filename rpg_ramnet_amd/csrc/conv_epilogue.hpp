@@ -52,6 +52,31 @@ __device__ __forceinline__ void epilogue_store(const ramnet_conv_desc &p, int ep
     p.out[pix * p.ldo + n] = v;
 }
 
+// Per-sample update masks (ramnet_conv_desc.active, ABI 25): sample b of a masked launch is active?  The kernels instantiate their masked
+// epilogues separately (template flag), the unmasked ones carry no trace of it.
+__device__ __forceinline__ bool sample_active(const ramnet_conv_desc &p, int b) { return p.active[b] != 0; }
+
+// Cell epilogue of an INACTIVE sample, channel n (< Cout; LSTM: hidden channel) of pixel pix: the state passes through as a copy and
+// what the backward reads is zero — u = r = 0 and h.r = 0 (gates), o = 0 (blend), gates = 0 (LSTM).  Copies, not h*(1-u)+o*u: -0.0
+// stays -0.0 and a non-finite candidate cannot leak in.
+__device__ __forceinline__ void epilogue_inactive(const ramnet_conv_desc &p, int epi, size_t pix, int n) {
+    float v = 0.f;
+    if (epi == RAMNET_EPI_SIGMOID_HR) {
+        if (n >= p.Cout / 2) p.o1[pix * p.ldo1 + n - p.Cout / 2] = 0.f;
+    } else if (epi == RAMNET_EPI_GRU_BLEND) {
+        if (p.o1) p.o1[pix * p.ldo1 + n] = 0.f;
+        v = p.e1 ? p.e1[pix * p.lde1 + n] : 0.f;
+    } else if (epi == RAMNET_EPI_LSTM) {
+        p.o1[pix * p.ldo1 + n] = p.e1 ? p.e1[pix * p.lde1 + n] : 0.f;
+        if (p.o2) {
+            float *g = p.o2 + pix * p.ldo2 + n;
+            g[0] = 0.f, g[p.Cout] = 0.f, g[2 * p.Cout] = 0.f, g[3 * p.Cout] = 0.f;
+        }
+        v = p.e0[pix * p.lde0 + n];
+    }
+    p.out[pix * p.ldo + n] = v;
+}
+
 // RAMNET_EPI_GRU_BWD, channels of the d(h.r) half: g = the convolution's result, r, h, old = the direct path already in `out`;
 // writes the reset gate's pre-activation gradient and returns the completed dh.
 __device__ __forceinline__ float4 gru_bwd_quad(float4 g, float4 r, float4 h, float4 old, float *dpr) {

@@ -37,8 +37,8 @@ struct ConvClass {
 };
 struct ConvClasses { ConvClass c[4]; };
 
-// Exact fp32 (v_mfma_f32_32x32x2_f32), 16 channels per chunk.
-template <int BM, int BN, int WM, int WN>
+// Exact fp32 (v_mfma_f32_32x32x2_f32), 16 channels per chunk.  MASK: cell launch with a per-sample update mask (ramnet_conv_desc.active).
+template <int BM, int BN, int WM, int WN, bool MASK = false>
 __global__ void __launch_bounds__(256) conv_igemm_kernel(const ramnet_conv_desc p, const ConvCommon qc, const ConvClasses qk) {
     // XCD-aware tile order: the dispatcher deals consecutive (flattened) workgroup ids round-robin to the 8 XCDs, each with
     // a private L2.  Remap the flattened id so that every XCD walks a CONTIGUOUS range of (class, channel tile, spatial
@@ -149,6 +149,7 @@ __global__ void __launch_bounds__(256) conv_igemm_kernel(const ramnet_conv_desc 
 
     // ---- epilogue.  D layout of 32x32 MFMA: col = lane&31 (output channel), row = (r&3)+8*(r>>2)+4*(lane>>5) (pixel)
     const int epi = p.epi;
+    const bool act = !MASK || sample_active(p, b);         // (b: one image per workgroup)
 #pragma unroll
     for (int ms = 0; ms < TM; ++ms) {
 #pragma unroll
@@ -162,7 +163,9 @@ __global__ void __launch_bounds__(256) conv_igemm_kernel(const ramnet_conv_desc 
                 if constexpr (TN == 4) {
                     // packed N order = (channel block of 32, gate, channel): ns is the gate (i, f, o, g)
                     const int C = p.Cout, ch = by * 32 + l31;
-                    if (ch < C) {
+                    if (MASK && !act) {
+                        if (ch < C) epilogue_inactive(p, epi, pix, ch);
+                    } else if (ch < C) {
                         const float gi = sigmoidf_(acc[ms][0][r] + p.bias[ch]);
                         const float gf = sigmoidf_(acc[ms][1][r] + p.bias[C + ch]);
                         const float go = sigmoidf_(acc[ms][2][r] + p.bias[2 * C + ch]);
@@ -183,6 +186,10 @@ __global__ void __launch_bounds__(256) conv_igemm_kernel(const ramnet_conv_desc 
             for (int ns = 0; ns < TN; ++ns) {
                 const int n = n0 + (wn * TN + ns) * 32 + l31;
                 if (n >= p.Cout) continue;
+                if (MASK && !act) {
+                    epilogue_inactive(p, epi, pix, n);
+                    continue;
+                }
                 epilogue_store(p, epi, pix, n, acc[ms][ns][r] + epilogue_side(p, epi, b, oy * p.osy + q.ooy, ox * p.osx + q.oox, n), addold);
             }
         }
@@ -191,19 +198,19 @@ __global__ void __launch_bounds__(256) conv_igemm_kernel(const ramnet_conv_desc 
 
 template <int BM, int BN, int WM, int WN>
 static int launch_cfg(const ramnet_conv_desc &d, const ConvCommon &qc, const ConvClasses &qk, int max_tiles, hipStream_t st) {
-    auto kern = conv_igemm_kernel<BM, BN, WM, WN>;
+    auto kern = d.active ? conv_igemm_kernel<BM, BN, WM, WN, true> : conv_igemm_kernel<BM, BN, WM, WN>;
     const size_t lds = ((size_t)qc.patch_floats + 2 * BN * LDP) * sizeof(float);
-    static size_t lds_set = 0;   // raise the dynamic-LDS cap once per instantiation
-    if (lds > lds_set) {
+    static size_t lds_set[2] = {0, 0};   // raise the dynamic-LDS cap once per instantiation
+    if (lds > lds_set[d.active != nullptr]) {
         RAMNET_FULL_LDS((kern));
-        lds_set = 160 * 1024;
+        lds_set[d.active != nullptr] = 160 * 1024;
     }
     if (lds > 160 * 1024) {
         set_error("conv patch does not fit LDS (%zu bytes)", lds);
         return RAMNET_E_UNSUPPORTED;
     }
     dim3 grid(max_tiles * d.B, qc.CoutPad / BN, qc.nclass);
-    note_kernel("conv_igemm_kernel<%d,%d,%d,%d>", BM, BN, WM, WN);
+    note_kernel(d.active ? "conv_igemm_kernel<%d,%d,%d,%d,masked>" : "conv_igemm_kernel<%d,%d,%d,%d>", BM, BN, WM, WN);
     hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, d, qc, qk);
     RAMNET_LAUNCH_CHECK();
     return 0;
@@ -235,6 +242,11 @@ static int check_desc(const ramnet_conv_desc &d) {
         RAMNET_CHECK_ARG(px * ld < (1ull << 32));
     }
     RAMNET_CHECK_ARG(d.frame >= 0);
+    // per-sample update masks: the cell epilogues only, on the families that implement them (ramnet_hip.h)
+    if (d.active) RAMNET_CHECK_ARG((d.epi == RAMNET_EPI_SIGMOID || d.epi == RAMNET_EPI_SIGMOID_HR || d.epi == RAMNET_EPI_GRU_BLEND ||
+                                    (d.epi == RAMNET_EPI_LSTM && d.e0)) && d.frame == 0 && d.out_s2d == 0 &&
+                                   (d.algo == RAMNET_ALGO_DIRECT || d.algo == RAMNET_ALGO_WINOGRAD || d.algo == RAMNET_ALGO_WINOGRAD_2X4 ||
+                                    d.algo == RAMNET_ALGO_WINOGRAD_2X4_SPLIT));
     if (d.frame > 0) RAMNET_CHECK_ARG(d.e0 && d.e1 && (d.epi == RAMNET_EPI_RELU || d.epi == RAMNET_EPI_LINEAR));
     return 0;
 }
@@ -247,7 +259,7 @@ static int launch_classes(const ramnet_conv_desc *ds, int n, hipStream_t st) {
         if (rc) return rc;
         RAMNET_CHECK_ARG(ds[i].x0 == d.x0 && ds[i].w == d.w && ds[i].out == d.out && ds[i].stride == d.stride &&
                          ds[i].Cout == d.Cout && ds[i].epi == d.epi && ds[i].osy == d.osy && ds[i].osx == d.osx &&
-                         ds[i].B == d.B && ds[i].in_mode == d.in_mode);
+                         ds[i].B == d.B && ds[i].in_mode == d.in_mode && ds[i].active == d.active);
     }
     const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
     ConvCommon qc;

@@ -52,7 +52,8 @@ template <int TX> struct RGeom {
 // NF = 32-channel output blocks per workgroup: 2 (64 channels), or 1 for launches that would otherwise put fewer than one
 // workgroup on a CU (batch-1 streaming on the coarse maps: 44-88 workgroups of 32-64 chunks each): twice the workgroups, half the
 // MFMAs per chunk and wave — the same transform work per workgroup, but the launch is latency-bound there, not pipe-bound.
-template <int TX, int SP, int MODE, int NF = 2>
+// MASK: cell launch with a per-sample update mask (ramnet_conv_desc.active; separate instantiations of the concatenated input modes)
+template <int TX, int SP, int MODE, int NF = 2, bool MASK = false>
 __global__ void __launch_bounds__(256, 2) conv_wino_r_kernel(const ramnet_conv_desc p, const WinoParams q) {
     // NF = 1: the exchange buffer holds 32 columns (37 KB instead of 70 KB of LDS), so that these workgroups — of DIFFERENT launches:
     // the per-scale update chains of the streaming runtime run side by side — share a CU with the decoders' (building it for three
@@ -223,6 +224,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r_kernel(const ramnet_conv_d
         return make_float4(t0.x + t1.x + t2.x, t0.y + t1.y + t2.y, t0.z + t1.z + t2.z, t0.w + t1.w + t2.w);
     };
     const int epi = p.epi;
+    const bool act = !MASK || sample_active(p, b);         // (b: one image per workgroup)
     if (NF == 2 && q.vec4 && epi == RAMNET_EPI_LSTM) {
         // ConvLSTM cell (submodules.py:346-358): the block's 64 columns are 16 hidden channels x gates (i, f, o, g)
         const int C = p.Cout;
@@ -250,6 +252,15 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r_kernel(const ramnet_conv_d
             if (!ok[i]) continue;
             const int pxl = pxlv[i];
             const size_t pix = pixv[i];
+            if (MASK && !act) {          // inactive sample: h' = h, c' = c (copies), gates 0
+                st4(p.out + pix * p.ldo + chn, ld4(p.e0 + pix * p.lde0 + chn));
+                st4(p.o1 + pix * p.ldo1 + chn, cpv[i]);
+                if (p.o2) {
+                    float *g = p.o2 + pix * p.ldo2 + chn;
+                    st4(g, f4zero()), st4(g + C, f4zero()), st4(g + 2 * C, f4zero()), st4(g + 3 * C, f4zero());
+                }
+                continue;
+            }
             const float4 ai = f4add(out4(pxl, qd * 4), bi), af = f4add(out4(pxl, 16 + qd * 4), bf);
             const float4 ao = f4add(out4(pxl, 32 + qd * 4), bo), ag = f4add(out4(pxl, 48 + qd * 4), bg);
             const float4 gi = make_float4(sigmoidf_(ai.x), sigmoidf_(ai.y), sigmoidf_(ai.z), sigmoidf_(ai.w));
@@ -372,9 +383,11 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r_kernel(const ramnet_conv_d
                         if (relu) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
                     } else if (K == 4) {
                         v = make_float4(sigmoidf_(v.x), sigmoidf_(v.y), sigmoidf_(v.z), sigmoidf_(v.w));
+                        if (MASK && !act) v = f4zero();      // inactive sample: u = r = 0
                     } else if (K == 5) {      // gates: the reset gate's quads also leave h.r (RAMNET_EPI_SIGMOID_HR; other quads: offset WOOB, h = 0)
                         v = make_float4(sigmoidf_(v.x), sigmoidf_(v.y), sigmoidf_(v.z), sigmoidf_(v.w));
-                        const float4 h = eb[i];
+                        if (MASK && !act) v = f4zero();      // inactive sample: u = r = 0, h.r = 0
+                        const float4 h = (MASK && !act) ? f4zero() : eb[i];
                         bst(r_o1, (o_o1 + j * s_o1) | bad[j], make_float4(h.x * v.x, h.y * v.y, h.z * v.z, h.w * v.w));
                     } else if (K == 1) {
                         v = make_float4(fmaxf(v.x + ea[i].x, 0.f), fmaxf(v.y + ea[i].y, 0.f), fmaxf(v.z + ea[i].z, 0.f), fmaxf(v.w + ea[i].w, 0.f));
@@ -385,9 +398,14 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r_kernel(const ramnet_conv_d
                         v = make_float4(old.x + g.x * r.x, old.y + g.y * r.y, old.z + g.z * r.z, old.w + g.w * r.w);
                     } else {
                         const float4 o = make_float4(tanhf_(v.x), tanhf_(v.y), tanhf_(v.z), tanhf_(v.w)), u = ea[i], h = eb[i];
-                        bst(r_o1, (o_o1 + j * s_o1) | bad[j], o);
-                        v = make_float4(h.x * (1.0f - u.x) + o.x * u.x, h.y * (1.0f - u.y) + o.y * u.y, h.z * (1.0f - u.z) + o.z * u.z,
-                                        h.w * (1.0f - u.w) + o.w * u.w);
+                        if (MASK && !act) {          // inactive sample: h' = h (a copy), o = 0
+                            bst(r_o1, (o_o1 + j * s_o1) | bad[j], f4zero());
+                            v = h;
+                        } else {
+                            bst(r_o1, (o_o1 + j * s_o1) | bad[j], o);
+                            v = make_float4(h.x * (1.0f - u.x) + o.x * u.x, h.y * (1.0f - u.y) + o.y * u.y, h.z * (1.0f - u.z) + o.z * u.z,
+                                            h.w * (1.0f - u.w) + o.w * u.w);
+                        }
                     }
                     bst(r_out, oo[i], v);
                 }
@@ -415,7 +433,11 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r_kernel(const ramnet_conv_d
         }
         const size_t pix = ((size_t)b * p.HoF + (oy * p.osy + p.ooy)) * p.WoF + (ox * p.osx + p.oox);
         const bool addold = epilogue_addold(p, oy * p.osy + p.ooy, ox * p.osx + p.oox);
-        if (q.vec4) {
+        if (MASK && !act) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (nq + e < p.Cout) epilogue_inactive(p, epi, pix, nq + e);
+        } else if (q.vec4) {
             epilogue_store4(p, epi, pix, nq, y, addold);
         } else {                // channel counts / strides that rule out 16-byte accesses
             const float ys[4] = {y.x, y.y, y.z, y.w};
@@ -584,8 +606,8 @@ int launch_wino(const ramnet_conv_desc &d, hipStream_t st) {
     dim3 grid(gridx, q.ksplit);
     const size_t lds = (size_t)(nf == 1 ? 4 * 2 * 32 * (32 + 4) : RO_FLOATS) * sizeof(float);       // (the two patch buffers, 2 x 2 planes, and the scratch cells are smaller)
     // one instantiation per (tile shape, sparse mode, input mode) that occurs: the kernel body has no run-time mode branches
-    const int key = (tall ? 0 : 1000) + q.sparse * 100 + d.in_mode + (nf == 1 ? 10000 : 0);
-    note_kernel("conv_wino_r_kernel<%d,%d,%d,%d>", tall ? 2 : 8, q.sparse, d.in_mode, nf);
+    const int key = (tall ? 0 : 1000) + q.sparse * 100 + d.in_mode + (nf == 1 ? 10000 : 0) + (d.active ? 100000 : 0);
+    note_kernel(d.active ? "conv_wino_r_kernel<%d,%d,%d,%d,masked>" : "conv_wino_r_kernel<%d,%d,%d,%d>", tall ? 2 : 8, q.sparse, d.in_mode, nf);
 #define RAMNET_GO(TXv, SPv, MDv)                                                                        \
     case ((TXv) == 2 ? 0 : 1000) + (SPv) * 100 + (MDv):                                                 \
         RAMNET_FULL_LDS((conv_wino_r_kernel<TXv, SPv, MDv>));                                           \
@@ -596,12 +618,18 @@ int launch_wino(const ramnet_conv_desc &d, hipStream_t st) {
         RAMNET_FULL_LDS((conv_wino_r_kernel<TXv, SPv, MDv, 1>));                                        \
         hipLaunchKernelGGL((conv_wino_r_kernel<TXv, SPv, MDv, 1>), grid, dim3(256), lds, st, d, q);     \
         break;
+#define RAMNET_GOM(TXv, MDv, NFv)                                                                       \
+    case 100000 + (NFv == 1 ? 10000 : 0) + ((TXv) == 2 ? 0 : 1000) + (MDv):                             \
+        RAMNET_FULL_LDS((conv_wino_r_kernel<TXv, 0, MDv, NFv, true>));                                  \
+        hipLaunchKernelGGL((conv_wino_r_kernel<TXv, 0, MDv, NFv, true>), grid, dim3(256), lds, st, d, q); \
+        break;
 #define RAMNET_GO_TX(TXv)                                                                               \
     RAMNET_GO(TXv, 0, RAMNET_IN_PLAIN) RAMNET_GO(TXv, 0, RAMNET_IN_CAT) RAMNET_GO(TXv, 0, RAMNET_IN_CAT_MUL)        \
     RAMNET_GO(TXv, 0, RAMNET_IN_RELUMASK) RAMNET_GO(TXv, 0, RAMNET_IN_S2D) RAMNET_GO(TXv, 1, RAMNET_IN_S2D)         \
     RAMNET_GO(TXv, 2, RAMNET_IN_PLAIN) RAMNET_GO(TXv, 2, RAMNET_IN_RELUMASK)                                        \
     RAMNET_GO1(TXv, 0, RAMNET_IN_PLAIN) RAMNET_GO1(TXv, 0, RAMNET_IN_CAT) RAMNET_GO1(TXv, 0, RAMNET_IN_CAT_MUL)     \
-    RAMNET_GO1(TXv, 0, RAMNET_IN_S2D) RAMNET_GO1(TXv, 1, RAMNET_IN_S2D) RAMNET_GO1(TXv, 0, RAMNET_IN_RELUMASK)
+    RAMNET_GO1(TXv, 0, RAMNET_IN_S2D) RAMNET_GO1(TXv, 1, RAMNET_IN_S2D) RAMNET_GO1(TXv, 0, RAMNET_IN_RELUMASK)           \
+    RAMNET_GOM(TXv, RAMNET_IN_CAT, 2) RAMNET_GOM(TXv, RAMNET_IN_CAT_MUL, 2) RAMNET_GOM(TXv, RAMNET_IN_CAT, 1) RAMNET_GOM(TXv, RAMNET_IN_CAT_MUL, 1)
     switch (key) {
         RAMNET_GO_TX(2)
         RAMNET_GO_TX(8)
@@ -609,6 +637,7 @@ int launch_wino(const ramnet_conv_desc &d, hipStream_t st) {
         RAMNET_CHECK_ARG(!"conv_wino_r: unsupported (sparse, input mode) combination");
     }
 #undef RAMNET_GO_TX
+#undef RAMNET_GOM
 #undef RAMNET_GO1
 #undef RAMNET_GO
     RAMNET_LAUNCH_CHECK();

@@ -55,7 +55,8 @@ template <int TXG> struct R6Geom {
     static_assert(PH * PW * 2 <= 768, "three patch slots per thread");
 };
 
-template <int TXG, int MODE>
+// MASK: cell launch with a per-sample update mask (ramnet_conv_desc.active; separate instantiations of the concatenated input modes)
+template <int TXG, int MODE, bool MASK = false>
 __global__ void __launch_bounds__(256, 2) conv_wino_r6_kernel(const ramnet_conv_desc p, const WinoParams q) {
     constexpr int NF = 1;                        // 32-channel output blocks per workgroup (the index algebra below keeps the general form)
     constexpr int RO_LD = NF * 32 + 4;           // row of the exchange buffer [wave 4][column 4][tile 32][channels + pad]
@@ -292,6 +293,7 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r6_kernel(const ramnet_conv_
     // even rows t0 + t1 + t2, odd rows t1 - t2 - t3 = r0 + s r1 + s r2 with the first row and the sign selected by the parity (same sums,
     // same order).  The launcher only selects this kernel for 16-byte-accessible operands (q.vec4), unit output strides and images < 2 GB.
     const int epi = p.epi;
+    const bool act = !MASK || sample_active(p, b);         // (b: one image per workgroup)
     constexpr int NI = 4, RSTEP = 32 / RTW;                   // pixels per half; rows between consecutive pixels of a thread
     const int px0 = (tid >> 3) % RTW, py0 = (tid >> 3) / RTW;
     const bool colok = nok && ox0 + px0 < p.Wo;
@@ -353,9 +355,11 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r6_kernel(const ramnet_conv_
                     if (relu) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
                 } else if (K == 4) {
                     v = make_float4(sigmoidf_(v.x), sigmoidf_(v.y), sigmoidf_(v.z), sigmoidf_(v.w));
+                    if (MASK && !act) v = f4zero();      // inactive sample: u = r = 0
                 } else if (K == 5) {      // gates: the reset gate's quads also leave h.r (RAMNET_EPI_SIGMOID_HR; other quads: offset WOOB, h = 0)
                     v = make_float4(sigmoidf_(v.x), sigmoidf_(v.y), sigmoidf_(v.z), sigmoidf_(v.w));
-                    const float4 h = eb[i];
+                    if (MASK && !act) v = f4zero();      // inactive sample: u = r = 0, h.r = 0
+                    const float4 h = (MASK && !act) ? f4zero() : eb[i];
                     bst(r_o1, (o_o1 + (half * NI + i) * s_o1) | bad[half * NI + i], make_float4(h.x * v.x, h.y * v.y, h.z * v.z, h.w * v.w));
                 } else if (K == 1) {
                     v = make_float4(fmaxf(v.x + ea[i].x, 0.f), fmaxf(v.y + ea[i].y, 0.f), fmaxf(v.z + ea[i].z, 0.f), fmaxf(v.w + ea[i].w, 0.f));
@@ -366,9 +370,14 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r6_kernel(const ramnet_conv_
                     v = make_float4(old.x + g.x * r.x, old.y + g.y * r.y, old.z + g.z * r.z, old.w + g.w * r.w);
                 } else {
                     const float4 o = make_float4(tanhf_(v.x), tanhf_(v.y), tanhf_(v.z), tanhf_(v.w)), u = ea[i], h = eb[i];
-                    bst(r_o1, (o_o1 + (half * NI + i) * s_o1) | bad[half * NI + i], o);
-                    v = make_float4(h.x * (1.0f - u.x) + o.x * u.x, h.y * (1.0f - u.y) + o.y * u.y, h.z * (1.0f - u.z) + o.z * u.z,
-                                    h.w * (1.0f - u.w) + o.w * u.w);
+                    if (MASK && !act) {          // inactive sample: h' = h (a copy), o = 0
+                        bst(r_o1, (o_o1 + (half * NI + i) * s_o1) | bad[half * NI + i], f4zero());
+                        v = h;
+                    } else {
+                        bst(r_o1, (o_o1 + (half * NI + i) * s_o1) | bad[half * NI + i], o);
+                        v = make_float4(h.x * (1.0f - u.x) + o.x * u.x, h.y * (1.0f - u.y) + o.y * u.y, h.z * (1.0f - u.z) + o.z * u.z,
+                                        h.w * (1.0f - u.w) + o.w * u.w);
+                    }
                 }
                 bst(r_out, oo[i], v);
             }
@@ -555,7 +564,7 @@ int launch_wino6(const ramnet_conv_desc &d, hipStream_t st) {
         lo = lo > d.lde1 ? lo : d.lde1;
         RAMNET_CHECK_ARG((unsigned long long)d.HoF * d.WoF * lo * 4ull < (unsigned long long)WOOB);
     }
-    note_kernel("conv_wino_r6_kernel<%d,%d>", txg, d.in_mode);
+    note_kernel(d.active ? "conv_wino_r6_kernel<%d,%d,masked>" : "conv_wino_r6_kernel<%d,%d>", txg, d.in_mode);
     size_t probe_pad = 0;                       // (probe builds: RAMNET_PROBE_LDS_KB pads the allocation — 90: ONE workgroup per CU)
 #ifdef RAMNET_PROBE
     if (const char *e = getenv("RAMNET_PROBE_LDS_KB")) probe_pad = (size_t)atoi(e) * 1024;
@@ -566,10 +575,17 @@ int launch_wino6(const ramnet_conv_desc &d, hipStream_t st) {
         RAMNET_FULL_LDS((conv_wino_r6_kernel<TXv, MDv>));                                                           \
         hipLaunchKernelGGL((conv_wino_r6_kernel<TXv, MDv>), grid, dim3(256), (ex > pf ? ex : pf) + probe_pad, st, d, q); \
     } break;
+#define RAMNET_GO6M(TXv, MDv)                                                                                       \
+    case 100000 + (TXv) * 100 + (MDv): {                                                                            \
+        const size_t pf = (size_t)(2 * R6Geom<TXv>::PFLOATS + 256 * 4) * sizeof(float);                             \
+        RAMNET_FULL_LDS((conv_wino_r6_kernel<TXv, MDv, true>));                                                     \
+        hipLaunchKernelGGL((conv_wino_r6_kernel<TXv, MDv, true>), grid, dim3(256), (ex > pf ? ex : pf) + probe_pad, st, d, q); \
+    } break;
 #define RAMNET_GO6_TX(TXv)                                                                                          \
+    RAMNET_GO6M(TXv, RAMNET_IN_CAT) RAMNET_GO6M(TXv, RAMNET_IN_CAT_MUL)                                             \
     RAMNET_GO6(TXv, RAMNET_IN_PLAIN) RAMNET_GO6(TXv, RAMNET_IN_CAT) RAMNET_GO6(TXv, RAMNET_IN_CAT_MUL) RAMNET_GO6(TXv, RAMNET_IN_RELUMASK) \
     RAMNET_GO6(TXv, RAMNET_IN_S2D)
-    switch (txg * 100 + d.in_mode) {
+    switch (txg * 100 + d.in_mode + (d.active ? 100000 : 0)) {
         RAMNET_GO6_TX(4)
         RAMNET_GO6_TX(2)
         RAMNET_GO6_TX(8)
@@ -577,6 +593,7 @@ int launch_wino6(const ramnet_conv_desc &d, hipStream_t st) {
         RAMNET_CHECK_ARG(!"conv_wino_r6: unsupported (tile, input mode) combination");
     }
 #undef RAMNET_GO6_TX
+#undef RAMNET_GO6M
 #undef RAMNET_GO6
     RAMNET_LAUNCH_CHECK();
     return 0;

@@ -132,7 +132,8 @@ __device__ constexpr OpRef op_at(int P, int k) {
     return {-1, 0, 0, 0};
 }
 
-template <int TXG, int MODE>
+// MASK: cell launch with a per-sample update mask (ramnet_conv_desc.active; separate instantiations of the concatenated input modes)
+template <int TXG, int MODE, bool MASK = false>
 __global__ void __launch_bounds__(256, 1) conv_wino_r6s_kernel(const ramnet_conv_desc p, const WinoParams q) {
     constexpr int RO_LD = 64 + 4;                    // row of the exchange buffer [wave 4][column 4][tile 32][64 channels + pad]: both halves at once
     using G = R6SGeom<TXG>;
@@ -384,6 +385,7 @@ __global__ void __launch_bounds__(256, 1) conv_wino_r6s_kernel(const ramnet_conv
     auto bld = [](decltype(wino_rsrc(nullptr, 0u)) r, unsigned off) { return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0)); };
     auto bst = [](decltype(wino_rsrc(nullptr, 0u)) r, unsigned off, float4 x) { __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x), r, (int)off, 0, 0); };
     const int epi = p.epi;
+    const bool act = !MASK || sample_active(p, b);         // (b: one image per workgroup)
     // 0: linear / ReLU (+ beta * old), 4: sigmoid, 5: sigmoid + h.r (gates), 1: residual + ReLU, 2: GRU blend, 3: GRU backward stage B, 6: out_s2d scatter
     const int kind = q.s2d_shift ? 6 : epi == RAMNET_EPI_GRU_BLEND ? 2 : epi == RAMNET_EPI_RES_RELU ? 1 : (epi == RAMNET_EPI_GRU_BWD && n0 >= p.Cout / 2) ? 3
                    : epi == RAMNET_EPI_SIGMOID ? 4 : epi == RAMNET_EPI_SIGMOID_HR ? 5 : 0;      // (GRU_BWD: a block lies in one half: launcher)
@@ -486,9 +488,11 @@ __global__ void __launch_bounds__(256, 1) conv_wino_r6s_kernel(const ramnet_conv
                     if (relu) x = make_float4(fmaxf(x.x, 0.f), fmaxf(x.y, 0.f), fmaxf(x.z, 0.f), fmaxf(x.w, 0.f));
                 } else if (K == 4) {
                     x = make_float4(sigmoidf_(x.x), sigmoidf_(x.y), sigmoidf_(x.z), sigmoidf_(x.w));
+                    if (MASK && !act) x = f4zero();      // inactive sample: u = r = 0
                 } else if (K == 5) {      // gates: the reset gate's quads also leave h.r (RAMNET_EPI_SIGMOID_HR; other quads: offset WOOB, h = 0)
                     x = make_float4(sigmoidf_(x.x), sigmoidf_(x.y), sigmoidf_(x.z), sigmoidf_(x.w));
-                    const float4 h = eb[FH][j];
+                    if (MASK && !act) x = f4zero();      // inactive sample: u = r = 0, h.r = 0
+                    const float4 h = (MASK && !act) ? f4zero() : eb[FH][j];
                     bst(r_o1, (o1 + j * s1) | bad[j], make_float4(h.x * x.x, h.y * x.y, h.z * x.z, h.w * x.w));
                 } else if (K == 1) {
                     const float4 e = ea[FH][j];
@@ -500,9 +504,14 @@ __global__ void __launch_bounds__(256, 1) conv_wino_r6s_kernel(const ramnet_conv
                     x = make_float4(old.x + gq.x * r.x, old.y + gq.y * r.y, old.z + gq.z * r.z, old.w + gq.w * r.w);
                 } else if (K == 2) {
                     const float4 o = make_float4(tanhf_(x.x), tanhf_(x.y), tanhf_(x.z), tanhf_(x.w)), u = ea[FH][j], h = eb[FH][j];
-                    bst(r_o1, (o1 + j * s1) | bad[j], o);
-                    x = make_float4(h.x * (1.0f - u.x) + o.x * u.x, h.y * (1.0f - u.y) + o.y * u.y, h.z * (1.0f - u.z) + o.z * u.z,
-                                    h.w * (1.0f - u.w) + o.w * u.w);
+                    if (MASK && !act) {          // inactive sample: h' = h (a copy), o = 0
+                        bst(r_o1, (o1 + j * s1) | bad[j], f4zero());
+                        x = h;
+                    } else {
+                        bst(r_o1, (o1 + j * s1) | bad[j], o);
+                        x = make_float4(h.x * (1.0f - u.x) + o.x * u.x, h.y * (1.0f - u.y) + o.y * u.y, h.z * (1.0f - u.z) + o.z * u.z,
+                                        h.w * (1.0f - u.w) + o.w * u.w);
+                    }
                 }
                 bst(r_out, (oo + j * so) | bad[j], x);
             }
@@ -675,21 +684,28 @@ int launch_wino6s(const ramnet_conv_desc &d, hipStream_t st) {
         lo = lo > d.lde1 ? lo : d.lde1;
         RAMNET_CHECK_ARG((unsigned long long)d.HoF * d.WoF * lo * 4ull < (unsigned long long)WOOB);
     }
-    note_kernel("conv_wino_r6s_kernel<%d,%d>", txg, d.in_mode);
+    note_kernel(d.active ? "conv_wino_r6s_kernel<%d,%d,masked>" : "conv_wino_r6s_kernel<%d,%d>", txg, d.in_mode);
 #define RAMNET_GO6S(TXv, MDv)                                                                                       \
     case (TXv) * 100 + (MDv): {                                                                                     \
         const size_t pf = (size_t)(2 * R6SGeom<TXv>::PFLOATS + 256 * 4) * sizeof(float);                            \
         RAMNET_FULL_LDS((conv_wino_r6s_kernel<TXv, MDv>));                                                          \
         hipLaunchKernelGGL((conv_wino_r6s_kernel<TXv, MDv>), grid, dim3(256), (ex > pf ? ex : pf), st, d, q);       \
     } break;
+#define RAMNET_GO6SM(TXv, MDv)                                                                                      \
+    case 100000 + (TXv) * 100 + (MDv): {                                                                            \
+        const size_t pf = (size_t)(2 * R6SGeom<TXv>::PFLOATS + 256 * 4) * sizeof(float);                            \
+        RAMNET_FULL_LDS((conv_wino_r6s_kernel<TXv, MDv, true>));                                                    \
+        hipLaunchKernelGGL((conv_wino_r6s_kernel<TXv, MDv, true>), grid, dim3(256), (ex > pf ? ex : pf), st, d, q); \
+    } break;
 #if RAMNET_ABL6S
-#define RAMNET_GO6S_TX(TXv) RAMNET_GO6S(TXv, RAMNET_IN_CAT)
+#define RAMNET_GO6S_TX(TXv) RAMNET_GO6S(TXv, RAMNET_IN_CAT) RAMNET_GO6SM(TXv, RAMNET_IN_CAT)
 #else
 #define RAMNET_GO6S_TX(TXv)                                                                                         \
+    RAMNET_GO6SM(TXv, RAMNET_IN_CAT) RAMNET_GO6SM(TXv, RAMNET_IN_CAT_MUL)                                           \
     RAMNET_GO6S(TXv, RAMNET_IN_PLAIN) RAMNET_GO6S(TXv, RAMNET_IN_CAT) RAMNET_GO6S(TXv, RAMNET_IN_CAT_MUL) RAMNET_GO6S(TXv, RAMNET_IN_RELUMASK) \
     RAMNET_GO6S(TXv, RAMNET_IN_S2D)
 #endif
-    switch (txg * 100 + d.in_mode) {
+    switch (txg * 100 + d.in_mode + (d.active ? 100000 : 0)) {
         RAMNET_GO6S_TX(4)
         RAMNET_GO6S_TX(2)
 #if !RAMNET_ABL6S
@@ -699,6 +715,7 @@ int launch_wino6s(const ramnet_conv_desc &d, hipStream_t st) {
         RAMNET_CHECK_ARG(!"conv_wino_r6s: unsupported (tile, input mode) combination");
     }
 #undef RAMNET_GO6S_TX
+#undef RAMNET_GO6SM
 #undef RAMNET_GO6S
     RAMNET_LAUNCH_CHECK();
     return 0;

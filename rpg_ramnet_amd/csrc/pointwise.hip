@@ -872,18 +872,34 @@ __global__ void gru_bwd_b_kernel(float *__restrict__ dxhr, const float *__restri
 }
 
 // gates = activated [i|f|o|g] (4C per pixel), natural order.
+// MASK (ramnet_lstm_bwd_masked): a pixel of an inactive sample (active[pix / hw] == 0) passes dc' to dc_prev and dh' to the h half of
+// dxh [npix][2C], with zero gate pre-activation gradients; every other pixel zeroes its row of dxh (a beta = 1 backward-data launch adds
+// the convolution's part there)
+template <bool MASK>
 __global__ void lstm_bwd_kernel(const float *__restrict__ gates, const float *__restrict__ cprev, const float *__restrict__ cnew,
                                 const float *__restrict__ dhn, const float *__restrict__ dcn, float *__restrict__ dpre,
-                                float *__restrict__ dcprev, size_t npix, int C) {
+                                float *__restrict__ dcprev, size_t npix, int C, const int *__restrict__ active = nullptr,
+                                float *__restrict__ dxh = nullptr, int hw = 1) {
     const int C4 = C / 4;
     const size_t total = npix * C4;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t pix = i / C4;
         const int c = (int)(i - pix * C4) * 4;
         const float *gp = gates + pix * 4 * C + c;
+        const float4 dh = dhn ? ld4(dhn + pix * C + c) : f4zero(), dc = dcn ? ld4(dcn + pix * C + c) : f4zero();
+        if (MASK) {
+            const bool act = active[pix / (size_t)hw] != 0;
+            st4(dxh + pix * 2 * C + c, f4zero());
+            st4(dxh + pix * 2 * C + C + c, act ? f4zero() : dh);
+            if (!act) {
+                float *op = dpre + pix * 4 * C + c;
+                st4(op, f4zero()), st4(op + C, f4zero()), st4(op + 2 * C, f4zero()), st4(op + 3 * C, f4zero());
+                st4(dcprev + pix * C + c, dc);
+                continue;
+            }
+        }
         const float4 gi = ld4(gp), gf = ld4(gp + C), go = ld4(gp + 2 * C), gc = ld4(gp + 3 * C);
         const float4 cp = cprev ? ld4(cprev + pix * C + c) : f4zero(), cn = ld4(cnew + pix * C + c);
-        const float4 dh = dhn ? ld4(dhn + pix * C + c) : f4zero(), dc = dcn ? ld4(dcn + pix * C + c) : f4zero();
         float4 pi, pf, po, pg, dp;
 #define RN_ONE(f)                                                   \
     {                                                               \
@@ -1264,7 +1280,17 @@ extern "C" int ramnet_gru_bwd_b(const float *dxhr, const float *ur, const float 
 extern "C" int ramnet_lstm_bwd(const float *gates, const float *cprev, const float *cnew, const float *dhn, const float *dcn,
                                float *dpre, float *dcprev, size_t npix, int C, void *stream) {
     RAMNET_CHECK_ARG(gates && cnew && dpre && dcprev && C % 4 == 0);
-    hipLaunchKernelGGL(lstm_bwd_kernel, dim3(grid_for(npix * (C / 4))), dim3(256), 0, (hipStream_t)stream, gates, cprev, cnew, dhn, dcn, dpre, dcprev, npix, C);
+    hipLaunchKernelGGL(lstm_bwd_kernel<false>, dim3(grid_for(npix * (C / 4))), dim3(256), 0, (hipStream_t)stream, gates, cprev, cnew, dhn, dcn, dpre, dcprev, npix, C,
+                       nullptr, nullptr, 1);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ramnet_lstm_bwd_masked(const float *gates, const float *cprev, const float *cnew, const float *dhn, const float *dcn,
+                                      const int *active, float *dpre, float *dcprev, float *dxh, size_t npix, int hw, int C, void *stream) {
+    RAMNET_CHECK_ARG(gates && cnew && dpre && dcprev && active && dxh && hw > 0 && npix % (size_t)hw == 0 && C % 4 == 0);
+    hipLaunchKernelGGL(lstm_bwd_kernel<true>, dim3(grid_for(npix * (C / 4))), dim3(256), 0, (hipStream_t)stream, gates, cprev, cnew, dhn, dcn, dpre, dcprev, npix, C,
+                       active, dxh, hw);
     RAMNET_LAUNCH_CHECK();
     return 0;
 }

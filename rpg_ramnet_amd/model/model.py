@@ -160,20 +160,40 @@ class ERGB2DepthRecurrent(BaseERGB2Depth):
                        else torch.zeros(shp, device=self.gpu))
         return out
 
-    def update_events(self, events, states, lstm_state=None, out=None):
+    def update_events(self, events, states, lstm_state=None, out=None, active=None):
         """Asynchronous primitive (irregular schedules, BASELINE configs[3]): fold ONE event voxel grid [B,Ce,H,W] into the
         shared multi-scale state.  `states`: list returned by init_states()/a previous update (NHWC buffers or the
         NCHW-shaped views forward() returns).  Returns (new_states, lstm_state); nothing is modified in place.
         Equivalent to one iteration of the k-loop of model.py:176-195 without the decode.  out: optional per-scale NHWC buffers (a second
-        init_states() set, never the one passed as `states`) that receive — and are returned as — the new state."""
+        init_states() set, never the one passed as `states`) that receive — and are returned as — the new state.
+        active: optional per-sample update mask [B] (bool / integer, host or device; a device mask is never read on the host, so a
+        captured graph replays with its current contents): sample b with active[b] == 0 keeps its state bit for bit and its gradient
+        passes through unchanged (ConvGRU / ConvLSTM state, plain-conv encoders, no batch-statistics norm)."""
         assert not bool(self.baseline), "baselines have no event branch (model.py:181-185)"
+        self._check_masked(active)
         st = [_state_nhwc(s, self.base_num_channels * 2 ** (i + 1)) for i, s in enumerate(states)]
-        return self.statenetphasedrecurrent.forward_events(ops.pack_input(events, self.gpu, self._crop_for(*events.shape[2:])), st, lstm_state, out=out)
+        return self.statenetphasedrecurrent.forward_events(ops.pack_input(events, self.gpu, self._crop_for(*events.shape[2:])), st, lstm_state, out=out,
+                                                           active=active)
 
-    def update_image(self, image, states, lstm_state=None, out=None):
-        """Fold ONE frame [B,Cr,H,W] into the shared state (model.py:196-213 without the decode)."""
+    def update_image(self, image, states, lstm_state=None, out=None, active=None):
+        """Fold ONE frame [B,Cr,H,W] into the shared state (model.py:196-213 without the decode).  active: as for update_events."""
+        self._check_masked(active)
         st = [_state_nhwc(s, self.base_num_channels * 2 ** (i + 1)) for i, s in enumerate(states)]
-        return self.statenetphasedrecurrent.forward_images(ops.pack_input(image, self.gpu, self._crop_for(*image.shape[2:])), st, lstm_state, out=out)
+        return self.statenetphasedrecurrent.forward_images(ops.pack_input(image, self.gpu, self._crop_for(*image.shape[2:])), st, lstm_state, out=out,
+                                                           active=active)
+
+    def _check_masked(self, active=True):
+        """Per-sample update masks need RAM-Net's wiring, plain-conv encoders and no batch-statistics norm (an inactive sample would
+        still move the batch statistics); anything else is refused before a launch."""
+        if active is None:
+            return
+        net = self.statenetphasedrecurrent
+        if bool(self.baseline):
+            raise NotImplementedError("per-sample update masks / irregular packages: not for the baseline wirings")
+        if net.recurrent_block_type != 'conv':
+            raise NotImplementedError("per-sample update masks / irregular packages: recurrent_block_type 'conv' only")
+        if net.norm in ('BN', 'IN'):
+            raise NotImplementedError("per-sample update masks / irregular packages: no BN / IN norm")
 
     def decode(self, states, frame_hw=None):
         """Depth prediction [B,1,H,W] in [0,1] from the current state (statenet.py:290-315).  frame_hw (full-frame mode): the (height,
@@ -272,6 +292,63 @@ class ERGB2DepthRecurrent(BaseERGB2Depth):
         for k in range(K + 1):
             emit(keys[k], preds[k], per_slot[k], {'encoders': [None] * n, 'state_comb': per_slot[k]})
 
+    def _forward_irregular(self, item, states, crop, decode, emit):
+        """A batch of IRREGULAR packages (MVSEC: each sample has its own number of event grids before its frame):
+        item['num_events'] = n_b per sample, events0..events{Kmax-1} with sample b's grids in the first n_b slots.  Per sample b the
+        result is that of n_b event updates, a decode ('events_last'), the frame update and a decode ('image_last').  Batched as in
+        _forward_time_batched: the event grids that any sample uses go through head + encoders as ONE chain; update k runs at batch B
+        with the mask num_events > k (the inactive samples keep their state bit for bit); the two decodes run as one chain."""
+        net, n = self.statenetphasedrecurrent, self.num_encoders
+        B = item['image'].shape[0]
+        cnt, kact = self._irregular_counts(item)
+        if kact > 0:
+            ev = _cat_batch([item['events{}'.format(k)].to(device=self.gpu, dtype=torch.float32) for k in range(kact)])
+            x = net.head_events(ops.pack_input(ev, self.gpu, crop))
+            feats = []
+            for i, enc in enumerate(net.encoders_events):
+                x = enc(x)
+                pm = ops.premask_relu_feature(x)
+                if i + 1 < n:
+                    fan = ops.TimeFan.apply(x, kact, pm)
+                    x, parts = fan[0], fan[1:]
+                else:
+                    parts = ops.TimeSplit.apply(x, kact, pm)
+                feats.append(parts)
+            for k in range(kact):
+                active = cnt > k
+                states = [net.state_combination_events[i](feats[i][k], states[i], None, active)[1] for i in range(n)]
+        s_ev = states
+        ximg = ops.pack_input(item['image'], self.gpu, crop)
+        s_img, _ = net.forward_images(ximg, states, None)
+        pair = net.state_combination == 'convlstm'
+        hof = (lambda s: s[0]) if pair else (lambda s: s)
+        joined = [torch.cat([hof(s_ev[i]), hof(s_img[i])], 0) for i in range(n)]
+        pred = decode([(h,) for h in joined] if pair else joined)
+        for key, p, ss in (('events_last', pred[:B], s_ev), ('image_last', pred[B:], s_img)):
+            emit(key, p, ss, {'encoders': [None] * n, 'state_comb': ss})
+
+    @staticmethod
+    def _irregular_counts(item):
+        """Checks an irregular package's schema (before any launch) -> (num_events, number of updates any sample takes)."""
+        B = item['image'].shape[0]
+        cnt = item['num_events']
+        kmax = 0
+        while 'events{}'.format(kmax) in item:
+            kmax += 1
+        if not torch.is_tensor(cnt) or cnt.device.type != 'cpu' or cnt.dtype.is_floating_point or cnt.is_complex() \
+                or cnt.dtype == torch.bool or cnt.dim() != 1 or cnt.shape[0] != B:
+            raise ValueError("num_events: a CPU integer tensor of shape [%d] expected" % B)
+        if any(k.startswith('events') and k[6:].isdigit() and int(k[6:]) >= kmax for k in item):
+            raise ValueError("events keys must be events0 .. events{Kmax-1} without gaps")
+        if bool((cnt < 0).any()) or bool((cnt > kmax).any()):
+            raise ValueError("num_events: every count must lie in [0, %d] (the number of events* grids in the item)" % kmax)
+        kact = int(cnt.max()) if B > 0 else 0          # updates past the largest count have no active sample: skipped
+        for k in range(kact):
+            e = item['events{}'.format(k)]
+            if e.dim() != 4 or e.shape[0] != B or tuple(e.shape[2:]) != tuple(item['image'].shape[2:]) or e.shape != item['events0'].shape:
+                raise ValueError("events{}: shape {} does not fit the batch / the frame / events0".format(k, tuple(e.shape)))
+        return cnt, kact
+
     def _si_request(self, item, keys, crop):
         """(weight, n_lambda, {key: device target}) when this package's trainer asked for the scale-invariant loss of the supervised
         predictions to be formed inside the prediction layer (`self._si_fuse`, set around the call by trainer.sequence_loss) and it can be:
@@ -295,6 +372,9 @@ class ERGB2DepthRecurrent(BaseERGB2Depth):
         net = self.statenetphasedrecurrent
         predictions_dict, super_state_dict, states_lstm_dict = {}, {}, {}
         crop = self._crop_for(*item['image'].shape[2:])
+        if 'num_events' in item:           # (irregular packages: refused before any launch)
+            self._check_masked()
+            self._irregular_counts(item)
         if prev_super_states is None:
             B, _, H, W = item['image'].shape
             states = self.init_states(B, H, W) if crop is None else self.init_states(B, crop.height_crop_size, crop.width_crop_size)
@@ -331,6 +411,16 @@ class ERGB2DepthRecurrent(BaseERGB2Depth):
                         u.record_stream(side)
             return pred
 
+        if 'num_events' in item:           # a batch of irregular packages
+            self._forward_irregular(item, states, crop, decode, emit)
+            if side is not None:
+                torch.cuda.current_stream().wait_stream(side)
+                if not torch.cuda.is_current_stream_capturing():
+                    for pred in predictions_dict.values():
+                        pred.record_stream(torch.cuda.current_stream())
+            super_state_dict['image'] = super_state_dict['image_last']
+            states_lstm_dict['image'] = states_lstm_dict['image_last']
+            return predictions_dict, super_state_dict, states_lstm_dict
         events_as_image = baseline == "ergb0" or (baseline == "e" and lc == "image")
         last = None
         if (ops.time_batching() and not bool(baseline) and K >= 2 and net.recurrent_block_type == 'conv'

@@ -261,8 +261,11 @@ class Taps:
         return cls._cache[key]
 
 
-def conv_launch(x0, taps, w, out, Cout, **kw):
+def conv_launch(x0, taps, w, out, Cout, active=None, **kw):
+    """active: optional [B] int32 DEVICE mask of a cell launch (ramnet_conv_desc.active; active_mask())."""
     d = _conv_desc(x0, taps, w, out, Cout, **kw)
+    if active is not None:
+        d.active = _p(active)
     H.check(H.lib().ramnet_conv_launch(C.byref(d), _st()), "ramnet_conv_launch")
 
 
@@ -1706,15 +1709,35 @@ def norm_act(x, layer, act=None, res=None):
     return NormAct.apply(x, g, b, res, mr[0], mr[1], ss[0], ss[1], use_input, _ACT_CODE[act])
 
 
+def active_mask(active, B, device):
+    """Per-sample update mask of a cell (bool / integer tensor [B], host or device) -> the [B] int32 device tensor the launches read.
+    A device mask is converted ON the device and never read on the host (a captured graph replays with whatever the mask then holds);
+    a host mask is checked and copied over."""
+    if active is None:
+        return None
+    if not torch.is_tensor(active) or active.dim() != 1 or active.shape[0] != B:
+        raise ValueError("active: a bool / integer tensor of shape [%d] expected, got %s" % (
+            B, tuple(active.shape) if torch.is_tensor(active) else type(active).__name__))
+    if active.dtype.is_floating_point or active.is_complex():
+        raise ValueError("active: a bool / integer tensor expected, got %s" % active.dtype)
+    if active.device.type == "cpu":
+        return (active != 0).to(torch.int32).to(device)
+    if active.device != device:
+        raise ValueError("active: on %s, the cell runs on %s" % (active.device, device))
+    return active if (active.dtype == torch.int32 and active.is_contiguous()) else (active != 0).to(torch.int32).contiguous()
+
+
 class GRUCell(Function):
     """ConvGRU (submodules.py:436-454) as two fused launches: [u|r] = sigmoid(W_ur*[x,h]) and
     h' = h(1-u) + tanh(W_o*[x, h.r]) u (concat, h.r, tanh and the blend never touch HBM separately)."""
 
     @staticmethod
-    def forward(ctx, x, h, wu, bu, wr, br, wo, bo, cp_ur, cp_o, out=None):
+    def forward(ctx, x, h, wu, bu, wr, br, wo, bo, cp_ur, cp_o, out=None, active=None):
         """out: optional NHWC buffer that receives h' (the streaming runtimes write the new state straight into their static
-        state buffers instead of copying it there)."""
+        state buffers instead of copying it there).  active: optional per-sample update mask [B] (active_mask): an inactive
+        sample keeps h bit for bit and its gradient passes through (u = r = o = 0 there: the backward below needs nothing else)."""
         x, h = dense(x), dense(h)
+        act = active_mask(active, x.shape[0], x.device)
         if x.shape != h.shape:       # the reference fails in torch.cat here (e.g. H, W not divisible by 2**num_encoders)
             raise RuntimeError("Sizes of tensors must match except in dimension 1. Expected %s but got %s (input vs state; "
                                "NHWC)" % (tuple(x.shape), tuple(h.shape)))
@@ -1723,9 +1746,10 @@ class GRUCell(Function):
         ur = torch.empty(B, Hh, W, 2 * Cc, device=x.device)
         hr = torch.empty(B, Hh, W, Cc, device=x.device) if (_GRU_HR and Cc % 4 == 0) else None
         if hr is not None:
-            conv_launch(x, taps, cp_ur.fwd(), ur, 2 * Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, bias=cp_ur.bias(), epi=H.EPI_SIGMOID_HR, e1=h, o1=hr)
+            conv_launch(x, taps, cp_ur.fwd(), ur, 2 * Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, bias=cp_ur.bias(), epi=H.EPI_SIGMOID_HR, e1=h, o1=hr,
+                        active=act)
         else:
-            conv_launch(x, taps, cp_ur.fwd(), ur, 2 * Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, bias=cp_ur.bias(), epi=H.EPI_SIGMOID)
+            conv_launch(x, taps, cp_ur.fwd(), ur, 2 * Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, bias=cp_ur.bias(), epi=H.EPI_SIGMOID, active=act)
         hn = torch.empty(B, Hh, W, Cc, device=x.device) if out is None else out
         if out is not None:
             if tuple(out.shape) != (B, Hh, W, Cc) or not out.is_contiguous() or out.dtype != torch.float32:
@@ -1736,10 +1760,11 @@ class GRUCell(Function):
         need = any(ctx.needs_input_grad)
         o = torch.empty_like(hn) if need else None
         if hr is not None:
-            conv_launch(x, taps, cp_o.fwd(), hn, Cc, x1=hr, in_mode=H.IN_CAT, C1=Cc, bias=cp_o.bias(), epi=H.EPI_GRU_BLEND, e0=ur, e1=h, o1=o)
+            conv_launch(x, taps, cp_o.fwd(), hn, Cc, x1=hr, in_mode=H.IN_CAT, C1=Cc, bias=cp_o.bias(), epi=H.EPI_GRU_BLEND, e0=ur, e1=h, o1=o,
+                        active=act)
         else:
             conv_launch(x, taps, cp_o.fwd(), hn, Cc, x1=h, xm=ur, xm_off=Cc, in_mode=H.IN_CAT_MUL, C1=Cc, bias=cp_o.bias(),
-                        epi=H.EPI_GRU_BLEND, e0=ur, e1=h, o1=o)
+                        epi=H.EPI_GRU_BLEND, e0=ur, e1=h, o1=o, active=act)
         ctx.cps = (cp_ur, cp_o)
         ctx.has_hr = hr is not None
         if need:
@@ -1782,7 +1807,7 @@ class GRUCell(Function):
         ws, bws = cp_ur.grad_ws(wino_ok=Cc % 32 == 0)
         _wgrad_cell(cp_ur, ws, [x, h, dpur], x, taps, dpur, 2 * Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, dbias=bws)
         conv_launch(dpur, tapsd, cp_ur.bwd(), dxh, 2 * Cc, beta=1.0)
-        return dxh[..., :Cc], dxh[..., Cc:], None, None, None, None, None, None, None, None, None
+        return dxh[..., :Cc], dxh[..., Cc:], None, None, None, None, None, None, None, None, None, None
 
 
 _TIME_BATCH = True
@@ -1952,8 +1977,11 @@ class LSTMCell(Function):
     """ConvLSTM (submodules.py:318-358): one launch; the gate non-linearities and the cell update are the epilogue."""
 
     @staticmethod
-    def forward(ctx, x, h, c, w, b, cp, out_h=None, out_c=None):
+    def forward(ctx, x, h, c, w, b, cp, out_h=None, out_c=None, active=None):
+        """active: optional per-sample update mask [B] (active_mask): an inactive sample keeps (h, c) bit for bit, its gradients pass
+        through (ramnet_lstm_bwd_masked)."""
         x, h, c = dense(x), dense(h), dense(c)
+        act = active_mask(active, x.shape[0], x.device)
         if x.shape != h.shape or x.shape != c.shape:
             raise RuntimeError("Sizes of tensors must match except in dimension 1. Expected %s but got %s / %s (input vs "
                                "hidden / cell state; NHWC)" % (tuple(x.shape), tuple(h.shape), tuple(c.shape)))
@@ -1968,9 +1996,14 @@ class LSTMCell(Function):
             ctx.mark_dirty(*dirty)          # (as in GRUCell: written by the library, declared to autograd)
         need = any(ctx.needs_input_grad)
         gates = torch.empty(B, Hh, W, 4 * Cc, device=x.device) if need else None
-        conv_launch(x, Taps.get("conv", 3, 1), cp.fwd(), hn, Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, bias=cp.bias(),
-                    epi=H.EPI_LSTM, e1=c, o1=cn, o2=gates)
+        if act is None:
+            conv_launch(x, Taps.get("conv", 3, 1), cp.fwd(), hn, Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, bias=cp.bias(),
+                        epi=H.EPI_LSTM, e1=c, o1=cn, o2=gates)
+        else:               # (e0 = h: what an inactive sample copies)
+            conv_launch(x, Taps.get("conv", 3, 1), cp.fwd(), hn, Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, bias=cp.bias(),
+                        epi=H.EPI_LSTM, e0=h, e1=c, o1=cn, o2=gates, active=act)
         ctx.cp = cp
+        ctx.active = act
         if need:
             ctx.save_for_backward(x, h, c, cn, gates)
         return hn, cn
@@ -1985,12 +2018,16 @@ class LSTMCell(Function):
         dcn = None if dcn is None else dense(dcn).contiguous()
         dpre = torch.empty_like(gates)
         dc = torch.empty_like(cn)
-        H.check(H.lib().ramnet_lstm_bwd(_p(gates), _p(c), _p(cn), _p(dhn), _p(dcn), _p(dpre), _p(dc), npix, Cc, _st()), "lstm_bwd")
+        dxh = torch.empty(B, Hh, W, 2 * Cc, device=x.device)
+        if ctx.active is None:
+            H.check(H.lib().ramnet_lstm_bwd(_p(gates), _p(c), _p(cn), _p(dhn), _p(dcn), _p(dpre), _p(dc), npix, Cc, _st()), "lstm_bwd")
+        else:               # inactive samples: dh = dh' (left in dxh for the beta = 1 launch below), dc = dc', dpre = 0
+            H.check(H.lib().ramnet_lstm_bwd_masked(_p(gates), _p(c), _p(cn), _p(dhn), _p(dcn), _p(ctx.active), _p(dpre), _p(dc), _p(dxh),
+                                                   npix, Hh * W, Cc, _st()), "lstm_bwd_masked")
         ws, bws = cp.grad_ws(wino_ok=x.shape[3] % 32 == 0)
         wgrad_side([x, h, dpre], x, Taps.get("conv", 3, 1), dpre, ws, 4 * Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, dbias=bws)
-        dxh = torch.empty(B, Hh, W, 2 * Cc, device=x.device)
-        conv_launch(dpre, Taps.get("dgrad1", 3, 1), cp.bwd(), dxh, 2 * Cc)
-        return dxh[..., :Cc], dxh[..., Cc:], dc, None, None, None, None, None
+        conv_launch(dpre, Taps.get("dgrad1", 3, 1), cp.bwd(), dxh, 2 * Cc, beta=0.0 if ctx.active is None else 1.0)
+        return dxh[..., :Cc], dxh[..., Cc:], dc, None, None, None, None, None, None
 
 
 class PredSigmoid(Function):

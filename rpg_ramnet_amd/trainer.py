@@ -59,6 +59,8 @@ def sequence_loss(model, sequence, loss_composition, loss_weights, loss_params=N
         loss_params = {"weight": 1.0, "n_lambda": 1.0} if loss_type == "scale_invariant_loss" else {}
     if dp_exact:
         assert loss_type == "scale_invariant_loss" and mse_loss is None, "dp_exact: the scale-invariant loss only"
+        if any('num_events' in it for it in sequence):
+            raise NotImplementedError("dp_exact: batches of irregular packages (num_events) are not supported")
         return _sequence_loss_dp_exact(model, sequence, loss_composition, loss_weights, loss_params, grad_loss_weight, process_group)
     gterms, mterms = [], []
     L = len(sequence)

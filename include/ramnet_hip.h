@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define RAMNET_ABI_VERSION 25      /* 25: ramnet_conv_desc.active (per-sample update masks of the cell epilogues: batched irregular packages) + ramnet_lstm_bwd_masked; 24: ramnet_cat_batch_add_masked (the gradient of a time-batched ReLU feature leaves its fan-in already masked), ramnet_pred_sigmoid_si_bwd takes the forward's scratch (fixed-order join of the weight / bias partial sums); 23: ramnet_wgrad_desc.algo = RAMNET_ALGO_DIRECT_SPLIT (direct 3x3 backward-weights on the bf16 matrix pipe, split operands: csrc/conv_wgrad_dsplit.hip) + ramnet_wgrad_dsplit_slabs; 22: RAMNET_ALGO_WINOGRAD_2X4_SPLIT + ramnet_conv_wino_split_ok / ramnet_pack_weight_wino2x4_split (split bf16 operands on the F(2x4,3x3) forward / backward-data launches); 21: RAMNET_EPI_SIGMOID_HR (the ConvGRU gates launch also writes h.r: the candidate convolution and its backward-weights read a plain concatenation); 20 (never released on its own: shipped together with 21): ramnet_wgrad_desc.nseg / segs (multi-segment backward-weights launches: deferred ConvGRU cell updates); 19: ramnet_cat_batch_add (gradient of a time-batched feature); 18: RAMNET_EPI_GRU_BWD (stage B of the ConvGRU backward in the epilogue of the candidate convolution's backward-data launch) + ramnet_gru_bwd_a2; 17: ramnet_wgrad_desc.algo = RAMNET_ALGO_WINOGRAD_2X4 (F(2x4,3x3) backward-weights, csrc/conv_wgrad_wino6.hip) + ramnet_wgrad_wino2x4_slabs / ramnet_unpack_wgrad_wino2x4, option "wgrad_wino_nf"; 16: ramnet_conv_desc.splitk_ws / splitk_floats + ramnet_conv_splitk_floats (split channel reduction of latency-bound Winograd launches), option "wino_ksplit"; 15: ramnet_si_loss_from_stats (data-parallel exact loss), ramnet_si_log_loss_* / ramnet_mse_loss_*, ramnet_reflect_pad, ramnet_wgrad_desc.dw_slabs + ramnet_reduce_slabs, ramnet_set_option (environment knobs removed), fold weight-algebra kernels, RAMNET_ALGO_WINOGRAD_2X4 + ramnet_conv_wino_variant / ramnet_pack_weight_wino2x4; 14: ramnet_norm_* (BatchNorm / InstanceNorm); 13: pair layout of ramnet_pack_weight_fold_wino, head kernel for 10 input channels */
+#define RAMNET_ABI_VERSION 26      /* 26: RAMNET_ALGO_WINOGRAD24_2X3 (F(2x3,4x4) folded decoders) + ramnet_fold_wino_variant / ramnet_pack_weight_fold_wino2x3[_dgrad] / ramnet_packed_weight_elems_fold_wino2x3; 25: ramnet_conv_desc.active (per-sample update masks of the cell epilogues: batched irregular packages) + ramnet_lstm_bwd_masked; 24: ramnet_cat_batch_add_masked (the gradient of a time-batched ReLU feature leaves its fan-in already masked), ramnet_pred_sigmoid_si_bwd takes the forward's scratch (fixed-order join of the weight / bias partial sums); 23: ramnet_wgrad_desc.algo = RAMNET_ALGO_DIRECT_SPLIT (direct 3x3 backward-weights on the bf16 matrix pipe, split operands: csrc/conv_wgrad_dsplit.hip) + ramnet_wgrad_dsplit_slabs; 22: RAMNET_ALGO_WINOGRAD_2X4_SPLIT + ramnet_conv_wino_split_ok / ramnet_pack_weight_wino2x4_split (split bf16 operands on the F(2x4,3x3) forward / backward-data launches); 21: RAMNET_EPI_SIGMOID_HR (the ConvGRU gates launch also writes h.r: the candidate convolution and its backward-weights read a plain concatenation); 20 (never released on its own: shipped together with 21): ramnet_wgrad_desc.nseg / segs (multi-segment backward-weights launches: deferred ConvGRU cell updates); 19: ramnet_cat_batch_add (gradient of a time-batched feature); 18: RAMNET_EPI_GRU_BWD (stage B of the ConvGRU backward in the epilogue of the candidate convolution's backward-data launch) + ramnet_gru_bwd_a2; 17: ramnet_wgrad_desc.algo = RAMNET_ALGO_WINOGRAD_2X4 (F(2x4,3x3) backward-weights, csrc/conv_wgrad_wino6.hip) + ramnet_wgrad_wino2x4_slabs / ramnet_unpack_wgrad_wino2x4, option "wgrad_wino_nf"; 16: ramnet_conv_desc.splitk_ws / splitk_floats + ramnet_conv_splitk_floats (split channel reduction of latency-bound Winograd launches), option "wino_ksplit"; 15: ramnet_si_loss_from_stats (data-parallel exact loss), ramnet_si_log_loss_* / ramnet_mse_loss_*, ramnet_reflect_pad, ramnet_wgrad_desc.dw_slabs + ramnet_reduce_slabs, ramnet_set_option (environment knobs removed), fold weight-algebra kernels, RAMNET_ALGO_WINOGRAD_2X4 + ramnet_conv_wino_variant / ramnet_pack_weight_wino2x4; 14: ramnet_norm_* (BatchNorm / InstanceNorm); 13: pair layout of ramnet_pack_weight_fold_wino, head kernel for 10 input channels */
 #define RAMNET_E_BADARG 10001
 #define RAMNET_E_UNSUPPORTED 10002
 
@@ -65,8 +65,14 @@ enum ramnet_in_mode {
  * bf16 terms when a strip is staged, six of the nine partial products, fp32 accumulation (csrc/conv_wgrad_dsplit.hip); dw = the blocked
  * layout of ramnet_wgrad_dsplit_ws_floats() (ramnet_unpack_wgrad_dsplit), dw_slabs as for the Winograd forms with at most
  * ramnet_wgrad_dsplit_slabs() slabs.                                                                                                         */
+/* RAMNET_ALGO_WINOGRAD24_2X3 (ABI 26): the launches of RAMNET_ALGO_WINOGRAD24 (forward and RAMNET_IN_PARITY4) as F(2x3,4x4) — 2 x 3 output
+ * tiles, 30 instead of 25 positions per tile: 5.0 instead of 6.25 multiplies per output (csrc/conv_wino24.hip, TW = 3) — restricted to what
+ * ramnet_fold_wino_variant() accepts (64-column workgroups, no split reduction: splitk_ws NULL); w from ramnet_pack_weight_fold_wino2x3()
+ * or ramnet_pack_weight_fold_wino2x3_dgrad(): the layouts of the F(2x2) packs with 30 positions pos = a*6 + b, the row matrix G above and
+ * the column matrix Gc = [4 0 0 0; 2/3 2/3 2/3 2/3; 2/3 -2/3 2/3 -2/3; -8/3 -4/3 -2/3 -1/3; -8/3 4/3 -2/3 1/3; 0 0 0 1]
+ * (points 0, 1, -1, 1/2, -1/2, inf).                                                                                                        */
 enum ramnet_algo { RAMNET_ALGO_DIRECT = 0, RAMNET_ALGO_WINOGRAD = 1, RAMNET_ALGO_HEAD = 2, RAMNET_ALGO_WINOGRAD24 = 3, RAMNET_ALGO_WINOGRAD_2X4 = 4,
-                   RAMNET_ALGO_WINOGRAD_2X4_SPLIT = 5, RAMNET_ALGO_DIRECT_SPLIT = 6 };
+                   RAMNET_ALGO_WINOGRAD_2X4_SPLIT = 5, RAMNET_ALGO_DIRECT_SPLIT = 6, RAMNET_ALGO_WINOGRAD24_2X3 = 7 };
 
 /* ---- fused epilogues ------------------------------------------------------------------------- */
 enum ramnet_epilogue {
@@ -293,6 +299,16 @@ int ramnet_pack_weight_fold_wino(const float *w_oihw, float *wp, int Cout, int C
  *   dU [4][25][CinWs][Cout] (Winograd-domain launches; may be NULL), wr / wc [2][5*Cin][2*Cout] (border-GEMM gradients) — which it zeroes.   */
 int ramnet_pack_weight_fold_wino_dgrad(const float *w_oihw, float *wp, int Cout, int Cin, void *stream);
 int ramnet_pack_border_weights(const float *w_oihw, float *rows, float *cols, float *rows_t, float *cols_t, int Cout, int Cin, void *stream);
+/* F(2x3,4x4) (ABI 26): 1 when a RAMNET_ALGO_WINOGRAD24 launch (d->algo set so, every other field final) runs faster as
+ * RAMNET_ALGO_WINOGRAD24_2X3 — the caller then sets d->algo and d->w (the packs below) accordingly; else 0.  Forward launches with
+ * 64-column workgroups (the pair form included) and backward-data launches; force: skip the size heuristics (tests), which keep
+ * launches below a few rounds of workgroups and launches that would split their reduction on F(2x2).
+ * ramnet_pack_weight_fold_wino2x3 (forward; 64-column layouts only) / _dgrad (RAMNET_IN_PARITY4; Cin % 64 == 0): 120*Cout*Cin floats
+ * (ramnet_packed_weight_elems_fold_wino2x3), evaluated in double like the F(2x2) packs.                                               */
+int ramnet_fold_wino_variant(const ramnet_conv_desc *d, int force);
+size_t ramnet_packed_weight_elems_fold_wino2x3(int Cout, int Cin);
+int ramnet_pack_weight_fold_wino2x3(const float *w_oihw, float *wp, int Cout, int Cin, void *stream);
+int ramnet_pack_weight_fold_wino2x3_dgrad(const float *w_oihw, float *wp, int Cout, int Cin, void *stream);
 int ramnet_fold_unpack_wgrad(float *w4, float *dU, float *wr, float *wc, float *grad, int Cout, int Cin, int CinWs, void *stream);
 /* Head layers (RAMNET_ALGO_HEAD): OIHW [Cout<=32][Cin][5][5] -> [25*Cin rounded up to even][32], row = tap*Cin + channel.
  * ramnet_head_supported: does the head kernel serve this channel pair (Cin in {1,3,5,10}, Cout <= 32)?           */

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("RAMNET_HIP_LIB") or os.path.join(_PKG, "librpg_ramnet
 
 IN_PLAIN, IN_CAT, IN_CAT_MUL, IN_UP2X, IN_UP2X_SKIP, IN_RELUMASK, IN_S2D, IN_PARITY4 = range(8)
 ALGO_DIRECT, ALGO_WINOGRAD, ALGO_HEAD, ALGO_WINOGRAD24, ALGO_WINOGRAD_2X4, ALGO_WINOGRAD_2X4_SPLIT, ALGO_DIRECT_SPLIT = 0, 1, 2, 3, 4, 5, 6
+ALGO_WINOGRAD24_2X3 = 7
 EPI_LINEAR, EPI_RELU, EPI_SIGMOID, EPI_RES_RELU, EPI_GRU_BLEND, EPI_LSTM, EPI_GRU_BWD, EPI_SIGMOID_HR = range(8)
 
 _fp = C.c_void_p
@@ -105,6 +106,10 @@ _SIGS = {
     "ramnet_packed_weight_elems_fold_wino": (C.c_size_t, [C.c_int, C.c_int]),
     "ramnet_pack_weight_fold_wino": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp]),
     "ramnet_pack_weight_fold_wino_dgrad": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp]),
+    "ramnet_fold_wino_variant": (C.c_int, [C.POINTER(ConvDesc), C.c_int]),
+    "ramnet_packed_weight_elems_fold_wino2x3": (C.c_size_t, [C.c_int, C.c_int]),
+    "ramnet_pack_weight_fold_wino2x3": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp]),
+    "ramnet_pack_weight_fold_wino2x3_dgrad": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp]),
     "ramnet_pack_border_weights": (C.c_int, [_fp] * 5 + [C.c_int, C.c_int, _fp]),
     "ramnet_fold_unpack_wgrad": (C.c_int, [_fp] * 5 + [C.c_int, C.c_int, C.c_int, _fp]),
     "ramnet_unpad2_fold": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
@@ -213,7 +218,7 @@ def lib():
         for name, (res, args) in _SIGS.items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
-        if l.ramnet_abi_version() != 25:
+        if l.ramnet_abi_version() != 26:
             raise RuntimeError("ABI version mismatch in %s" % LIB_PATH)
         _lib = l
     return _lib if _tracer is None else _Traced(_lib)

@@ -14,6 +14,11 @@
 // 16-byte global (L2) read per position from weights packed in exactly that lane order.  Loads and the transform of chunk
 // i+1 are issued between the MFMAs of chunk i.  The output transform is register-local; bias / ReLU and the border
 // corrections of the folded layer (ramnet_conv_desc.frame) are applied by the shared epilogue.
+//
+// TW = 3 (RAMNET_ALGO_WINOGRAD24_2X3): F(2x3, 4x4), the same structure on 2 x 3 output tiles.  Rows keep the 5-point F(2,4)
+// transform, columns take the 6-point F(3,4) one (points 0, 1, -1, 1/2, -1/2, inf): a 5 x 6 window, 30 positions (15 pairs,
+// 120 accumulator VGPRs), 5.0 multiplies per output instead of 6.25 — 20 % fewer MFMAs and window loads per output.  V holds 30
+// positions (2 x 61.4 KB).  Training-batch launches only (ramnet_fold_wino_variant): no split reduction.
 #include <stdlib.h>
 #include "common.hpp"
 #include "conv_epilogue.hpp"
@@ -25,6 +30,7 @@ namespace ramnet {
 // tiles per workgroup (2x2 outputs each): 8 x 4 or 4 x 8 (rows x columns, TXW = columns) for 32 tiles, 8 x 8 for 64
 constexpr int W24_PS = 512;                       // floats per position in V: tiles x chunk channels (32 x 16 or 64 x 8)
 constexpr int W24_V = 25 * W24_PS;                // floats per V buffer (51.2 KB)
+constexpr int W23_V = 30 * W24_PS;                // the same for F(2x3, 4x4) (61.4 KB)
 
 __device__ __forceinline__ float2 ld2f(const float *p) { return *reinterpret_cast<const float2 *>(p); }
 
@@ -67,15 +73,19 @@ struct Wino24Params {
 // class-(py, 1) grid is tiled with its tile origins shifted by one column, so that both classes read the same 5 x 5 windows — and
 // the workgroup's 64 columns are (px, 32 channels): the input transform (25 loads + ~160 VALU per tile and channel, the cost that
 // bounds this kernel at 32 output channels: 35 % MFMA-busy) feeds twice the MFMAs.  NCQ = 4 geometry, chunks of 16.
-template <int NCQ, bool DG, int TXW, bool PAIR = false>
+// TW = output columns per tile: 2 = F(2x2, 4x4), 3 = F(2x3, 4x4) (NCQ = 4 only; window 5 x (TW + 3), NP = 5 (TW + 3) positions).
+template <int NCQ, bool DG, int TXW, bool PAIR = false, int TW = 2>
 __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_desc p, const Wino24Params q) {
     static_assert(!PAIR || (NCQ == 4 && !DG), "pair mode: forward, 64-column workgroups");
+    static_assert(TW == 2 || (TW == 3 && NCQ == 4), "F(2x3): 64-column workgroups");
+    constexpr int WC = TW + 3, NP = 5 * WC;           // window columns, Winograd positions
+    constexpr int VSZ = NP * W24_PS;                  // floats per V buffer
     constexpr int W24_K = NCQ == 4 ? 16 : 8;          // input channels per chunk
     constexpr int W24_TX = TXW, W24_TY = (NCQ == 4 ? 32 : 64) / TXW;      // tile columns / rows per workgroup
     constexpr int VEC = W24_K / 4;                    // floats per lane and operand read (k = VEC*ks + j)
-    constexpr int W24_U = 25 * NCQ * 64 * VEC;        // packed weights of one (class, chunk, channel block)
+    constexpr int W24_U = NP * NCQ * 64 * VEC;        // packed weights of one (class, chunk, channel block)
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *V = smem;                               // [2][25][32][16]
+    float *V = smem;                               // [2][NP][32][16]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, ks = lane >> 4;
@@ -96,34 +106,36 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
     // ---- input transform item of this thread: (tile, channel of the chunk)
     const int it = tid / W24_K, ik = tid % W24_K;
     // window rows / columns past the padded input only feed outputs past the grid: clamp them one by one
-    const int iy0 = 2 * (tby * W24_TY + it / W24_TX) + py, ix0 = 2 * (tbx * W24_TX + it % W24_TX) + px;
+    const int iy0 = 2 * (tby * W24_TY + it / W24_TX) + py, ix0 = TW * (tbx * W24_TX + it % W24_TX) + px;
     // byte offsets: lane part (image + row, column + channel: one add per load) + scalar part (chunk)
-    unsigned rowo[5], colo[5];
+    unsigned rowo[5], colo[WC];
     int cur_cls = -1;
     auto set_class = [&](int c) {                   // DG: window of parity class c = (c >> 1, c & 1); invalid -> offset past the tensor
         cur_cls = c;
         const int cy = c >> 1, cx = c & 1;
-        const int u0 = 2 * (tby * W24_TY + it / W24_TX), v0 = 2 * (tbx * W24_TX + it % W24_TX);
+        const int u0 = 2 * (tby * W24_TY + it / W24_TX), v0 = TW * (tbx * W24_TX + it % W24_TX);
 #pragma unroll
-        for (int r = 0; r < 5; ++r) {
+        for (int r = 0; r < WC; ++r) {
             const int i = u0 - cy - 3 + r, j = v0 - cx - 3 + r;           // class-grid row / column
-            rowo[r] = (unsigned)i < (unsigned)q.Hc ? 4u * (unsigned)((b * q.Hp + 2 * i + cy) * q.Wp * q.ldx) : 0x40000000u;
+            if (r < 5) rowo[r] = (unsigned)i < (unsigned)q.Hc ? 4u * (unsigned)((b * q.Hp + 2 * i + cy) * q.Wp * q.ldx) : 0x40000000u;
             colo[r] = (unsigned)j < (unsigned)q.Wc ? 4u * (unsigned)((2 * j + cx) * q.ldx + ik) : 0x40000000u;
         }
     };
     if (!DG) {
 #pragma unroll
-        for (int r = 0; r < 5; ++r)
-            rowo[r] = 4u * (unsigned)((b * q.Hp + min(iy0 + r, q.Hp - 1)) * q.Wp * q.ldx), colo[r] = 4u * (unsigned)(min(ix0 + r, q.Wp - 1) * q.ldx + ik);
+        for (int r = 0; r < WC; ++r) {
+            if (r < 5) rowo[r] = 4u * (unsigned)((b * q.Hp + min(iy0 + r, q.Hp - 1)) * q.Wp * q.ldx);
+            colo[r] = 4u * (unsigned)(min(ix0 + r, q.Wp - 1) * q.ldx + ik);
+        }
     }
     // Split reduction (forward launches far below one workgroup per CU: the first decoders at batch 1): workgroup blockIdx.y reduces
-    // chunks [cbeg, cbeg + nch) and the partial outputs are joined in front of the epilogue (as in conv_wino.hip)
-    const int ksp = DG ? 1 : q.ksplit;
+    // chunks [cbeg, cbeg + nch) and the partial outputs are joined in front of the epilogue (as in conv_wino.hip).  F(2x3): never split.
+    const int ksp = (DG || TW != 2) ? 1 : q.ksplit;
     const int cps = ((q.nchunks / 2 + ksp - 1) / ksp) * 2, cbeg = DG ? 0 : (int)blockIdx.y * cps;
     const auto xrs = make_rsrc(q.x + cbeg * W24_K, q.xbytes - (unsigned)cbeg * W24_K * 4u);
     // operand reads are VEC floats per lane; the XOR swizzle spreads the 16 tiles of a read over all banks
     const int vdst = NCQ == 4 ? it * 16 + (((ik >> 2) ^ ((it >> 2) & 3)) << 2) + (ik & 3) : it * 8 + (((ik >> 1) ^ ((it >> 3) & 1)) << 1) + (ik & 1);
-    float raw[25];
+    float raw[5 * WC];
     auto load_raw = [&](int chunk) {
         int soff = chunk * (W24_K * 4);                 // uniform
         if (DG) {
@@ -134,8 +146,8 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
 #pragma unroll
         for (int r = 0; r < 5; ++r)
 #pragma unroll
-            for (int c = 0; c < 5; ++c)
-                raw[r * 5 + c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, (int)(rowo[r] + colo[c]), soff, 0));
+            for (int c = 0; c < WC; ++c)
+                raw[r * WC + c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, (int)(rowo[r] + colo[c]), soff, 0));
     };
     // one window row at a time (the main loop requests row i as soon as tr_row(i) has consumed the previous window's row i: five loads per
     // slot instead of 25 in one)
@@ -150,26 +162,39 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
     };
     auto load_row = [&](int r) {
 #pragma unroll
-        for (int c = 0; c < 5; ++c)
-            raw[r * 5 + c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, (int)(rowo[r] + colo[c]), lr_soff, 0));
+        for (int c = 0; c < WC; ++c)
+            raw[r * WC + c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, (int)(rowo[r] + colo[c]), lr_soff, 0));
     };
     // B^T = [2 -1 -2 1 0; 0 -2 -1 1 0; 0 2 -3 1 0; 0 -1 0 1 0; 0 2 -1 -2 1]
     auto tr_col = [&](int c) {
-        const float d0 = raw[c], d1 = raw[5 + c], d2 = raw[10 + c], d3 = raw[15 + c], d4 = raw[20 + c];
+        const float d0 = raw[c], d1 = raw[WC + c], d2 = raw[2 * WC + c], d3 = raw[3 * WC + c], d4 = raw[4 * WC + c];
         raw[c] = 2.f * (d0 - d2) - d1 + d3;
-        raw[5 + c] = d3 - d2 - 2.f * d1;
-        raw[10 + c] = 2.f * d1 - 3.f * d2 + d3;
-        raw[15 + c] = d3 - d1;
-        raw[20 + c] = 2.f * (d1 - d3) - d2 + d4;
+        raw[WC + c] = d3 - d2 - 2.f * d1;
+        raw[2 * WC + c] = 2.f * d1 - 3.f * d2 + d3;
+        raw[3 * WC + c] = d3 - d1;
+        raw[4 * WC + c] = 2.f * (d1 - d3) - d2 + d4;
     };
+    // F(2x3): vbuf = the lane's first element of the buffer (V + vdst or V + dbuf1 below)
     auto tr_row = [&](float *vbuf, int i) {
-        const float d0 = raw[i * 5], d1 = raw[i * 5 + 1], d2 = raw[i * 5 + 2], d3 = raw[i * 5 + 3], d4 = raw[i * 5 + 4];
-        float *dst = vbuf + (i * 5) * W24_PS + vdst;
-        dst[0 * W24_PS] = 2.f * (d0 - d2) - d1 + d3;
-        dst[1 * W24_PS] = d3 - d2 - 2.f * d1;
-        dst[2 * W24_PS] = 2.f * d1 - 3.f * d2 + d3;
-        dst[3 * W24_PS] = d3 - d1;
-        dst[4 * W24_PS] = 2.f * (d1 - d3) - d2 + d4;
+        float *dst = TW == 2 ? vbuf + (i * WC) * W24_PS + vdst : vbuf + (i * WC) * W24_PS;
+        if constexpr (TW == 2) {
+            const float d0 = raw[i * 5], d1 = raw[i * 5 + 1], d2 = raw[i * 5 + 2], d3 = raw[i * 5 + 3], d4 = raw[i * 5 + 4];
+            dst[0 * W24_PS] = 2.f * (d0 - d2) - d1 + d3;
+            dst[1 * W24_PS] = d3 - d2 - 2.f * d1;
+            dst[2 * W24_PS] = 2.f * d1 - 3.f * d2 + d3;
+            dst[3 * W24_PS] = d3 - d1;
+            dst[4 * W24_PS] = 2.f * (d1 - d3) - d2 + d4;
+        } else {
+            // F(3,4) columns, B^T = [1/4 0 -5/4 0 1 0; 0 -1/4 -1/4 1 1 0; 0 1/4 -1/4 -1 1 0; 0 -1/2 -1 1/2 1 0; 0 1/2 -1 -1/2 1 0; 0 1/4 0 -5/4 0 1]
+            const float d0 = raw[i * 6], d1 = raw[i * 6 + 1], d2 = raw[i * 6 + 2], d3 = raw[i * 6 + 3], d4 = raw[i * 6 + 4], d5 = raw[i * 6 + 5];
+            const float u = d3 - d1, v = d4 - d2;
+            dst[0 * W24_PS] = fmaf(-1.25f, d2, fmaf(0.25f, d0, d4));
+            dst[1 * W24_PS] = fmaf(-0.25f, d1 + d2, d3 + d4);
+            dst[2 * W24_PS] = fmaf(0.25f, d1 - d2, d4 - d3);
+            dst[3 * W24_PS] = fmaf(0.5f, u, v);
+            dst[4 * W24_PS] = fmaf(-0.5f, u, v);
+            dst[5 * W24_PS] = fmaf(-1.25f, d3, fmaf(0.25f, d1, d5));
+        }
     };
 
     // ---- MFMA operands
@@ -193,25 +218,32 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
         }
     };
     const int wchunk = q.nblk * W24_U * 4;
+    // F(2x3): V is 2 x 61.4 KB.  The lane's offsets into buffer 1 are made opaque, so that every A-operand read and V store of a buffer is
+    // ONE base VGPR + an immediate offset (30 positions x 2 KB < 64 KB); left to itself the compiler keeps a base per group of positions
+    // and spills them (reloads behind s_waitcnt vmcnt(0) in the main loop).
+    int abuf1 = VSZ + aoff, dbuf1 = VSZ + vdst;
+    if constexpr (TW == 3) asm volatile("" : "+v"(abuf1), "+v"(dbuf1));
 
-    f32x4 acc[25];
+    f32x4 acc[NP];
 #pragma unroll
-    for (int i = 0; i < 25; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int i = 0; i < NP; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int nch = DG ? q.nchunks : min(cps, q.nchunks - cbeg);
     W24_STAMP(16, 0);
     load_raw(0);
     // Weight ring: 10 slots, prefetch distance 9 positions.  Vector loads return in order, so a weight load issued after the
     // 25 window loads of a chunk can only be consumed once those have landed: the ring is deep enough to give them ~9 positions
-    // (~1 us) of MFMA work, and the chunk loop is unrolled by two so that the slot of a position is a compile-time constant.
-    constexpr int RING = 10, DIST = 8;
+    // (~1 us) of MFMA work, and the chunk loop is unrolled by two so that the slot of a position is a compile-time constant
+    // (RING divides 2 NP).  F(2x3) forward: 6 slots, prefetch distance 4 — with 10 its 120 accumulators spill (backward-data keeps 10).
+    constexpr int RING = TW == 2 || DG ? 10 : 6, DIST = RING - 2;
+    static_assert((2 * NP) % RING == 0, "ring slots repeat every chunk pair");
     float4 bq[RING];
 #pragma unroll
     for (int i = 0; i < DIST; ++i) bq[i] = ldw(wsrc + i * (WPOS * 4));
 #pragma unroll
-    for (int c = 0; c < 5; ++c) tr_col(c);
+    for (int c = 0; c < WC; ++c) tr_col(c);
 #pragma unroll
-    for (int i = 0; i < 5; ++i) tr_row(V, i);
+    for (int i = 0; i < 5; ++i) tr_row(TW == 2 ? V : V + vdst, i);
     load_raw(min(1, nch - 1));
     __syncthreads();
 
@@ -220,8 +252,12 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
 #pragma unroll
         for (int half = 0; half < 2; ++half) {
             const int chunk = chunk0 + half;
-            const float *vb = V + half * W24_V;
-            float *vn = V + (half ^ 1) * W24_V;
+            const float *vb = V + half * VSZ;
+            float *vn = TW == 2 ? V + (half ^ 1) * VSZ : V + (half ? vdst : dbuf1);
+            auto lda = [&](int pos) {
+                if constexpr (TW == 2) return ldv(vb + pos * W24_PS + aoff);
+                else return ldv(V + (half ? abuf1 : aoff) + pos * W24_PS);
+            };
             // The window of chunk+1 is already in registers (loaded at the end of the previous phase: a weight load issued
             // after it can only be consumed once it has landed, and there it has a barrier and four position pairs to do so);
             // it is transformed into the other V buffer during this phase and the window of chunk+2 requested right after.
@@ -229,19 +265,19 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
             const int wcur = wsrc + chunk * wchunk, wnext = wsrc + cnext * wchunk;
             W24_STAMP(chunk, 0);
             // positions go in pairs (two independent accumulator chains: a 16x16x4 MFMA can be issued every 32 cycles but its
-            // result is only available to a dependent one after 40); the last position runs alone
+            // result is only available to a dependent one after 40); F(2x2): the last position runs alone
             float4 aq[2][2];                                   // A operands of the current / next pair (ping-pong, no copies)
-            aq[0][0] = ldv(vb + aoff), aq[0][1] = ldv(vb + W24_PS + aoff);
+            aq[0][0] = lda(0), aq[0][1] = lda(1);
 #pragma unroll
-            for (int pp = 0; pp < 13; ++pp) {
-                const int pos = 2 * pp, g = half * 25 + pos;
-                const bool two = pos + 1 < 25;
-                if (pos + 2 < 25) aq[(pp + 1) & 1][0] = ldv(vb + (pos + 2) * W24_PS + aoff);
-                if (pos + 3 < 25) aq[(pp + 1) & 1][1] = ldv(vb + (pos + 3) * W24_PS + aoff);
+            for (int pp = 0; pp < (NP + 1) / 2; ++pp) {
+                const int pos = 2 * pp, g = half * NP + pos;
+                const bool two = pos + 1 < NP;
+                if (pos + 2 < NP) aq[(pp + 1) & 1][0] = lda(pos + 2);
+                if (pos + 3 < NP) aq[(pp + 1) & 1][1] = lda(pos + 3);
                 const float4 a0 = aq[pp & 1][0], a1 = aq[pp & 1][1];
 #if !defined(W24_ABLATE) || !(W24_ABLATE & 2)
-                bq[(g + DIST) % RING] = pos + DIST < 25 ? ldw(wcur + (pos + DIST) * (WPOS * 4)) : ldw(wnext + (pos + DIST - 25) * (WPOS * 4));
-                if (two) bq[(g + 1 + DIST) % RING] = pos + 1 + DIST < 25 ? ldw(wcur + (pos + 1 + DIST) * (WPOS * 4)) : ldw(wnext + (pos + 1 + DIST - 25) * (WPOS * 4));
+                bq[(g + DIST) % RING] = pos + DIST < NP ? ldw(wcur + (pos + DIST) * (WPOS * 4)) : ldw(wnext + (pos + DIST - NP) * (WPOS * 4));
+                if (two) bq[(g + 1 + DIST) % RING] = pos + 1 + DIST < NP ? ldw(wcur + (pos + 1 + DIST) * (WPOS * 4)) : ldw(wnext + (pos + 1 + DIST - NP) * (WPOS * 4));
 #endif
                 const float4 b0 = bq[g % RING], b1 = bq[(g + 1) % RING];
                 __builtin_amdgcn_sched_barrier(0);
@@ -254,16 +290,18 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
                 // 24-34 VALU in three gaps and 25 loads in one: column transform c in slots 4..8, row transform i (+ its 5 LDS stores) in
                 // slots 9, 11, .., 17, and the five window loads of row i of chunk + 2 right behind it (slots 10, 12, .., 18: the row's
                 // registers are free, and the loads have six position pairs + the barrier to land before the next chunk's slot 4).
+                // F(2x3) (30 slots): column transforms in slots 4..9, rows in 10, 12, .., 18, their six loads in 11, 13, .., 19.
+                constexpr int R0 = 4 + WC;                     // slot of the first row transform
                 auto slot = [&](int sl) {
                     if (sl == 4) W24_STAMP(chunk, 1);
-                    if (sl >= 4 && sl <= 8) tr_col(sl - 4);
-                    if (sl == 9) W24_STAMP(chunk, 2);
-                    if (sl >= 9 && sl <= 17 && (sl & 1)) tr_row(vn, (sl - 9) >> 1);
+                    if (sl >= 4 && sl < R0) tr_col(sl - 4);
+                    if (sl == R0) W24_STAMP(chunk, 2);
+                    if (sl >= R0 && sl <= R0 + 8 && !((sl - R0) & 1)) tr_row(vn, (sl - R0) >> 1);
 #if !defined(W24_ABLATE) || !(W24_ABLATE & 1)      // timing experiments (tools/wino24_trace.hip): 1 = no window loads, 2 = no weight loads
-                    if (sl == 10) load_row_begin(cnext2);
-                    if (sl >= 10 && sl <= 18 && !(sl & 1)) load_row((sl - 10) >> 1);
+                    if (sl == R0 + 1) load_row_begin(cnext2);
+                    if (sl > R0 && sl <= R0 + 9 && ((sl - R0) & 1)) load_row((sl - R0 - 1) >> 1);
 #endif
-                    if (sl == 18) W24_STAMP(chunk, 3);
+                    if (sl == R0 + 9) W24_STAMP(chunk, 3);
                 };
                 slot(2 * pp);
                 __builtin_amdgcn_sched_barrier(0);
@@ -294,22 +332,29 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
     const int epi = p.epi;
     const float bias_n = (!DG && p.bias) ? p.bias[n] : 0.f;
     const bool relu = epi == RAMNET_EPI_RELU;
-    float ov[16];
-    size_t op[16];
-    bool oo[16];
+    constexpr int NOUT = 8 * TW;                      // 4 tiles x 2 x TW outputs
+    float ov[NOUT];
+    size_t op[NOUT];
+    bool oo[NOUT];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        float s[2][5];
+        float s[2][WC];
 #pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const float m0 = acc[j][r], m1 = acc[5 + j][r], m2 = acc[10 + j][r], m3 = acc[15 + j][r], m4 = acc[20 + j][r];
+        for (int j = 0; j < WC; ++j) {
+            const float m0 = acc[j][r], m1 = acc[WC + j][r], m2 = acc[2 * WC + j][r], m3 = acc[3 * WC + j][r], m4 = acc[4 * WC + j][r];
             s[0][j] = m0 + m1 + m2 + m3;
             s[1][j] = m1 - m2 + 2.f * m3 + m4;
         }
 #pragma unroll
         for (int a2 = 0; a2 < 2; ++a2) {
-            ov[(r * 2 + a2) * 2] = s[a2][0] + s[a2][1] + s[a2][2] + s[a2][3];
-            ov[(r * 2 + a2) * 2 + 1] = s[a2][1] - s[a2][2] + 2.f * s[a2][3] + s[a2][4];
+            if constexpr (TW == 2) {
+                ov[(r * 2 + a2) * 2] = s[a2][0] + s[a2][1] + s[a2][2] + s[a2][3];
+                ov[(r * 2 + a2) * 2 + 1] = s[a2][1] - s[a2][2] + 2.f * s[a2][3] + s[a2][4];
+            } else {                                // A^T = [1 1 1 1 1 0; 0 1 -1 1/2 -1/2 0; 0 1 1 1/4 1/4 1]
+                ov[(r * 2 + a2) * 3] = s[a2][0] + s[a2][1] + s[a2][2] + s[a2][3] + s[a2][4];
+                ov[(r * 2 + a2) * 3 + 1] = fmaf(0.5f, s[a2][3] - s[a2][4], s[a2][1] - s[a2][2]);
+                ov[(r * 2 + a2) * 3 + 2] = fmaf(0.25f, s[a2][3] + s[a2][4], s[a2][1] + s[a2][2]) + s[a2][5];
+            }
         }
     }
     if (!DG && ksp > 1) {
@@ -343,12 +388,12 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int t = th * 16 + 4 * ks + r;
-        const int oy0 = 2 * (tby * W24_TY + t / W24_TX), ox0 = 2 * (tbx * W24_TX + t % W24_TX) - (PAIR ? pxc : 0);
+        const int oy0 = 2 * (tby * W24_TY + t / W24_TX), ox0 = TW * (tbx * W24_TX + t % W24_TX) - (PAIR ? pxc : 0);
 #pragma unroll
         for (int a2 = 0; a2 < 2; ++a2) {
 #pragma unroll
-            for (int c2 = 0; c2 < 2; ++c2) {
-                const int oy = oy0 + a2, ox = ox0 + c2, idx = (r * 2 + a2) * 2 + c2;
+            for (int c2 = 0; c2 < TW; ++c2) {
+                const int oy = oy0 + a2, ox = ox0 + c2, idx = (r * 2 + a2) * TW + c2;
                 if (DG) {                           // dense output grid, plain store
                     oo[idx] = oy < p.Ho && ox < p.Wo;
                     op[idx] = (((size_t)b * p.Ho + oy) * p.Wo + ox) * p.ldo + n;
@@ -364,21 +409,31 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
         }
     }
 #pragma unroll
-    for (int idx = 0; idx < 16; ++idx)
+    for (int idx = 0; idx < NOUT; ++idx)
         if (oo[idx]) p.out[op[idx]] = ov[idx];
     W24_STAMP(16, 3);
 }
 
 // OIHW 5x5 weights of an UpsampleConvLayer -> U = G W4 G^T of the four 4x4 parity filters W4 = A_py w A_px^T (the bilinear x2
 // upsample folded into the filter) in the lane order of the kernel's B operand; evaluated in double.
+// TW = 3: F(2x3, 4x4), U = G W4 Gc^T with the 6 x 4 column matrix Gc (30 positions, pos = a*6 + b).
+__device__ __forceinline__ double fold_wino_gc(int tw, int b, int s) {
+    const double G[5][4] = {{0.5, 0, 0, 0}, {-0.5, -0.5, -0.5, -0.5}, {-1.0 / 6, 1.0 / 6, -1.0 / 6, 1.0 / 6}, {1.0 / 6, 1.0 / 3, 2.0 / 3, 4.0 / 3}, {0, 0, 0, 1}};
+    const double G3[6][4] = {{4, 0, 0, 0}, {2.0 / 3, 2.0 / 3, 2.0 / 3, 2.0 / 3}, {2.0 / 3, -2.0 / 3, 2.0 / 3, -2.0 / 3},
+                             {-8.0 / 3, -4.0 / 3, -2.0 / 3, -1.0 / 3}, {-8.0 / 3, 4.0 / 3, -2.0 / 3, 1.0 / 3}, {0, 0, 0, 1}};
+    return tw == 2 ? G[b][s] : G3[b][s];
+}
+
+template <int TW>
 __global__ void pack_weight_fold_wino_kernel(const float *__restrict__ w, float *__restrict__ wp, int Cout, int Cin, int kc, int ncq,
                                              int pair, size_t total) {
     const double FA[2][4][5] = {{{.25, 0, 0, 0, 0}, {.75, .75, .25, 0, 0}, {0, .25, .75, .75, .25}, {0, 0, 0, .25, .75}},
                                 {{.75, .25, 0, 0, 0}, {.25, .75, .75, .25, 0}, {0, 0, .25, .75, .75}, {0, 0, 0, 0, .25}}};
     const double G[5][4] = {{0.5, 0, 0, 0}, {-0.5, -0.5, -0.5, -0.5}, {-1.0 / 6, 1.0 / 6, -1.0 / 6, 1.0 / 6}, {1.0 / 6, 1.0 / 3, 2.0 / 3, 4.0 / 3}, {0, 0, 0, 1}};
+    constexpr int WC = TW + 3, NP = 5 * WC;
     const int vec = kc / 4, nblk = pair ? 1 : Cout / (16 * ncq), nch = Cin / kc;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        // i = ((((cls*nch + chunk)*nblk + nb)*25 + pos)*ncq + cq)*64*vec + (ks*16 + l15)*vec + j
+        // i = ((((cls*nch + chunk)*nblk + nb)*NP + pos)*ncq + cq)*64*vec + (ks*16 + l15)*vec + j
         size_t r = i;
         const int j = (int)(r % vec);
         r /= vec;
@@ -388,20 +443,20 @@ __global__ void pack_weight_fold_wino_kernel(const float *__restrict__ w, float 
         r /= 4;
         const int cq = (int)(r % ncq);
         r /= ncq;
-        const int pos = (int)(r % 25);
-        r /= 25;
+        const int pos = (int)(r % NP);
+        r /= NP;
         const int nb = (int)(r % nblk);
         r /= nblk;
         const int chunk = (int)(r % nch), cls = (int)(r / nch);
         const int k = chunk * kc + ks * vec + j, col = (nb * ncq + cq) * 16 + l15;
         // pair layout (32-channel layers): class = row parity, column = (column parity, channel)
         const int n = pair ? col & 31 : col;
-        const int py = pair ? cls : cls >> 1, px = pair ? col >> 5 : cls & 1, a = pos / 5, b = pos % 5;
+        const int py = pair ? cls : cls >> 1, px = pair ? col >> 5 : cls & 1, a = pos / WC, b = pos % WC;
         // U[a][b] = sum_{t,s} G[a][t] G[b][s] sum_{kh,kw} FA[py][t][kh] FA[px][s][kw] w[n][k][kh][kw]
         double ga[5], gb[5];                        // rows of G^T... combined with the fold: ga[kh] = sum_t G[a][t] FA[py][t][kh]
         for (int kh = 0; kh < 5; ++kh) {
             ga[kh] = 0, gb[kh] = 0;
-            for (int t = 0; t < 4; ++t) ga[kh] += G[a][t] * FA[py][t][kh], gb[kh] += G[b][t] * FA[px][t][kh];
+            for (int t = 0; t < 4; ++t) ga[kh] += G[a][t] * FA[py][t][kh], gb[kh] += fold_wino_gc(TW, b, t) * FA[px][t][kh];
         }
         double u = 0;
         const float *wk = w + ((size_t)n * Cin + k) * 25;
@@ -423,6 +478,34 @@ static bool fold_wino_geometry(int Cout, int Cin, int &kc, int &ncq) {
 // Backward-data of the folded layer: x0 = g = dy * mask [B][Hin = 2H][Win = 2W][C0 = Cout_fwd], out = gradient of the padded
 // low-res tensor [B][Ho = H+4][Wo = W+4][Cout = Cin_fwd]; w = Winograd weights of the flipped parity filters over 4*C0 reduction
 // channels (ops.pack_fold_wino_dgrad).
+// F(2x3) workgroup tile: 32 tiles of 2 x 3 outputs as 16 x 12 (TX 4), 32 x 6 (TX 2) or 4 x 48 (TX 16) outputs, whichever pads the
+// Ho x Wt grid least (as wino6_tile in conv_wino6.hip); returns the padded area.  Parity grids 32x43 / 64x86 / 128x172 (+1 column for
+// the pair form) and backward-data outputs 36x47 / 68x90 / 132x176: tile-level edge waste <= 4.7 %.
+static long wino23_tile(int Ho, int Wt, int &tx) {
+    const int shapes[3] = {4, 2, 16};
+    long best = -1;
+    for (int s = 0; s < 3; ++s) {
+        const int t = shapes[s], th = 2 * (32 / t), tw = 3 * t;
+        const long a = (long)cdiv(Ho, th) * th * cdiv(Wt, tw) * tw;
+        if (best < 0 || a < best) best = a, tx = t;
+    }
+    return best;
+}
+
+template <bool DG, bool PAIR>
+static int launch_wino23(int tx, dim3 grid, size_t lds, const ramnet_conv_desc &d, const Wino24Params &q, hipStream_t st) {
+#define W23_GO(T)                                                                                                         \
+    if (tx == T) {                                                                                                        \
+        RAMNET_FULL_LDS((conv_wino24_kernel<4, DG, T, PAIR, 3>));                                                           \
+        note_kernel("conv_wino24_kernel<4,%d,%d,%d,3>", (int)DG, T, (int)PAIR);                                            \
+        hipLaunchKernelGGL((conv_wino24_kernel<4, DG, T, PAIR, 3>), grid, dim3(512), lds, st, d, q);                        \
+    }
+    W23_GO(2) W23_GO(4) W23_GO(16)
+#undef W23_GO
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+
 static int launch_wino24_dgrad(const ramnet_conv_desc &d, hipStream_t st) {
     RAMNET_CHECK_ARG(d.stride == 1 && d.C0 % 16 == 0 && d.Cout % 64 == 0);
     RAMNET_CHECK_ARG(d.Hin % 2 == 0 && d.Win % 2 == 0 && d.Ho == d.Hin / 2 + 4 && d.Wo == d.Win / 2 + 4 && d.HoF == d.Ho && d.WoF == d.Wo);
@@ -432,9 +515,16 @@ static int launch_wino24_dgrad(const ramnet_conv_desc &d, hipStream_t st) {
     q.cpc = d.C0 / 16, q.nchunks = 4 * q.cpc, q.nblk = d.Cout / 64;
     q.ksplit = 1, q.ws = nullptr, q.cnt = nullptr;
     q.Hc = d.Hin / 2, q.Wc = d.Win / 2;
-    const size_t xb = (size_t)d.B * d.Hin * d.Win * d.ld0 * sizeof(float), wb = (size_t)100 * d.C0 * d.Cout * sizeof(float);
+    const bool w23 = d.algo == RAMNET_ALGO_WINOGRAD24_2X3;
+    const size_t xb = (size_t)d.B * d.Hin * d.Win * d.ld0 * sizeof(float), wb = (size_t)(w23 ? 120 : 100) * d.C0 * d.Cout * sizeof(float);
     RAMNET_CHECK_ARG(xb < 0x40000000ull && wb < 0x7fffffffull);          // invalid window elements use offsets >= 2^30
     q.xbytes = (unsigned)xb, q.wbytes = (unsigned)wb;
+    if (w23) {
+        int tx;
+        wino23_tile(d.Ho, d.Wo, tx);
+        q.tiles_x = cdiv(d.Wo, 3 * tx), q.tiles_y = cdiv(d.Ho, 64 / tx);
+        return launch_wino23<true, false>(tx, dim3((unsigned)(q.tiles_x * q.tiles_y * d.B * q.nblk)), (size_t)2 * W23_V * sizeof(float), d, q, st);
+    }
     // 16 x 8 or 8 x 16 output pixels per workgroup: whichever covers the grid with fewer workgroups
     const bool flat = cdiv(d.Wo, 16) * cdiv(d.Ho, 8) < cdiv(d.Wo, 8) * cdiv(d.Ho, 16);
     q.tiles_x = cdiv(d.Wo, flat ? 16 : 8), q.tiles_y = cdiv(d.Ho, flat ? 8 : 16);
@@ -485,6 +575,37 @@ size_t wino24_splitk_floats(const ramnet_conv_desc &d) {
     return ks > 1 ? wino24_ksplit_floats(gridx, ks) : 0;
 }
 
+// Does this RAMNET_ALGO_WINOGRAD24 launch run F(2x3, 4x4) (RAMNET_ALGO_WINOGRAD24_2X3)?  Forward launches with 64-column workgroups
+// (chunks of 16, the pair form included) and backward-data launches, not split, of at least one full round of workgroups (256: one
+// per CU), where the F(2x3) launch is estimated faster: its workgroups run 30 positions where F(2x2) ones run 25, so the launch takes
+// 30 x ceil(wgs23 / 256) against 25 x ceil(wgs22 / 256) position-times.  The isolated sweep of the three decoder layers over batch 1-32,
+// forward and backward-data (tools/bench_fold23.py, profiles/fold23_sweep.jsonl), never picks a launch that measured slower (those are
+// backward-data launches at batch <= 8, whose last, partial round of longer workgroups costs more than the 20 % fewer MFMAs save, and
+// the launches below one round); ties go to F(2x2), and so do two forward launches below one round that F(2x3) would speed up (batch <= 2).
+static int fold_wino_variant(const ramnet_conv_desc &d, int force) {
+    if (d.algo != RAMNET_ALGO_WINOGRAD24 || d.stride != 1) return 0;
+    long wgs22, wgs23;
+    int tx;
+    if (d.in_mode == RAMNET_IN_PARITY4) {
+        if (d.C0 % 16 != 0 || d.Cout % 64 != 0) return 0;
+        const bool flat = cdiv(d.Wo, 16) * cdiv(d.Ho, 8) < cdiv(d.Wo, 8) * cdiv(d.Ho, 16);
+        wgs22 = (long)cdiv(d.Wo, flat ? 16 : 8) * cdiv(d.Ho, flat ? 8 : 16) * d.B * (d.Cout / 64);
+        wgs23 = wino23_tile(d.Ho, d.Wo, tx) / 192 * d.B * (d.Cout / 64);
+    } else if (d.in_mode == RAMNET_IN_PLAIN) {
+        const bool pair = fold_wino_pair(d.Cout, d.C0), wide = pair || (d.Cout % 64 == 0 && d.C0 % 16 == 0);
+        if (!wide || d.C0 % 32 != 0 || d.Ho < 2 || d.Wo < 2) return 0;
+        const int Wt = pair ? d.Wo + 2 : d.Wo, nblk = pair ? 1 : d.Cout / 64, ncls = pair ? 2 : 4;
+        const bool flat = cdiv(Wt, 16) * cdiv(d.Ho, 8) < cdiv(Wt, 8) * cdiv(d.Ho, 16);
+        wgs22 = (long)cdiv(Wt, flat ? 16 : 8) * cdiv(d.Ho, flat ? 8 : 16) * d.B * nblk * ncls;
+        wgs23 = wino23_tile(d.Ho, pair ? d.Wo + 1 : d.Wo, tx) / 192 * d.B * nblk * ncls;
+        if (!force && wino24_ksplit(d, (int)wgs22, d.C0 / 16) > 1) return 0;          // split launches stay on F(2x2)
+    } else {
+        return 0;
+    }
+    if (force) return 1;                                            // (tests: every structurally eligible launch)
+    return wgs23 >= 256 && 6 * ((wgs23 + 255) / 256) < 5 * ((wgs22 + 255) / 256) ? 1 : 0;
+}
+
 int launch_wino24(const ramnet_conv_desc &d, hipStream_t st) {
     if (d.in_mode == RAMNET_IN_PARITY4) return launch_wino24_dgrad(d, st);
     // d.x0 = replicate-padded low-res input [B][Hin = H+4][Win = W+4][C0]; Ho, Wo = the parity grid (H, W); HoF = 2H, WoF = 2W
@@ -494,13 +615,25 @@ int launch_wino24(const ramnet_conv_desc &d, hipStream_t st) {
     RAMNET_CHECK_ARG(d.C0 % (wide ? 32 : 16) == 0);            // an even number of chunks (the chunk loop is unrolled by two)
     RAMNET_CHECK_ARG(d.C0 % 8 == 0 && d.Cout % 32 == 0 && d.Hin == d.Ho + 4 && d.Win == d.Wo + 4 && d.HoF == 2 * d.Ho && d.WoF == 2 * d.Wo);
     RAMNET_CHECK_ARG((d.epi == RAMNET_EPI_RELU || d.epi == RAMNET_EPI_LINEAR) && d.beta == 0.f && d.out_s2d == 0 && d.Ho >= 2 && d.Wo >= 2);
+    const bool w23 = d.algo == RAMNET_ALGO_WINOGRAD24_2X3;
+    if (w23) RAMNET_CHECK_ARG(wide && d.splitk_ws == nullptr);     // F(2x3): 64-column workgroups, no split reduction
     Wino24Params q;
     q.x = d.x0, q.wp = d.w, q.Hp = d.Hin, q.Wp = d.Win, q.ldx = d.ld0;
     q.nchunks = d.C0 / (wide ? 16 : 8), q.nblk = pair ? 1 : d.Cout / (wide ? 64 : 32);
     q.Hc = d.Ho, q.Wc = d.Wo, q.cpc = 1;
-    const size_t xb = (size_t)d.B * d.Hin * d.Win * d.ld0 * sizeof(float), wb = (size_t)100 * d.C0 * d.Cout * sizeof(float);
+    const size_t xb = (size_t)d.B * d.Hin * d.Win * d.ld0 * sizeof(float), wb = (size_t)(w23 ? 120 : 100) * d.C0 * d.Cout * sizeof(float);
     RAMNET_CHECK_ARG(xb < 0xffffffffull && wb < 0x7fffffffull);
     q.xbytes = (unsigned)xb, q.wbytes = (unsigned)wb;
+    if (w23) {
+        // pair: column parity 1 is tiled with its origins one column to the left, so the tiles cover Wo + 1 columns
+        int tx;
+        wino23_tile(d.Ho, pair ? d.Wo + 1 : d.Wo, tx);
+        q.tiles_x = cdiv(pair ? d.Wo + 1 : d.Wo, 3 * tx), q.tiles_y = cdiv(d.Ho, 64 / tx);
+        q.ksplit = 1, q.ws = nullptr, q.cnt = nullptr;
+        const dim3 grid((unsigned)(q.tiles_x * q.tiles_y * d.B * q.nblk * (pair ? 2 : 4)));
+        const size_t lds = (size_t)2 * W23_V * sizeof(float);
+        return pair ? launch_wino23<false, true>(tx, grid, lds, d, q, st) : launch_wino23<false, false>(tx, grid, lds, d, q, st);
+    }
     const int Wt = pair ? d.Wo + 2 : d.Wo;                     // pair: one more tile column (the shifted tiling of column parity 1)
     const bool flat = wide && cdiv(Wt, 16) * cdiv(d.Ho, 8) < cdiv(Wt, 8) * cdiv(d.Ho, 16);      // 8 x 16 instead of 16 x 8 pixels
     q.tiles_x = cdiv(Wt, wide && !flat ? 8 : 16), q.tiles_y = cdiv(d.Ho, flat ? 8 : 16);
@@ -542,24 +675,26 @@ int launch_wino24(const ramnet_conv_desc &d, hipStream_t st) {
 // with one class, chunks of 16 and 64-column blocks: i = ((((chunk*NB + nb)*25 + pos)*4 + cq)*4 + ks)*64 + l15*4 + j,
 // k = chunk*16 + ks*4 + j = (p*2 + q)*Cout + n, c = nb*64 + cq*16 + l15;
 // U[a][b][k][c] = sum_{t,s} G[a][t] G[b][s] W4[n][c][p][q][3-t][3-s],  W4 = FA_p w FA_q^T (double arithmetic, like the forward pack)
+template <int TW>
 __global__ void pack_weight_fold_wino_dgrad_kernel(const float *__restrict__ w, float *__restrict__ wp, int Cout, int Cin, size_t total) {
     const double FA[2][4][5] = {{{.25, 0, 0, 0, 0}, {.75, .75, .25, 0, 0}, {0, .25, .75, .75, .25}, {0, 0, 0, .25, .75}},
                                 {{.75, .25, 0, 0, 0}, {.25, .75, .75, .25, 0}, {0, 0, .25, .75, .75}, {0, 0, 0, 0, .25}}};
     const double G[5][4] = {{0.5, 0, 0, 0}, {-0.5, -0.5, -0.5, -0.5}, {-1.0 / 6, 1.0 / 6, -1.0 / 6, 1.0 / 6}, {1.0 / 6, 1.0 / 3, 2.0 / 3, 4.0 / 3}, {0, 0, 0, 1}};
+    constexpr int WC = TW + 3, NP = 5 * WC;
     const int NB = Cin / 64;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         size_t r = i;
         const int j = (int)(r & 3), l15 = (int)((r >> 2) & 15), ks = (int)((r >> 6) & 3), cq = (int)((r >> 8) & 3);
         r >>= 10;
-        const int pos = (int)(r % 25);
-        r /= 25;
+        const int pos = (int)(r % NP);
+        r /= NP;
         const int nb = (int)(r % NB), chunk = (int)(r / NB);
         const int k = chunk * 16 + ks * 4 + j, c = nb * 64 + cq * 16 + l15;
-        const int pq = k / Cout, n = k - pq * Cout, pp = pq >> 1, qq = pq & 1, a = pos / 5, b = pos % 5;
+        const int pq = k / Cout, n = k - pq * Cout, pp = pq >> 1, qq = pq & 1, a = pos / WC, b = pos % WC;
         double ga[5], gb[5];
         for (int kh = 0; kh < 5; ++kh) {
             ga[kh] = 0, gb[kh] = 0;
-            for (int t = 0; t < 4; ++t) ga[kh] += G[a][t] * FA[pp][3 - t][kh], gb[kh] += G[b][t] * FA[qq][3 - t][kh];
+            for (int t = 0; t < 4; ++t) ga[kh] += G[a][t] * FA[pp][3 - t][kh], gb[kh] += fold_wino_gc(TW, b, t) * FA[qq][3 - t][kh];
         }
         double u = 0;
         const float *wk = w + ((size_t)n * Cin + c) * 25;
@@ -669,7 +804,7 @@ extern "C" int ramnet_pack_weight_fold_wino(const float *w, float *wp, int Cout,
     const size_t total = (size_t)100 * Cout * Cin;
     size_t blocks = (total + 255) / 256;
     if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(pack_weight_fold_wino_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin, kc, ncq,
+    hipLaunchKernelGGL(pack_weight_fold_wino_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin, kc, ncq,
                        (int)fold_wino_pair(Cout, Cin), total);
     RAMNET_LAUNCH_CHECK();
     return 0;
@@ -680,10 +815,36 @@ extern "C" int ramnet_pack_weight_fold_wino_dgrad(const float *w, float *wp, int
     const size_t total = (size_t)100 * Cout * Cin;
     size_t blocks = (total + 255) / 256;
     if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(pack_weight_fold_wino_dgrad_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin, total);
+    hipLaunchKernelGGL(pack_weight_fold_wino_dgrad_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin, total);
     RAMNET_LAUNCH_CHECK();
     return 0;
 }
+
+extern "C" size_t ramnet_packed_weight_elems_fold_wino2x3(int Cout, int Cin) { return (size_t)120 * Cout * Cin; }
+
+extern "C" int ramnet_pack_weight_fold_wino2x3(const float *w, float *wp, int Cout, int Cin, void *stream) {
+    int kc, ncq;
+    RAMNET_CHECK_ARG(w && wp && Cout > 0 && Cin > 0 && fold_wino_geometry(Cout, Cin, kc, ncq) && kc == 16);
+    const size_t total = (size_t)120 * Cout * Cin;
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 65535) blocks = 65535;
+    hipLaunchKernelGGL(pack_weight_fold_wino_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin, kc, ncq,
+                       (int)fold_wino_pair(Cout, Cin), total);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ramnet_pack_weight_fold_wino2x3_dgrad(const float *w, float *wp, int Cout, int Cin, void *stream) {
+    RAMNET_CHECK_ARG(w && wp && Cout > 0 && Cin > 0 && Cin % 64 == 0 && (4 * Cout) % 16 == 0);
+    const size_t total = (size_t)120 * Cout * Cin;
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 65535) blocks = 65535;
+    hipLaunchKernelGGL(pack_weight_fold_wino_dgrad_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin, total);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ramnet_fold_wino_variant(const ramnet_conv_desc *d, int force) { return d ? fold_wino_variant(*d, force) : 0; }
 
 extern "C" int ramnet_pack_border_weights(const float *w, float *rows, float *cols, float *rows_t, float *cols_t, int Cout, int Cin, void *stream) {
     RAMNET_CHECK_ARG(w && rows && cols && rows_t && cols_t && Cout > 0 && Cin > 0);

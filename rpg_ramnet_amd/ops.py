@@ -179,6 +179,18 @@ def set_fold_winograd(on):
     _FOLD_WINO = bool(on)
 
 
+_FOLD_2X3 = "auto"
+
+
+def set_fold_winograd_2x3(mode):
+    """F(2x3,4x4) variant of the folded decoders' Winograd forward / backward-data launches (conv_wino24_kernel<.., 3>): "auto" = where
+    the library's size heuristics pick it (ramnet_fold_wino_variant: the training-batch launches), "off" = F(2x2,4x4) everywhere,
+    "force" = every structurally eligible launch (tests)."""
+    global _FOLD_2X3
+    assert mode in ("auto", "off", "force")
+    _FOLD_2X3 = mode
+
+
 def set_fold_upsample(on):
     global _FOLD_UP
     _FOLD_UP = bool(on)
@@ -343,7 +355,7 @@ def _conv_desc(x0, taps, w, out, Cout, *, stride=1, x1=None, xm=None, xm_off=0, 
     key = (id(taps), id(w.cp) if is_ref else 0, w.transposed if is_ref else -1, id(ws_owner), Cout, stride, in_mode, C0, C1, Hin, Win, epi, beta, Ho,
            Wo, os, out_off, frame, out_s2d, wino24, xm_off, tuple(x0.shape), x0.stride(2), _sd(x1), _sd(xm), out.shape[1], out.shape[2],
            out.stride(2), _sd(e0), _sd(e1), _sd(o1), _sd(o2), bias is None, al & 15, _WINOGRAD, _WINO_2X4, _SPLIT_OPERANDS, _HEAD, _S2D_SPARSE, _S2D_2X4,
-           _DESC_EPOCH, x0.device.index)
+           _FOLD_2X3, _DESC_EPOCH, x0.device.index)
     hit = _DESC_CACHE.get(key) if _DESC_CACHE_ON else None
     if hit is not None and (not is_ref or hit[3]() is w.cp) and (ws_owner is None or hit[4]() is ws_owner):
         tmpl, kind, nsplit = hit[0], hit[1], hit[2]
@@ -351,7 +363,10 @@ def _conv_desc(x0, taps, w, out, Cout, *, stride=1, x1=None, xm=None, xm_off=0, 
         d.x0, d.x1, d.xm = _p(x0), _p(x1), _p(xm, xm_off)
         d.bias, d.e0, d.e1 = _p(bias), _p(e0), _p(e1)
         d.out, d.o1, d.o2 = _p(out, out_off), _p(o1), _p(o2)
-        d.w = _p(w) if kind is None else _p(w.cp.pack(0, "head") if kind == "head" else w.cp.pack(w.transposed, kind))
+        if kind in ("f23", "f23d"):
+            d.w = _p(ws_owner.pack_fold_wino2x3_dgrad() if kind == "f23d" else ws_owner.pack_fold_wino2x3())
+        else:
+            d.w = _p(w) if kind is None else _p(w.cp.pack(0, "head") if kind == "head" else w.cp.pack(w.transposed, kind))
         if nsplit:
             d.splitk_ws = _p((w.cp if is_ref else ws_owner).splitk_ws(nsplit, x0.device))
         return d
@@ -371,7 +386,8 @@ def _conv_desc_build(x0, taps, w, out, Cout, meta, *, stride=1, x1=None, xm=None
                      C0=None, C1=0, Hin=None, Win=None, bias=None, epi=H.EPI_LINEAR, beta=0.0, e0=None, e1=None,
                      o1=None, o2=None, Ho=None, Wo=None, os=(1, 1, 0, 0), out_off=0, frame=0, out_s2d=0, wino24=False, ws_owner=None):
     """The descriptor from scratch; meta <- [which pack of the layer d.w points at (None: `w` is a packed tensor itself; "head"; False /
-    True / "2x4": ConvParam.pack(transposed, kind)), floats of the split-reduction workspace (0: none)]."""
+    True / "2x4": ConvParam.pack(transposed, kind); "f23" / "f23d": ws_owner.pack_fold_wino2x3[_dgrad]()), floats of the split-reduction
+    workspace (0: none)]."""
     B = x0.shape[0]
     kind, nsplit = None, 0
     d = H.ConvDesc()
@@ -416,6 +432,11 @@ def _conv_desc_build(x0, taps, w, out, Cout, meta, *, stride=1, x1=None, xm=None
         if _SPLIT_OPERANDS and H.lib().ramnet_conv_wino_split_ok(C.byref(d), int(_WINO_2X4 == "force")):
             d.algo, kind = H.ALGO_WINOGRAD_2X4_SPLIT, "2x4s"       # the same launch on the bf16 matrix pipe, split operands (csrc/conv_wino6s.hip)
         d.w = _p(ref.cp.pack(ref.transposed, kind))
+    if wino24 and cp is not None and _FOLD_2X3 != "off" and H.lib().ramnet_fold_wino_variant(C.byref(d), int(_FOLD_2X3 == "force")):
+        # F(2x3,4x4) on the training-batch decoder launches (csrc/conv_wino24.hip, TW = 3): its own Winograd-domain pack of the layer
+        kind = "f23d" if in_mode == H.IN_PARITY4 else "f23"
+        d.algo = H.ALGO_WINOGRAD24_2X3
+        d.w = _p(cp.pack_fold_wino2x3_dgrad() if kind == "f23d" else cp.pack_fold_wino2x3())
     if d.algo in (H.ALGO_WINOGRAD, H.ALGO_WINOGRAD24) and cp is not None:
         # latency-bound launches (batch-1 streaming on the coarse scales) split their channel reduction: the library says how much
         # workspace the launch would use, the layer owns it (csrc/conv_wino.hip, ramnet_conv_desc.splitk_ws)
@@ -950,6 +971,27 @@ class ConvParam:
             hit = self._packs["fold24d"] = (v, out)
         return hit[1]
 
+    def pack_fold_wino2x3(self):
+        """Winograd-domain weights of the folded upsample-conv for F(2x3,4x4) launches (conv_wino24_kernel<.., 3>), cached per parameter version."""
+        v = (self._versions(self.weights), "fold23")
+        hit = self._packs.get("fold23")
+        if hit is None or hit[0] != v:
+            L, w = H.lib(), self._cat_w()
+            out = torch.empty(L.ramnet_packed_weight_elems_fold_wino2x3(self.Cout, self.Cin), device=w.device, dtype=torch.float32)
+            H.check(L.ramnet_pack_weight_fold_wino2x3(_p(w), _p(out), self.Cout, self.Cin, _st()), "ramnet_pack_weight_fold_wino2x3")
+            hit = self._packs["fold23"] = (v, out)
+        return hit[1]
+
+    def pack_fold_wino2x3_dgrad(self):
+        v = (self._versions(self.weights), "fold23d")
+        hit = self._packs.get("fold23d")
+        if hit is None or hit[0] != v:
+            L, w = H.lib(), self._cat_w()
+            out = torch.empty(L.ramnet_packed_weight_elems_fold_wino2x3(self.Cout, self.Cin), device=w.device, dtype=torch.float32)
+            H.check(L.ramnet_pack_weight_fold_wino2x3_dgrad(_p(w), _p(out), self.Cout, self.Cin, _st()), "ramnet_pack_weight_fold_wino2x3_dgrad")
+            hit = self._packs["fold23d"] = (v, out)
+        return hit[1]
+
     def _border_pack(self):
         """(rows, cols, rows^T, cols^T) of the border matrices (tests/torch_restatements.border_matrices is the plain-torch statement; one launch of
         ramnet_pack_border_weights), cached per parameter version."""
@@ -1432,7 +1474,7 @@ def _folded_upsample_dgrad(x, dy, y, cp):
         g = torch.empty_like(dy)
         H.check(L.ramnet_relu_bwd(_p(dy), _p(y), _p(g), dy.numel(), _st()), "ramnet_relu_bwd")
     dxpad = torch.empty(B, Hh + 4, W + 4, Cc, device=dev)
-    conv_launch(g, Taps.get("fold", 4, 0, 0, 0), cp.pack_fold_wino_dgrad(), dxpad, Cc, in_mode=H.IN_PARITY4, wino24=True)
+    conv_launch(g, Taps.get("fold", 4, 0, 0, 0), cp.pack_fold_wino_dgrad(), dxpad, Cc, in_mode=H.IN_PARITY4, wino24=True, ws_owner=cp)
     dx = torch.empty(B, Hh, W, Cc, device=dev)
     H.check(L.ramnet_unpad2_fold(_p(dxpad), _p(dx), B, Hh, W, Cc, _st()), "ramnet_unpad2_fold")
     g_rows = torch.empty(2, B * W2, 2 * cp.Cout, device=dev)

@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define RAMNET_ABI_VERSION 26      /* 26: RAMNET_ALGO_WINOGRAD24_2X3 (F(2x3,4x4) folded decoders) + ramnet_fold_wino_variant / ramnet_pack_weight_fold_wino2x3[_dgrad] / ramnet_packed_weight_elems_fold_wino2x3; 25: ramnet_conv_desc.active (per-sample update masks of the cell epilogues: batched irregular packages) + ramnet_lstm_bwd_masked; 24: ramnet_cat_batch_add_masked (the gradient of a time-batched ReLU feature leaves its fan-in already masked), ramnet_pred_sigmoid_si_bwd takes the forward's scratch (fixed-order join of the weight / bias partial sums); 23: ramnet_wgrad_desc.algo = RAMNET_ALGO_DIRECT_SPLIT (direct 3x3 backward-weights on the bf16 matrix pipe, split operands: csrc/conv_wgrad_dsplit.hip) + ramnet_wgrad_dsplit_slabs; 22: RAMNET_ALGO_WINOGRAD_2X4_SPLIT + ramnet_conv_wino_split_ok / ramnet_pack_weight_wino2x4_split (split bf16 operands on the F(2x4,3x3) forward / backward-data launches); 21: RAMNET_EPI_SIGMOID_HR (the ConvGRU gates launch also writes h.r: the candidate convolution and its backward-weights read a plain concatenation); 20 (never released on its own: shipped together with 21): ramnet_wgrad_desc.nseg / segs (multi-segment backward-weights launches: deferred ConvGRU cell updates); 19: ramnet_cat_batch_add (gradient of a time-batched feature); 18: RAMNET_EPI_GRU_BWD (stage B of the ConvGRU backward in the epilogue of the candidate convolution's backward-data launch) + ramnet_gru_bwd_a2; 17: ramnet_wgrad_desc.algo = RAMNET_ALGO_WINOGRAD_2X4 (F(2x4,3x3) backward-weights, csrc/conv_wgrad_wino6.hip) + ramnet_wgrad_wino2x4_slabs / ramnet_unpack_wgrad_wino2x4, option "wgrad_wino_nf"; 16: ramnet_conv_desc.splitk_ws / splitk_floats + ramnet_conv_splitk_floats (split channel reduction of latency-bound Winograd launches), option "wino_ksplit"; 15: ramnet_si_loss_from_stats (data-parallel exact loss), ramnet_si_log_loss_* / ramnet_mse_loss_*, ramnet_reflect_pad, ramnet_wgrad_desc.dw_slabs + ramnet_reduce_slabs, ramnet_set_option (environment knobs removed), fold weight-algebra kernels, RAMNET_ALGO_WINOGRAD_2X4 + ramnet_conv_wino_variant / ramnet_pack_weight_wino2x4; 14: ramnet_norm_* (BatchNorm / InstanceNorm); 13: pair layout of ramnet_pack_weight_fold_wino, head kernel for 10 input channels */
+#define RAMNET_ABI_VERSION 27      /* 27: RAMNET_EPI_LSTM on RAMNET_ALGO_WINOGRAD_2X4 (the ConvLSTM cell epilogue of the F(2x4,3x3) kernel) + ramnet_pack_weight_wino2x4_gates / ramnet_packed_weight_elems_wino2x4_gates (gate-interleaved pack); 26: RAMNET_ALGO_WINOGRAD24_2X3 (F(2x3,4x4) folded decoders) + ramnet_fold_wino_variant / ramnet_pack_weight_fold_wino2x3[_dgrad] / ramnet_packed_weight_elems_fold_wino2x3; 25: ramnet_conv_desc.active (per-sample update masks of the cell epilogues: batched irregular packages) + ramnet_lstm_bwd_masked; 24: ramnet_cat_batch_add_masked (the gradient of a time-batched ReLU feature leaves its fan-in already masked), ramnet_pred_sigmoid_si_bwd takes the forward's scratch (fixed-order join of the weight / bias partial sums); 23: ramnet_wgrad_desc.algo = RAMNET_ALGO_DIRECT_SPLIT (direct 3x3 backward-weights on the bf16 matrix pipe, split operands: csrc/conv_wgrad_dsplit.hip) + ramnet_wgrad_dsplit_slabs; 22: RAMNET_ALGO_WINOGRAD_2X4_SPLIT + ramnet_conv_wino_split_ok / ramnet_pack_weight_wino2x4_split (split bf16 operands on the F(2x4,3x3) forward / backward-data launches); 21: RAMNET_EPI_SIGMOID_HR (the ConvGRU gates launch also writes h.r: the candidate convolution and its backward-weights read a plain concatenation); 20 (never released on its own: shipped together with 21): ramnet_wgrad_desc.nseg / segs (multi-segment backward-weights launches: deferred ConvGRU cell updates); 19: ramnet_cat_batch_add (gradient of a time-batched feature); 18: RAMNET_EPI_GRU_BWD (stage B of the ConvGRU backward in the epilogue of the candidate convolution's backward-data launch) + ramnet_gru_bwd_a2; 17: ramnet_wgrad_desc.algo = RAMNET_ALGO_WINOGRAD_2X4 (F(2x4,3x3) backward-weights, csrc/conv_wgrad_wino6.hip) + ramnet_wgrad_wino2x4_slabs / ramnet_unpack_wgrad_wino2x4, option "wgrad_wino_nf"; 16: ramnet_conv_desc.splitk_ws / splitk_floats + ramnet_conv_splitk_floats (split channel reduction of latency-bound Winograd launches), option "wino_ksplit"; 15: ramnet_si_loss_from_stats (data-parallel exact loss), ramnet_si_log_loss_* / ramnet_mse_loss_*, ramnet_reflect_pad, ramnet_wgrad_desc.dw_slabs + ramnet_reduce_slabs, ramnet_set_option (environment knobs removed), fold weight-algebra kernels, RAMNET_ALGO_WINOGRAD_2X4 + ramnet_conv_wino_variant / ramnet_pack_weight_wino2x4; 14: ramnet_norm_* (BatchNorm / InstanceNorm); 13: pair layout of ramnet_pack_weight_fold_wino, head kernel for 10 input channels */
 #define RAMNET_E_BADARG 10001
 #define RAMNET_E_UNSUPPORTED 10002
 
@@ -81,7 +81,11 @@ enum ramnet_epilogue {
     RAMNET_EPI_SIGMOID = 2,   /* sigmoid(acc + bias)                 GRU gates submodules.py:448-449 */
     RAMNET_EPI_RES_RELU = 3,  /* relu(acc + bias + e0)               ResidualBlock submodules.py:212-214 */
     RAMNET_EPI_GRU_BLEND = 4, /* o=tanh(acc+bias); out=h*(1-u)+o*u   submodules.py:450-452; e0=u, e1=h, o1<-o */
-    RAMNET_EPI_LSTM = 5,      /* i,f,o,g -> c'=f*c+i*g, h'=o*tanh(c') submodules.py:346-358; e1=c, out<-h', o1<-c', o2<-gates */
+    RAMNET_EPI_LSTM = 5,      /* i,f,o,g -> c'=f*c+i*g, h'=o*tanh(c') submodules.py:346-358; e1=c, out<-h', o1<-c', o2<-gates.
+                               * Families: DIRECT, WINOGRAD (w from ramnet_pack_weight_wino with gates = 4) and, ABI 27, WINOGRAD_2X4 where
+                               * ramnet_conv_wino_variant() accepts the descriptor (RAMNET_IN_CAT, C0 % 8 == 0, hidden size Cout % 16 == 0,
+                               * bias and o1 present, 16-byte-accessible operands, unit output strides; w from ramnet_pack_weight_wino2x4_gates
+                               * with gates = 4).  Never WINOGRAD_2X4_SPLIT: ramnet_conv_wino_split_ok() answers 0 for the cell.         */
     RAMNET_EPI_GRU_BWD = 6,   /* backward-data of the candidate convolution W_o*[x, h.r] (ABI 18; Cout = 2C, no bias, beta = 0): channels n < C
                                * (dx) are stored as they are; channels n >= C carry g = d(h.r): with r = e0[pix*lde0 + n] (e0 = [u|r]),
                                * h = e1[pix*lde1 + n - C] (NULL: 0): o1[pix*ldo1 + n] <- g*h*r*(1-r) (the reset gate's pre-activation gradient)
@@ -144,8 +148,8 @@ typedef struct ramnet_conv_desc {
                                      *   RAMNET_EPI_LSTM: e0 = h (required, lde0), out <- h, o1 <- c (e1; NULL: 0), o2 <- 0.
                                      * With u = r = o = 0 the unmasked ConvGRU backward gives dh = dh', zero pre-activation gradients and
                                      * no contribution to dx or dW for those samples; the ConvLSTM uses ramnet_lstm_bwd_masked.  Every
-                                     * family a cell launch can take honours it (DIRECT, WINOGRAD incl. its split reduction, WINOGRAD_2X4,
-                                     * WINOGRAD_2X4_SPLIT); the others refuse the descriptor.                                          */
+                                     * family a cell launch can take honours it (DIRECT, WINOGRAD incl. its split reduction, WINOGRAD_2X4 — the
+                                     * ConvLSTM cell included, ABI 27 —, WINOGRAD_2X4_SPLIT); the others refuse the descriptor.                                          */
 } ramnet_conv_desc;
 
 /* Weight-gradient launch: dW[t][c][n] += sum_{b,a,b'} in(a*stride+dy[t], b'*stride+dx[t], c) * g(a,b',n)
@@ -266,6 +270,11 @@ int ramnet_pack_weight_wino(const float *w_oihw, float *wp, int Cout, int Cin, i
  * [Cin/8][Cout/64][row 4][column 6][n-block 2][lane 64][4], zero padded; transposed=1: the backward-data operator.            */
 size_t ramnet_packed_weight_elems_wino2x4(int Cout, int Cin, int transposed);
 int ramnet_pack_weight_wino2x4(const float *w_oihw, float *wp, int Cout, int Cin, int transposed, void *stream);
+/* ABI 27: the same with gates = 1; gates = 4 (forward only, Cout = 4C with C % 16 == 0) is the pack of a RAMNET_EPI_LSTM launch on
+ * RAMNET_ALGO_WINOGRAD_2X4: the 32 columns of n-block f of 64-column block nb are 8 hidden channels x gates (i, f, o, g) — column n is gate
+ * n >> 3 of hidden channel nb*16 + f*8 + (n & 7) — so that one workgroup holds the four gates of its hidden channels.  Same size.       */
+size_t ramnet_packed_weight_elems_wino2x4_gates(int Cout, int Cin, int transposed, int gates);
+int ramnet_pack_weight_wino2x4_gates(const float *w_oihw, float *wp, int Cout, int Cin, int transposed, int gates, void *stream);
 /* 1 when a launch that qualifies for RAMNET_ALGO_WINOGRAD (d->algo set so, every other field final) runs faster as
  * RAMNET_ALGO_WINOGRAD_2X4 — the caller then sets d->algo and d->w (ramnet_pack_weight_wino2x4) accordingly; else 0.              */
 int ramnet_conv_wino_variant(const ramnet_conv_desc *d, int force);   /* force: skip the size heuristics (tests) */

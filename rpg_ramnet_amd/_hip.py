@@ -93,6 +93,8 @@ _SIGS = {
     "ramnet_pack_weight_wino": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ramnet_packed_weight_elems_wino2x4": (C.c_size_t, [C.c_int] * 3),
     "ramnet_pack_weight_wino2x4": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
+    "ramnet_packed_weight_elems_wino2x4_gates": (C.c_size_t, [C.c_int] * 4),
+    "ramnet_pack_weight_wino2x4_gates": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ramnet_wino2x4_config": (C.c_int, [C.c_int]),
     "ramnet_conv_wino_variant": (C.c_int, [C.POINTER(ConvDesc), C.c_int]),
     "ramnet_conv_wino_split_ok": (C.c_int, [C.POINTER(ConvDesc), C.c_int]),
@@ -218,7 +220,7 @@ def lib():
         for name, (res, args) in _SIGS.items():
             fn = getattr(l, name)
             fn.restype, fn.argtypes = res, args
-        if l.ramnet_abi_version() != 26:
+        if l.ramnet_abi_version() != 27:
             raise RuntimeError("ABI version mismatch in %s" % LIB_PATH)
         _lib = l
     return _lib if _tracer is None else _Traced(_lib)

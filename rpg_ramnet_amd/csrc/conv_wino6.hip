@@ -1,6 +1,6 @@
 // Winograd F(2x4, 3x3) convolution for gfx950 (MI355X): forward and backward-data of the 3x3 stride-1 layers of the RAM-Net path at the
-// training batch — ConvGRU gates / candidate (submodules.py:447-452), residual blocks (:200-215) and every backward-data launch of those
-// layers (launches of >= 150 64-channel x 256-pixel output blocks: wino6_eligible) — exact-fp32 arithmetic on v_mfma_f32_32x32x2_f32.
+// training batch — ConvGRU gates / candidate (submodules.py:447-452), the ConvLSTM gates + cell (:346-358), residual blocks (:200-215) and
+// every backward-data launch of those layers (launches of >= 150 64-channel x 256-pixel output blocks: wino6_eligible) — exact-fp32 arithmetic on v_mfma_f32_32x32x2_f32.
 //
 //   Y = A2^T [ sum_ci (G2 g G4^T) .* (B2^T d B4) ] A4        F(2,3) down the rows, F(4,3) along the columns (Lavin & Gray 2016)
 //
@@ -56,7 +56,9 @@ template <int TXG> struct R6Geom {
 };
 
 // MASK: cell launch with a per-sample update mask (ramnet_conv_desc.active; separate instantiations of the concatenated input modes)
-template <int TXG, int MODE, bool MASK = false>
+// LSTM: the ConvLSTM cell (RAMNET_EPI_LSTM) — an epilogue of its own over gate-interleaved columns that only these instantiations contain
+// (RAMNET_IN_CAT, plain and MASK); every other epilogue kind lives in the LSTM = false instantiations, which carry no trace of it.
+template <int TXG, int MODE, bool MASK = false, bool LSTM = false>
 __global__ void __launch_bounds__(256, 2) conv_wino_r6_kernel(const ramnet_conv_desc p, const WinoParams q) {
     constexpr int NF = 1;                        // 32-channel output blocks per workgroup (the index algebra below keeps the general form)
     constexpr int RO_LD = NF * 32 + 4;           // row of the exchange buffer [wave 4][column 4][tile 32][channels + pad]
@@ -258,6 +260,14 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r6_kernel(const ramnet_conv_
     const int qd = tid & 7, nq = n0 + qd * 4;
     const bool nok = nq < p.Cout;
     const float4 bias4 = p.bias ? ld4(p.bias + (nok ? nq : 0)) : f4zero();
+    // (ConvLSTM cell: the workgroup's 32 columns are 8 hidden channels x gates (i, f, o, g) — pack_weight_wino_r6_kernel, gates = 4 —, a
+    // thread owns hidden channel quad tid & 1 of two pixels: its four gate bias quads; p.Cout = hidden size C, a multiple of 16: launcher)
+    const int lchn = nblk_i * 16 + fh * 8 + (tid & 1) * 4;
+    float4 lbias[4];
+    if constexpr (LSTM) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) lbias[g] = ld4(p.bias + g * p.Cout + lchn);
+    }
     // ---- exchange: column transform of the wave's row (M A4: 4 of 6 columns), all waves -> LDS.
     // A4^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
     // D of the 32x32 MFMA (weights first, round 6): col = lane & 31 (TILE), row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) (channel): registers
@@ -311,6 +321,61 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r6_kernel(const ramnet_conv_
     auto off0_of = [&](int ld, bool have, int dn = 0) { return have ? (pix0 * (unsigned)ld + (unsigned)(nq + dn)) * 4u : WOOB; };
     auto step_of = [&](int ld) { return (unsigned)(RSTEP * p.WoF * ld * 4); };
     const auto r_out = rsrc_of(p.out, p.ldo);
+    if constexpr (LSTM) {
+        // ---- ConvLSTM cell (submodules.py:346-358): i, f, o = sigmoid, g = tanh, c' = f c + i g, h' = o tanh(c'); out <- h', o1 <- c', o2 <-
+        // the activated gates [4C] in (i, f, o, g) order (NULL: inference), e1 = c (NULL: zeros).  Thread (tid >> 1, tid & 1) owns hidden
+        // channel quad tid & 1 of the pixels pxl = (tid >> 1) + 128 i, i = 0, 1 — one column of the tile, rows 128 / TW apart — and reads
+        // the same quad of all four gates (columns 8 g + 4 (tid & 1)) out of the exchange buffer.  Same straight-line form as the
+        // channel-quad epilogue below: c of both pixels (and h for a masked launch: what an inactive sample copies) requested first, then
+        // per pixel the 12 LDS reads before the first value is used; a pixel outside the map or a missing tensor: offset WOOB.
+        // Inactive sample of a MASK launch (uniform over the workgroup): h' = h, c' = c as copies, gates 0 — selects, no branch.
+        constexpr int LSTEP = 128 / RTW;
+        const int C = p.Cout, lpx = (tid >> 1) % RTW, lpy = (tid >> 1) / RTW;
+        const unsigned lpix = (unsigned)((oy0 + lpy) * p.WoF + ox0 + lpx);
+        const float *lb0 = P + ((lpx & 3) * 32 + (lpx >> 2)) * RO_LD + (tid & 1) * 4;
+        const auto r_c = rsrc_of(p.e1, p.lde1), r_h = MASK ? rsrc_of(p.e0, p.lde0) : r_out;
+        const auto r_cn = rsrc_of(p.o1, p.ldo1), r_g = rsrc_of(p.o2, p.ldo2);
+        const bool lact = !MASK || sample_active(p, b);
+        auto lsel = [&](float4 v, float4 w) { return make_float4(lact ? v.x : w.x, lact ? v.y : w.y, lact ? v.z : w.z, lact ? v.w : w.w); };
+        unsigned lbad[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) lbad[i] = (ox0 + lpx < p.Wo && oy0 + lpy + i * LSTEP < p.Ho) ? 0u : WOOB;
+        auto loff = [&](int ld, bool have, int i) {
+            return have ? ((lpix * (unsigned)ld + (unsigned)lchn) * 4u + (unsigned)(i * LSTEP * p.WoF * ld * 4)) | lbad[i] : WOOB;
+        };
+        float4 cp[2], hp[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            cp[i] = bld(r_c, loff(p.lde1, p.e1 != nullptr, i));
+            if (MASK) hp[i] = bld(r_h, loff(p.lde0, true, i));
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int py = lpy + i * LSTEP;
+            const float *bb = lb0 + ((py >> 1) * TXG + (py & 1) * 128) * RO_LD;
+            const float sg = (py & 1) ? -1.f : 1.f;
+            float4 t0[4], t1[4], t2[4], a[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) t0[g] = ld4(bb + 8 * g), t1[g] = ld4(bb + 128 * RO_LD + 8 * g), t2[g] = ld4(bb + 256 * RO_LD + 8 * g);
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                a[g] = f4add(make_float4(fmaf(sg, t2[g].x, fmaf(sg, t1[g].x, t0[g].x)), fmaf(sg, t2[g].y, fmaf(sg, t1[g].y, t0[g].y)),
+                                         fmaf(sg, t2[g].z, fmaf(sg, t1[g].z, t0[g].z)), fmaf(sg, t2[g].w, fmaf(sg, t1[g].w, t0[g].w))), lbias[g]);
+            float4 gi = make_float4(sigmoidf_(a[0].x), sigmoidf_(a[0].y), sigmoidf_(a[0].z), sigmoidf_(a[0].w));
+            float4 gf = make_float4(sigmoidf_(a[1].x), sigmoidf_(a[1].y), sigmoidf_(a[1].z), sigmoidf_(a[1].w));
+            float4 go = make_float4(sigmoidf_(a[2].x), sigmoidf_(a[2].y), sigmoidf_(a[2].z), sigmoidf_(a[2].w));
+            float4 gc = make_float4(tanhf_(a[3].x), tanhf_(a[3].y), tanhf_(a[3].z), tanhf_(a[3].w));
+            const float4 c = cp[i];
+            float4 cn = make_float4(gf.x * c.x + gi.x * gc.x, gf.y * c.y + gi.y * gc.y, gf.z * c.z + gi.z * gc.z, gf.w * c.w + gi.w * gc.w);
+            float4 hn = make_float4(go.x * tanhf_(cn.x), go.y * tanhf_(cn.y), go.z * tanhf_(cn.z), go.w * tanhf_(cn.w));
+            if (MASK) hn = lsel(hn, hp[i]), cn = lsel(cn, c), gi = lsel(gi, f4zero()), gf = lsel(gf, f4zero()), go = lsel(go, f4zero()), gc = lsel(gc, f4zero());
+            bst(r_out, loff(p.ldo, true, i), hn);
+            bst(r_cn, loff(p.ldo1, true, i), cn);
+            const unsigned og = loff(p.ldo2, p.o2 != nullptr, i);      // (+ 12 C bytes at most on WOOB | offset: still out of range)
+            bst(r_g, og, gi), bst(r_g, og + (unsigned)C * 4u, gf), bst(r_g, og + (unsigned)C * 8u, go), bst(r_g, og + (unsigned)C * 12u, gc);
+        }
+        return;
+    }
     auto run = [&](auto kind) {
         // 0: linear / ReLU (+ beta * old), 4: sigmoid, 5: sigmoid + h.r (gates), 1: residual + ReLU, 2: GRU blend, 3: GRU backward stage B
         constexpr int K = decltype(kind)::value;
@@ -425,8 +490,11 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r6_kernel(const ramnet_conv_
 // OIHW 3x3 -> U = G2 g G4^T (evaluated in double) in the lane order of the kernel's B operand:
 // index = (((((chunk * nblk + nb) * 4 + w) * 6 + pl) * 2 + f) * 64 + lane) * 4 + j  ->
 // U[row w][column pl][input channel chunk*8 + 4*(lane >> 5) + j][output channel nb*64 + f*32 + (lane & 31)]
+// gates = 4 (ConvLSTM, forward only; N = 4C, C % 16 == 0): the 32 columns of half f of block nb are 8 hidden channels x gates (i, f, o, g) —
+// column n = lane & 31 is gate n >> 3 of hidden channel nb*16 + f*8 + (n & 7), output channel (n >> 3) * C + that of the OIHW weights —
+// so one workgroup of the kernel holds all four gates of its hidden channels (the cell epilogue).
 __global__ void pack_weight_wino_r6_kernel(const float *__restrict__ w, float *__restrict__ wp, int Cout, int Cin, int transposed,
-                                           int R, int N, int nchunks, int nblk, size_t total) {
+                                           int gates, int R, int N, int nchunks, int nblk, size_t total) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int j = (int)(i & 3), lane = (int)((i >> 2) & 63), f = (int)((i >> 8) & 1);
         size_t jj = i >> 9;
@@ -437,7 +505,8 @@ __global__ void pack_weight_wino_r6_kernel(const float *__restrict__ w, float *_
         const int nb = (int)(jj % nblk), chunk = (int)(jj / nblk);
         const int n = f * 32 + (lane & 31);
         const int r = chunk * WK + 4 * (lane >> 5) + j;
-        const int no = nb * W6_BN + n;
+        int no = nb * W6_BN + n;
+        if (gates > 1) no = ((lane & 31) >> 3) * (N / gates) + nb * 16 + f * 8 + (lane & 7);
         float v = 0.f;
         if (r < R && no < N) {
             double g[3][3];
@@ -483,8 +552,16 @@ static bool wino6_vec4(const ramnet_conv_desc &d) {
            (!d.e0 || (d.lde0 % 4 == 0 && al16(d.e0))) && (!d.e1 || (d.lde1 % 4 == 0 && al16(d.e1)));
 }
 
+// What the ConvLSTM cell epilogue of conv_wino_r6_kernel needs beyond wino6_vec4: concatenated input on a chunk boundary, hidden size a
+// multiple of 16 (4C gate columns = whole 64-column blocks), bias and o1 present, 16-byte-accessible gates, dense output
+static bool wino6_lstm_ok(const ramnet_conv_desc &d) {
+    return d.in_mode == RAMNET_IN_CAT && d.C0 % WK == 0 && d.Cout > 0 && d.Cout % 16 == 0 && d.o1 && d.bias && !d.out_s2d && !d.frame &&
+           d.osy == 1 && d.osx == 1 && d.ooy == 0 && d.oox == 0 &&
+           (!d.o2 || (d.ldo2 % 4 == 0 && d.ldo2 >= 4 * d.Cout && ((uintptr_t)d.o2 & 15) == 0));
+}
+
 // Does this WINOGRAD-eligible launch run F(2x4,3x3)?  Dense 3x3 layers with plain / concatenated / masked inputs and the channel-quad
-// epilogues (no ConvLSTM cell, no space-to-depth view), 64-channel output blocks, on maps where (a) the 2 x 4 tiling wastes less than
+// epilogues or the ConvLSTM cell (no space-to-depth view there), 64-column output blocks, on maps where (a) the 2 x 4 tiling wastes less than
 // a quarter of what it saves and (b) the launch still fills the chip with 64-channel workgroups at ONE per CU.
 static int g_w6_min_wgs = 150;                  // ramnet_wino2x4_config(): launch-size threshold (64-channel workgroups of 256 pixels)
 
@@ -497,7 +574,11 @@ int wino6_eligible(const ramnet_conv_desc &d, int force) {
     if (d.in_mode == RAMNET_IN_S2D && (d.C0 < WK || (d.C0 & (d.C0 - 1)) != 0)) return 0;
     if (d.out_s2d && (d.out_s2d < 8 || (d.out_s2d & (d.out_s2d - 1)) != 0 || d.Cout != 4 * d.out_s2d || d.epi != RAMNET_EPI_LINEAR || d.bias || d.beta != 0.f ||
                       d.HoF != 2 * d.Ho || d.WoF != 2 * d.Wo || (d.in_mode != RAMNET_IN_PLAIN && d.in_mode != RAMNET_IN_RELUMASK))) return 0;
-    if (d.epi == RAMNET_EPI_LSTM || d.Cout % 64 != 0 || !wino6_vec4(d)) return 0;
+    // ConvLSTM cell (ABI 27): Cout is the hidden size C, the launch has 4C gate columns — 16 hidden channels x (i, f, o, g) per 64-column block
+    const bool lstm = d.epi == RAMNET_EPI_LSTM;
+    if (lstm && !wino6_lstm_ok(d)) return 0;
+    const int ncol = lstm ? 4 * d.Cout : d.Cout;
+    if (ncol % 64 != 0 || !wino6_vec4(d)) return 0;
     if (d.epi == RAMNET_EPI_GRU_BWD && d.Cout % 128 != 0) return 0;          // a 64-channel block lies in one half of [dx | d(h.r)]
     int txg;
     const long a6 = wino6_tile(d.Ho, d.Wo, txg);
@@ -505,12 +586,16 @@ int wino6_eligible(const ramnet_conv_desc &d, int force) {
     const long a4 = a4t < a4w ? a4t : a4w;
     if (force) return 1;                                            // (tests: every structurally eligible launch)
     if (3 * a6 > 4 * a4 * 0.9) return 0;                            // less than 10 % fewer MFMAs: not worth the larger tiles
-    const long wgs = a6 / 256 * d.B * cdiv(d.Cout, 64);
+    const long wgs = a6 / 256 * d.B * cdiv(ncol, 64);             // (ConvLSTM: the same rule on its 4C gate columns)
     return wgs >= g_w6_min_wgs ? 1 : 0;
 }
 
 int launch_wino6(const ramnet_conv_desc &d, hipStream_t st) {
-    RAMNET_CHECK_ARG(d.ntaps == 9 && d.stride == 1 && !d.frame && d.epi != RAMNET_EPI_LSTM);
+    RAMNET_CHECK_ARG(d.ntaps == 9 && d.stride == 1 && !d.frame);
+    const bool lstm = d.epi == RAMNET_EPI_LSTM;
+    if (lstm) RAMNET_CHECK_ARG(wino6_lstm_ok(d) && (!d.active || d.e0));
+    const int ncol = lstm ? 4 * d.Cout : d.Cout;                    // (ConvLSTM: Cout = hidden size, the weights hold 4C gate columns)
+    RAMNET_CHECK_ARG(ncol % 64 == 0);
     RAMNET_CHECK_ARG(d.in_mode == RAMNET_IN_PLAIN || d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL || d.in_mode == RAMNET_IN_RELUMASK ||
                      d.in_mode == RAMNET_IN_S2D);
     auto log2_exact = [](int v) { int sh = 0; while ((1 << sh) < v) ++sh; return (1 << sh) == v ? sh : -1; };
@@ -539,7 +624,7 @@ int launch_wino6(const ramnet_conv_desc &d, hipStream_t st) {
     q.src.C0 = d.C0, q.src.Cin = d.C0 + (cat ? d.C1 : 0);
     q.src.mode = d.in_mode, q.src.Hin = d.Hin, q.src.Win = d.Win;
     if (d.in_mode == RAMNET_IN_S2D) q.src.Cin = 4 * d.C0, q.src.ld1 = log2_exact(d.C0);
-    q.nchunks = cdiv(q.src.Cin, WK), q.nblk = cdiv(d.Cout, W6_BN);
+    q.nchunks = cdiv(q.src.Cin, WK), q.nblk = cdiv(ncol, W6_BN);
     int txg;
     wino6_tile(d.Ho, d.Wo, txg);
     q.tiles_x = cdiv(d.Wo, 4 * txg), q.tiles_y = cdiv(d.Ho, 2 * (32 / txg));
@@ -562,9 +647,11 @@ int launch_wino6(const ramnet_conv_desc &d, hipStream_t st) {
         int lo = d.ldo > d.ldo1 ? d.ldo : d.ldo1;                              // ... of the epilogue's tensors too
         lo = lo > d.lde0 ? lo : d.lde0;
         lo = lo > d.lde1 ? lo : d.lde1;
+        if (lstm && d.o2) lo = lo > d.ldo2 ? lo : d.ldo2;
         RAMNET_CHECK_ARG((unsigned long long)d.HoF * d.WoF * lo * 4ull < (unsigned long long)WOOB);
     }
-    note_kernel(d.active ? "conv_wino_r6_kernel<%d,%d,masked>" : "conv_wino_r6_kernel<%d,%d>", txg, d.in_mode);
+    if (lstm) note_kernel(d.active ? "conv_wino_r6_kernel<%d,%d,masked,lstm>" : "conv_wino_r6_kernel<%d,%d,lstm>", txg, d.in_mode);
+    else note_kernel(d.active ? "conv_wino_r6_kernel<%d,%d,masked>" : "conv_wino_r6_kernel<%d,%d>", txg, d.in_mode);
     size_t probe_pad = 0;                       // (probe builds: RAMNET_PROBE_LDS_KB pads the allocation — 90: ONE workgroup per CU)
 #ifdef RAMNET_PROBE
     if (const char *e = getenv("RAMNET_PROBE_LDS_KB")) probe_pad = (size_t)atoi(e) * 1024;
@@ -581,11 +668,18 @@ int launch_wino6(const ramnet_conv_desc &d, hipStream_t st) {
         RAMNET_FULL_LDS((conv_wino_r6_kernel<TXv, MDv, true>));                                                     \
         hipLaunchKernelGGL((conv_wino_r6_kernel<TXv, MDv, true>), grid, dim3(256), (ex > pf ? ex : pf) + probe_pad, st, d, q); \
     } break;
+#define RAMNET_GO6L(TXv, MSKv)                                                                                      \
+    case 200000 + (MSKv) * 100000 + (TXv) * 100 + RAMNET_IN_CAT: {                                                  \
+        const size_t pf = (size_t)(2 * R6Geom<TXv>::PFLOATS + 256 * 4) * sizeof(float);                             \
+        RAMNET_FULL_LDS((conv_wino_r6_kernel<TXv, RAMNET_IN_CAT, MSKv, true>));                                     \
+        hipLaunchKernelGGL((conv_wino_r6_kernel<TXv, RAMNET_IN_CAT, MSKv, true>), grid, dim3(256), (ex > pf ? ex : pf) + probe_pad, st, d, q); \
+    } break;
 #define RAMNET_GO6_TX(TXv)                                                                                          \
+    RAMNET_GO6L(TXv, false) RAMNET_GO6L(TXv, true)                                                                  \
     RAMNET_GO6M(TXv, RAMNET_IN_CAT) RAMNET_GO6M(TXv, RAMNET_IN_CAT_MUL)                                             \
     RAMNET_GO6(TXv, RAMNET_IN_PLAIN) RAMNET_GO6(TXv, RAMNET_IN_CAT) RAMNET_GO6(TXv, RAMNET_IN_CAT_MUL) RAMNET_GO6(TXv, RAMNET_IN_RELUMASK) \
     RAMNET_GO6(TXv, RAMNET_IN_S2D)
-    switch (txg * 100 + d.in_mode + (d.active ? 100000 : 0)) {
+    switch (txg * 100 + d.in_mode + (d.active ? 100000 : 0) + (lstm ? 200000 : 0)) {
         RAMNET_GO6_TX(4)
         RAMNET_GO6_TX(2)
         RAMNET_GO6_TX(8)
@@ -593,6 +687,7 @@ int launch_wino6(const ramnet_conv_desc &d, hipStream_t st) {
         RAMNET_CHECK_ARG(!"conv_wino_r6: unsupported (tile, input mode) combination");
     }
 #undef RAMNET_GO6_TX
+#undef RAMNET_GO6L
 #undef RAMNET_GO6M
 #undef RAMNET_GO6
     RAMNET_LAUNCH_CHECK();
@@ -616,21 +711,31 @@ extern "C" int ramnet_wino2x4_config(int min_wgs) {
 
 extern "C" int ramnet_conv_wino_variant(const ramnet_conv_desc *d, int force) { return d ? wino6_eligible(*d, force) : 0; }
 
-extern "C" size_t ramnet_packed_weight_elems_wino2x4(int Cout, int Cin, int transposed) {
+extern "C" size_t ramnet_packed_weight_elems_wino2x4_gates(int Cout, int Cin, int transposed, int gates) {
     int R, N, nchunks, nblk;
+    (void)gates;                                 // (the gate-interleaved pack permutes columns inside whole 64-column blocks: the generic size)
     wino6_geometry(Cout, Cin, transposed, R, N, nchunks, nblk);
     return (size_t)nchunks * nblk * W6_U_FLOATS;
 }
 
-extern "C" int ramnet_pack_weight_wino2x4(const float *w, float *wp, int Cout, int Cin, int transposed, void *stream) {
+extern "C" size_t ramnet_packed_weight_elems_wino2x4(int Cout, int Cin, int transposed) {
+    return ramnet_packed_weight_elems_wino2x4_gates(Cout, Cin, transposed, 1);
+}
+
+extern "C" int ramnet_pack_weight_wino2x4_gates(const float *w, float *wp, int Cout, int Cin, int transposed, int gates, void *stream) {
     RAMNET_CHECK_ARG(w && wp && Cout > 0 && Cin > 0);
+    RAMNET_CHECK_ARG(gates == 1 || (gates == 4 && !transposed && Cout % 64 == 0));      // ConvLSTM: Cout = 4C, C % 16 == 0, forward only
     int R, N, nchunks, nblk;
     wino6_geometry(Cout, Cin, transposed, R, N, nchunks, nblk);
     const size_t total = (size_t)nchunks * nblk * W6_U_FLOATS;
     size_t blocks = (total + 255) / 256;
     if (blocks > 65535) blocks = 65535;
     hipLaunchKernelGGL(pack_weight_wino_r6_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin,
-                       transposed, R, N, nchunks, nblk, total);
+                       transposed, gates, R, N, nchunks, nblk, total);
     RAMNET_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int ramnet_pack_weight_wino2x4(const float *w, float *wp, int Cout, int Cin, int transposed, void *stream) {
+    return ramnet_pack_weight_wino2x4_gates(w, wp, Cout, Cin, transposed, 1, stream);
 }

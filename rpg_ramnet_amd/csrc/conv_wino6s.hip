@@ -611,7 +611,7 @@ int wino6_eligible(const ramnet_conv_desc &d, int force);          // conv_wino6
 // The split-operand form runs what the exact-fp32 F(2x4,3x3) kernel runs, with 16-channel chunks: a chunk must lie in one tensor of a
 // concatenation and in one parity group of a space-to-depth view.
 int wino6s_eligible(const ramnet_conv_desc &d, int force) {
-    if (!wino6_eligible(d, force)) return 0;
+    if (d.epi == RAMNET_EPI_LSTM || !wino6_eligible(d, force)) return 0;      // (the ConvLSTM cell: exact-fp32 F(2x4) kernel only)
     if ((d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL) && d.C0 % WKS != 0) return 0;
     if (d.in_mode == RAMNET_IN_S2D && d.C0 < WKS) return 0;
     return 1;

@@ -49,7 +49,8 @@ def set_wgrad_slabs(on):
 def set_winograd_2x4(mode, min_wgs=None):
     """F(2x4,3x3) variant of the Winograd forward / backward-data launches (csrc/conv_wino6.hip): "auto" = where the library's size
     heuristics pick it (large maps: the two fine scales at the training batch), "off" = F(2x2,3x3) everywhere, "force" = every
-    structurally eligible launch (tests).  min_wgs: launch-size threshold of "auto" (library default when None)."""
+    structurally eligible launch (tests).  The ConvLSTM cell launch (hidden size a multiple of 16; gate-interleaved pack "2x4g") and its
+    backward-data launch are governed like every other launch.  min_wgs: launch-size threshold of "auto" (library default when None)."""
     global _WINO_2X4
     assert mode in ("auto", "off", "force")
     _WINO_2X4 = mode
@@ -386,7 +387,7 @@ def _conv_desc_build(x0, taps, w, out, Cout, meta, *, stride=1, x1=None, xm=None
                      C0=None, C1=0, Hin=None, Win=None, bias=None, epi=H.EPI_LINEAR, beta=0.0, e0=None, e1=None,
                      o1=None, o2=None, Ho=None, Wo=None, os=(1, 1, 0, 0), out_off=0, frame=0, out_s2d=0, wino24=False, ws_owner=None):
     """The descriptor from scratch; meta <- [which pack of the layer d.w points at (None: `w` is a packed tensor itself; "head"; False /
-    True / "2x4": ConvParam.pack(transposed, kind); "f23" / "f23d": ws_owner.pack_fold_wino2x3[_dgrad]()), floats of the split-reduction
+    True / "2x4" / "2x4g" / "2x4s": ConvParam.pack(transposed, kind); "f23" / "f23d": ws_owner.pack_fold_wino2x3[_dgrad]()), floats of the split-reduction
     workspace (0: none)]."""
     B = x0.shape[0]
     kind, nsplit = None, 0
@@ -406,7 +407,10 @@ def _conv_desc_build(x0, taps, w, out, Cout, meta, *, stride=1, x1=None, xm=None
         d.algo = H.ALGO_WINOGRAD if wino else H.ALGO_DIRECT
         # the 3x3 view of a 5x5 stride-2 layer read / written in place: 11 of its 36 slices are zero by construction (s2d_weights)
         d.s2d_5x5 = int(wino and isinstance(w.cp, S2DConvParam) and _S2D_SPARSE and (in_mode == H.IN_S2D or out_s2d > 0))
-        if wino and w.cp.gates == 1 and os == (1, 1, 0, 0) and (_S2D_2X4 or not isinstance(w.cp, S2DConvParam)):
+        # (a ConvLSTM layer — gates == 4 — offers its cell launch, which reads the gate-interleaved pack "2x4g", and its backward-data
+        # launch, a plain LINEAR launch whose transposed pack ignores the gates)
+        if (wino and (w.cp.gates == 1 or w.transposed or (epi == H.EPI_LSTM and w.cp.gates == 4)) and os == (1, 1, 0, 0)
+                and (_S2D_2X4 or not isinstance(w.cp, S2DConvParam))):
             ref = w                      # candidate for F(2x4,3x3): the library decides once the descriptor is complete (below)
         kind = bool(wino)
         w = w.cp.pack(w.transposed, wino)
@@ -428,7 +432,7 @@ def _conv_desc_build(x0, taps, w, out, Cout, meta, *, stride=1, x1=None, xm=None
     if ref is not None and _WINO_2X4 != "off" and H.lib().ramnet_conv_wino_variant(C.byref(d), int(_WINO_2X4 == "force")):
         # F(2x4,3x3) on the fine scales (csrc/conv_wino6.hip): its own Winograd-domain pack of the same parameters
         d.algo, d.s2d_5x5 = H.ALGO_WINOGRAD_2X4, 0      # (dense: the F(2x4) kernel skips no zero slices)
-        kind = "2x4"
+        kind = "2x4g" if epi == H.EPI_LSTM else "2x4"
         if _SPLIT_OPERANDS and H.lib().ramnet_conv_wino_split_ok(C.byref(d), int(_WINO_2X4 == "force")):
             d.algo, kind = H.ALGO_WINOGRAD_2X4_SPLIT, "2x4s"       # the same launch on the bf16 matrix pipe, split operands (csrc/conv_wino6s.hip)
         d.w = _p(ref.cp.pack(ref.transposed, kind))
@@ -908,6 +912,10 @@ class ConvParam:
             out = torch.empty(L.ramnet_packed_weight_elems_wino2x4(self.Cout, self.Cin, transposed), device=w.device, dtype=torch.float32)
             H.check(L.ramnet_pack_weight_wino2x4(_p(w), _p(out), self.Cout, self.Cin, transposed, _st()), "ramnet_pack_weight_wino2x4")
             return out
+        if wino == "2x4g":      # ConvLSTM cell launch: 8 hidden channels x (i, f, o, g) per 32-column workgroup (forward only)
+            out = torch.empty(L.ramnet_packed_weight_elems_wino2x4_gates(self.Cout, self.Cin, transposed, g), device=w.device, dtype=torch.float32)
+            H.check(L.ramnet_pack_weight_wino2x4_gates(_p(w), _p(out), self.Cout, self.Cin, transposed, g, _st()), "ramnet_pack_weight_wino2x4_gates")
+            return out
         if wino == "2x4s":      # three bf16 planes of the same Winograd-domain weights (csrc/conv_wino6s.hip); the size is in 4-byte units
             out = torch.empty(L.ramnet_packed_weight_elems_wino2x4_split(self.Cout, self.Cin, transposed), device=w.device, dtype=torch.float32)
             H.check(L.ramnet_pack_weight_wino2x4_split(_p(w), _p(out), self.Cout, self.Cin, transposed, _st()), "ramnet_pack_weight_wino2x4_split")
@@ -925,7 +933,7 @@ class ConvParam:
     def pack(self, transposed, wino=False):
         """Packed weights for the forward (transposed=0) / backward-data (1) launch, re-packed when a parameter changes."""
         v = self._versions(self.weights)
-        wino = wino if wino in ("head", "2x4", "2x4s") else bool(wino)
+        wino = wino if wino in ("head", "2x4", "2x4g", "2x4s") else bool(wino)
         key = (transposed, wino)
         hit = self._packs.get(key)
         if hit is None or hit[0] != v:

@@ -526,6 +526,26 @@ int ramnet_normalize_nonzero(float *grid, size_t n, double *scratch, void *strea
 int ramnet_voxelize_batch(const double *events, const long long *offsets, int n_grids, size_t max_events, int bins, int W, int H,
                           float *grids, void *stream);
 int ramnet_normalize_nonzero_batch(float *grids, int n_grids, size_t n, double *scratch, void *stream);
+/* The statistics alone: stats[3 g ..] = (sum, sum of squares, nonzero count) of grid g (zeroed here); the grids are not modified.  */
+int ramnet_nonzero_stats_batch(const float *grids, int n_grids, size_t n, double *stats, void *stream);
+
+/* ---- training augmentation: utils/data_augmentation.py:52-216 (RandomRotationFlip, then RandomCrop / CenterCrop) -----------------
+ * G tensors [C][H][W] -> G windows of th x tw pixels in ONE launch.  src / dst: DEVICE tables of G device pointers (the tensors of a
+ * collated sequence are separate allocations; dst 16-byte aligned for the vector path).  Tensor g uses parameter set pidx[g] (device
+ * int32 [G]; NULL: g) of n_params sets: theta [n_params][6] (the 2x3 matrix the reference hands to affine_grid, row-major) and
+ * win [n_params][4] int32 = top, left, exact, flips (bit 0: columns mirrored, bit 1: rows mirrored).  Output pixel (y, x) is pixel
+ * (y + top, x + left) of the flipped / rotated image.
+ *   exact != 0 (theta = diag(+-1, +-1), decided by the HOST): source pixels are copied bit for bit, NaN included;
+ *   exact == 0: affine_grid + grid_sample (bilinear, zeros, align_corners=False) in fp32 with the normalised coordinates bx [W] and
+ *               by [H] (device; torch's linspace(-1, 1, n) * (n - 1) / n); taps outside the image are skipped.
+ * stats (optional, [G][3] doubles of the entry above): a source value v is read as v != 0 ? (v - mean) / std : 0 — the nonzero
+ * normalisation of the FULL grid, fused in front of the transform; degenerate statistics leave values unchanged.
+ * nhwc = 0: dst [C][th][tw]; nhwc = 1: [th][tw][Cpad], channels zero-padded (the model's input layout; Cpad % 4 == 0).
+ * win_host (optional): a HOST copy of win; when given, every window is checked against the image before anything is launched.  The
+ * kernel itself clamps top / left into the image.  G = 0 is a no-op.                                                              */
+int ramnet_augment_batch(const float *const *src, float *const *dst, const int *pidx, const float *theta, const int *win,
+                         const int *win_host, const double *stats, const float *bx, const float *by, int G, int n_params, int C,
+                         int H, int W, int th, int tw, int Cpad, int nhwc, void *stream);
 
 #ifdef __cplusplus
 }

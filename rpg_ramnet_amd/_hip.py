@@ -173,6 +173,8 @@ _SIGS = {
     "ramnet_normalize_nonzero": (C.c_int, [_fp, C.c_size_t, _fp, _fp]),
     "ramnet_voxelize_batch": (C.c_int, [_fp, _fp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "ramnet_normalize_nonzero_batch": (C.c_int, [_fp, C.c_int, C.c_size_t, _fp, _fp]),
+    "ramnet_nonzero_stats_batch": (C.c_int, [_fp, C.c_int, C.c_size_t, _fp, _fp]),
+    "ramnet_augment_batch": (C.c_int, [_fp] * 9 + [C.c_int] * 9 + [_fp]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -1109,6 +1109,20 @@ extern "C" int ramnet_normalize_nonzero_batch(float *grids, int n_grids, size_t 
     return 0;
 }
 
+// The statistics half of ramnet_normalize_nonzero_batch alone: the grids stay as they are, a consumer (ramnet_augment_batch) normalises
+// the values it reads.
+extern "C" int ramnet_nonzero_stats_batch(const float *grids, int n_grids, size_t n, double *stats, void *stream) {
+    RAMNET_CHECK_ARG(grids && stats && n > 0 && n % 4 == 0 && n_grids > 0 && n_grids <= 65535);
+    hipStream_t st = (hipStream_t)stream;
+    RAMNET_HIP(hipMemsetAsync(stats, 0, (size_t)3 * n_grids * sizeof(double), st));
+    int gx = (int)((n / 4 + 255) / 256);
+    const int cap = (2048 * 4 + n_grids - 1) / n_grids;
+    if (gx > cap) gx = cap;
+    hipLaunchKernelGGL(nonzero_stats_batch_kernel, dim3(gx, n_grids), dim3(256), 0, st, grids, n, stats);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int ramnet_voxel_indices(const double *events, size_t n_events, int bins, int W, int H, long long *idx_left, long long *idx_right, void *stream) {
     RAMNET_CHECK_ARG(events && idx_left && idx_right && n_events > 0 && bins > 0 && W > 0 && H > 0);
     hipLaunchKernelGGL(voxel_indices_kernel, dim3(grid_for(n_events)), dim3(256), 0, (hipStream_t)stream, events, n_events, bins, W, H, idx_left, idx_right);

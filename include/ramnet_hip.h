@@ -547,6 +547,27 @@ int ramnet_augment_batch(const float *const *src, float *const *dst, const int *
                          const int *win_host, const double *stats, const float *bx, const float *by, int G, int n_params, int C,
                          int H, int W, int th, int tw, int Cpad, int nhwc, void *stream);
 
+/* ---- training metrics of G (prediction, target) pairs: model/metric.py:8-54, lstm_trainer.py:100-106 ----------------------------
+ * pred / target: DEVICE tables of G device pointers; pair g is a contiguous [N][npix] fp32 prediction and target (N x 1 x H x W;
+ * NaN in the target = no ground truth; 4-byte alignment is enough).  Both are only read.  out[g][10] doubles, d = |t - p| in fp32:
+ *   0 n = count of non-NaN d                       1 count of non-NaN t
+ *   2 mse: mean over the N samples of mean((p - t)^2 | t valid)        3 abs_rel_diff: mean d / (t + 1e-6)
+ *   4 squ_rel_diff: mean d^2 / (t^2 + 1e-6)        5 rms_linear: sqrt(mean d^2)
+ *   6 scale_invariant_error: mean d^2 - (mean d)^2  7 mean_error: mean d
+ *   8 median_error: np.median of the non-NaN d as float32 (even n: (a + b) * 0.5f of the two middle elements), exact, by a three-pass
+ *     radix selection on the bit pattern of d            9 reserved (0)
+ * Element arithmetic in fp32 as numpy does it (IEEE division, no contraction), accumulation in double, joined in a fixed order: the
+ * same input gives the same bits on every call.  A pair without a valid pixel: columns 2-8 NaN; a sample without a valid target:
+ * mse NaN; a non-finite prediction shows as column 0 != column 1.  Three launches whatever G is; no host synchronisation.
+ * workspace: ramnet_batch_metrics_workspace(G, N, npix) bytes (0 for arguments the call would reject), 256-byte aligned.  Its first
+ * RAMNET_BATCH_METRICS_TICKET_BYTES must be ZERO WHEN IT IS ALLOCATED; every call leaves them zero again and writes whatever else
+ * it reads, so calls of any (G, N, npix) that fit the allocation follow each other with no memset in between — one call at a time
+ * per workspace (order them on one stream).  G = 0 is a no-op.                                                                      */
+#define RAMNET_BATCH_METRICS_TICKET_BYTES 262144
+size_t ramnet_batch_metrics_workspace(int G, int N, size_t npix);
+int ramnet_batch_metrics(const float *const *pred, const float *const *target, int G, int N, size_t npix, void *workspace,
+                         double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

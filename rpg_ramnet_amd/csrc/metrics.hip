@@ -1,0 +1,343 @@
+// Training metrics (model/metric.py:8-54) of G (prediction, target) pairs without the host: the six means, the per-sample mse and the
+// EXACT median of d = |t - p| of every pair, three launches for all pairs together.
+//
+// grid = (Ws, N, G): workgroup (w, s, g) reads a contiguous quarter-or-so of sample s of pair g, 16 bytes per lane and map (the loads are
+// 4-byte aligned global loads: a sample need not start on a 16-byte boundary), so a pass reads 8 B per element and writes nothing but its
+// partials.  P = N * Ws workgroups work on one pair.
+//
+// pass 1  sums + histogram of bits 30..20 of d   (d >= +0: the uint32 pattern of a non-NaN d orders like its value, bit 31 is 0)
+// pass 2  histogram of bits 19..10 of the d whose bits 30..20 equal the bin that holds the wanted rank
+// pass 3  histogram of bits  9..0  of the d whose bits 30..10 equal the 21-bit prefix     -> the element of that rank, bit for bit
+// An even count needs the elements of ranks n/2 - 1 and n/2: both are carried through the passes, with a histogram each from the pass after
+// the one where they part (np.median: (a + b) * 0.5 rounded in fp32).
+//
+// Joins.  Every workgroup counts in an LDS histogram (ds_add_u32) and STORES it whole to its own slab, stores its eight double partial sums
+// to its own row, releases both with one device-scope fence and takes a ticket of its pair; the last arrival of a pair adds the P rows
+// and the P slabs in index order (integer sums and a fixed order of the double sums: the same bits on every launch), picks the bin
+// that holds each rank and leaves the (prefix, rank inside it) of the pair in the workspace for the next pass.  No value crosses to
+// the host between the passes.
+//
+// Workspace: [64 Ki tickets][G states][G x P partial rows][G x P x 2 slabs].  Slabs, rows and states are written in full before they are
+// read in every call; the tickets are set back to 0 by the last arrival.  So ONE zero-fill of the first RAMNET_BATCH_METRICS_TICKET_BYTES
+// at allocation is all a caller owes, and calls of any shape that fit the allocation can follow each other without a memset
+// (one call at a time per workspace: calls on the same workspace are ordered on one stream).
+//
+// Element arithmetic is numpy's on float32 arrays: fabsf(t - p), d / (t + 1e-6f), d * d / (t * t + 1e-6f) with IEEE division and no
+// contraction (this file is built with -ffp-contract=off; the divisions are __fdiv_rn), accumulated in double.
+#include "common.hpp"
+
+namespace ramnet {
+
+typedef float bm_f4u __attribute__((ext_vector_type(4), aligned(4)));
+typedef const float __attribute__((address_space(1))) *bm_src_t;
+
+constexpr int BM_T = 256;                  // threads of a workgroup
+constexpr int BM_BINS = 2048;              // bins of pass 1 (11 bits); passes 2 and 3 use the first 1024 of a slab
+constexpr int BM_ROW = 8;                  // doubles of a partial row: n, n_target, sum d/(t+eps), sum d^2/(t^2+eps), sum d^2, sum d, sum (p-t)^2 | t valid, (unused)
+constexpr int BM_STATE = 8;                // uint32 of a pair's state: prefix0, rank0, prefix1, rank1, n
+constexpr int BM_MAX_PER_PAIR = 32;        // workgroups per pair when N allows it (N > 32: one per sample)
+constexpr int BM_STAGE = 64;                // partial rows the last arrival stages through LDS at a time
+constexpr unsigned BM_SPAN = 8192;         // elements a workgroup should at least have
+
+struct bm_plan_t {
+    int Ws, P;
+    size_t off_state, off_part, off_slab, total;
+};
+
+static bm_plan_t bm_plan(int G, int N, size_t npix) {
+    bm_plan_t p;
+    size_t ws = (npix + BM_SPAN - 1) / BM_SPAN;
+    const size_t cap = N >= BM_MAX_PER_PAIR ? 1 : BM_MAX_PER_PAIR / N;
+    if (ws > cap) ws = cap;
+    if (ws < 1) ws = 1;
+    p.Ws = (int)ws;
+    p.P = N * p.Ws;
+    p.off_state = RAMNET_BATCH_METRICS_TICKET_BYTES;
+    p.off_part = p.off_state + (((size_t)G * BM_STATE * sizeof(unsigned) + 255) & ~(size_t)255);
+    p.off_slab = p.off_part + (((size_t)G * p.P * BM_ROW * sizeof(double) + 255) & ~(size_t)255);
+    p.total = p.off_slab + (size_t)G * p.P * 2 * BM_BINS * sizeof(unsigned);
+    return p;
+}
+
+__device__ __forceinline__ double bm_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    return v;
+}
+
+__device__ __forceinline__ unsigned bm_ld(const unsigned *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double bm_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// The part of sample s that workgroup w of Ws reads: [lo, hi) in elements of the sample, lo a multiple of 4.
+__device__ __forceinline__ void bm_range(unsigned npix, int Ws, int w, unsigned &lo, unsigned &hi) {
+    const unsigned chunk = ((npix + Ws - 1) / Ws + 3u) & ~3u;
+    const unsigned long long a = (unsigned long long)w * chunk;
+    lo = a < npix ? (unsigned)a : npix;
+    hi = npix - lo < chunk ? npix : lo + chunk;
+}
+
+// f(p, t) over the elements [lo, hi) of one sample: 16 bytes per lane and map, then the tail of fewer than 4 elements.
+template <class F>
+__device__ __forceinline__ void bm_sweep(bm_src_t p, bm_src_t t, unsigned lo, unsigned hi, F f) {
+    typedef const bm_f4u __attribute__((address_space(1))) *v4_t;
+    const unsigned nv = (hi - lo) >> 2;
+    unsigned i = threadIdx.x;
+    for (; i + 3 * BM_T < nv; i += 4 * BM_T) {                   // eight loads in flight per lane
+        bm_f4u a[4], b[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] = *(v4_t)(p + lo + 4 * (size_t)(i + j * BM_T)), b[j] = *(v4_t)(t + lo + 4 * (size_t)(i + j * BM_T));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) f(a[j].x, b[j].x), f(a[j].y, b[j].y), f(a[j].z, b[j].z), f(a[j].w, b[j].w);
+    }
+    for (; i < nv; i += BM_T) {
+        const bm_f4u a = *(v4_t)(p + lo + 4 * (size_t)i), b = *(v4_t)(t + lo + 4 * (size_t)i);
+        f(a.x, b.x), f(a.y, b.y), f(a.z, b.z), f(a.w, b.w);
+    }
+    for (unsigned k = lo + 4 * nv + threadIdx.x; k < hi; k += BM_T) f(p[k], t[k]);
+}
+
+// Adds the P slabs `h` of pair g into the LDS histogram (index order), all threads.  The loads of four slabs are in flight together: one
+// after the other, the P x NBINS / BM_T coherent loads of a thread were most of a launch (profiles/epoch_metrics_notes.md).
+template <int NBINS>
+__device__ __forceinline__ void bm_join_slabs(const unsigned *slab, size_t g, int P, int h, unsigned *lds) {
+    constexpr int PER = NBINS / BM_T;
+    unsigned v[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) v[j] = 0;
+    for (int k0 = 0; k0 < P; k0 += 4) {
+        unsigned x[4][PER];
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int j = 0; j < PER; ++j)
+                x[kk][j] = k0 + kk < P ? bm_ld(slab + (((size_t)g * P + k0 + kk) * 2 + h) * BM_BINS + threadIdx.x + j * BM_T) : 0u;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int j = 0; j < PER; ++j) v[j] += x[kk][j];
+    }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) lds[threadIdx.x + j * BM_T] = v[j];
+    __syncthreads();
+}
+
+// The bin of the joined LDS histogram that holds the element of rank `rank` (0-based) and the rank inside that bin -> res[0], res[1]
+// (LDS; {0, 0} when the histogram holds no such rank).  scan: a word of LDS per wave.  All threads; ends with a barrier.
+__device__ __forceinline__ void bm_select(const unsigned *lds, int nbins, unsigned rank, unsigned *scan, unsigned *res) {
+    const int per = nbins / BM_T;
+    unsigned tot = 0;
+    for (int j = 0; j < per; ++j) tot += lds[threadIdx.x * per + j];
+    // exclusive scan of the 256 totals: inside each wave by shuffles, the four wave totals through LDS
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned inc = tot;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned u = __shfl_up(inc, o);
+        if (lane >= o) inc += u;
+    }
+    if (lane == 63) scan[wave] = inc;
+    if (threadIdx.x == 0) res[0] = 0, res[1] = 0;
+    __syncthreads();
+    unsigned before = inc - tot;
+    for (int w = 0; w < wave; ++w) before += scan[w];
+    if (rank >= before && rank - before < tot) {                  // exactly one thread
+        unsigned r = rank - before;
+        for (int j = 0; j < per; ++j) {
+            const unsigned c = lds[threadIdx.x * per + j];
+            if (r < c) {
+                res[0] = threadIdx.x * per + j, res[1] = r;
+                break;
+            }
+            r -= c;
+        }
+    }
+    __syncthreads();
+}
+
+// Stores the workgroup's histogram(s) to its slab(s), takes the pair's ticket; true in every thread of the last arrival of the pair.
+__device__ __forceinline__ bool bm_arrive(unsigned (*hist)[BM_BINS], int nh, int nbins, unsigned *slab, size_t g, int P, int wg, unsigned *tickets,
+                                          int *flag) {
+    for (int h = 0; h < nh; ++h)
+        for (int b = threadIdx.x; b < nbins; b += BM_T) slab[(((size_t)g * P + wg) * 2 + h) * BM_BINS + b] = hist[h][b];
+    // Release ONCE per workgroup (a __threadfence() in each of the 6144 waves of a G = 48 launch writes the L2 back 6144 times): every wave
+    // waits until its own stores have reached the L2 (the barrier alone does not), then thread 0 fences at device scope and takes the ticket.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();
+        *flag = atomicAdd(tickets + g, 1u) == (unsigned)P - 1u;
+    }
+    __syncthreads();
+    const bool last = *flag != 0;
+    if (last) __threadfence();
+    return last;
+}
+
+__global__ void __launch_bounds__(BM_T) bm_sums_kernel(const float *const *__restrict__ preds, const float *const *__restrict__ targets, int N,
+                                                       unsigned npix, int Ws, unsigned *tickets, unsigned *state, double *part, unsigned *slab,
+                                                       double *__restrict__ out) {
+    __shared__ unsigned hist[2][BM_BINS];
+    __shared__ double red[BM_ROW][BM_T / 64], stage[BM_STAGE * BM_ROW];
+    __shared__ unsigned scan[BM_T / 64], res[2];
+    __shared__ int flag;
+    const int w = blockIdx.x, s = blockIdx.y, P = N * Ws, wg = s * Ws + w;
+    const size_t g = blockIdx.z;
+    for (int b = threadIdx.x; b < BM_BINS; b += BM_T) hist[0][b] = 0;
+    __syncthreads();
+    unsigned lo, hi;
+    bm_range(npix, Ws, w, lo, hi);
+    const bm_src_t p = (bm_src_t)preds[g] + (size_t)s * npix, t = (bm_src_t)targets[g] + (size_t)s * npix;
+    double acc[BM_ROW] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    unsigned n = 0, nt = 0;
+    bm_sweep(p, t, lo, hi, [&](float pv, float tv) {
+        const float d = fabsf(tv - pv);
+        if (tv == tv) {
+            const float e = pv - tv;
+            ++nt;
+            acc[6] += (double)(e * e);                            // NaN for a non-finite prediction, as sklearn's mean would be
+        }
+        if (d == d) {
+            const float d2 = d * d;
+            ++n;
+            acc[2] += (double)__fdiv_rn(d, tv + 1e-6f);
+            acc[3] += (double)__fdiv_rn(d2, tv * tv + 1e-6f);
+            acc[4] += (double)d2;
+            acc[5] += (double)d;
+            atomicAdd(&hist[0][__float_as_uint(d) >> 20], 1u);
+        }
+    });
+    acc[0] = (double)n, acc[1] = (double)nt;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < BM_ROW; ++k) {
+        const double v = bm_wave_sum(acc[k]);
+        if (lane == 0) red[k][wave] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < BM_ROW) {
+        double v = 0.0;
+        for (int i = 0; i < BM_T / 64; ++i) v += red[threadIdx.x][i];
+        part[((size_t)g * P + wg) * BM_ROW + threadIdx.x] = v;
+    }
+    if (!bm_arrive(hist, 1, BM_BINS, slab, g, P, wg, tickets, &flag)) return;
+
+    // last arrival of the pair: the rows come through LDS 64 at a time (all loads of a chunk in flight), one thread per column adds them in
+    // index order; column 6 becomes the per-sample mse (thread 6 closes a sample after its Ws rows)
+    const double *rows = part + (size_t)g * P * BM_ROW;
+    double v = 0.0, sq = 0.0, c = 0.0;
+    for (int r0 = 0; r0 < P; r0 += BM_STAGE) {
+        const int nr = P - r0 < BM_STAGE ? P - r0 : BM_STAGE;
+        for (int i = threadIdx.x; i < nr * BM_ROW; i += BM_T) stage[i] = bm_ld(rows + (size_t)r0 * BM_ROW + i);
+        __syncthreads();
+        if (threadIdx.x < 6) {
+            for (int r = 0; r < nr; ++r) v += stage[r * BM_ROW + threadIdx.x];
+        } else if (threadIdx.x == 6) {
+            for (int r = 0; r < nr; ++r) {
+                sq += stage[r * BM_ROW + 6], c += stage[r * BM_ROW + 1];
+                if ((r0 + r + 1) % Ws == 0) v += sq / c, sq = 0.0, c = 0.0;          // 0 / 0: a sample without a valid target makes the pair's mse NaN
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 6) red[threadIdx.x][0] = v;
+    else if (threadIdx.x == 6) red[6][0] = v / (double)N;
+    bm_join_slabs<BM_BINS>(slab, g, P, 0, hist[0]);               // (barrier: red is complete as well)
+    const double cnt = red[0][0];
+    const unsigned total = (unsigned)cnt;
+    if (threadIdx.x == 0) {
+        double *o = out + g * 10;
+        const double md = red[5][0] / cnt, md2 = red[4][0] / cnt;
+        o[0] = cnt, o[1] = red[1][0], o[2] = red[6][0];
+        o[3] = red[2][0] / cnt, o[4] = red[3][0] / cnt, o[5] = sqrt(md2), o[6] = md2 - md * md, o[7] = md;
+        o[9] = 0.0;
+    }
+    unsigned *st = state + g * BM_STATE;
+    const unsigned r0 = total ? (total - 1) / 2 : 0, r1 = total / 2;
+    bm_select(hist[0], BM_BINS, r0, scan, res);
+    if (threadIdx.x == 0) st[0] = res[0], st[1] = res[1], st[4] = total;
+    bm_select(hist[0], BM_BINS, r1, scan, res);
+    if (threadIdx.x == 0) {
+        st[2] = res[0], st[3] = res[1];
+        atomicExch(tickets + g, 0u);                              // ready for the next pass
+    }
+}
+
+// SHIFT = 10: bits 19..10 of the d whose bits 30..20 equal the pair's prefix; SHIFT = 0: bits 9..0 under the 21-bit prefix, and the median.
+template <int SHIFT>
+__global__ void __launch_bounds__(BM_T) bm_select_kernel(const float *const *__restrict__ preds, const float *const *__restrict__ targets, int N,
+                                                         unsigned npix, int Ws, unsigned *tickets, unsigned *state, unsigned *slab,
+                                                         double *__restrict__ out) {
+    constexpr int NB = 1024;
+    __shared__ unsigned hist[2][BM_BINS];
+    __shared__ unsigned scan[BM_T / 64], res[2];
+    __shared__ int flag;
+    const int w = blockIdx.x, s = blockIdx.y, P = N * Ws, wg = s * Ws + w;
+    const size_t g = blockIdx.z;
+    unsigned *st = state + g * BM_STATE;
+    const unsigned pre0 = st[0], rank0 = st[1], pre1 = st[2], rank1 = st[3], total = st[4];
+    const bool two = pre0 != pre1;
+    for (int b = threadIdx.x; b < NB; b += BM_T) hist[0][b] = 0, hist[1][b] = 0;
+    __syncthreads();
+    unsigned lo, hi;
+    bm_range(npix, Ws, w, lo, hi);
+    const bm_src_t p = (bm_src_t)preds[g] + (size_t)s * npix, t = (bm_src_t)targets[g] + (size_t)s * npix;
+    bm_sweep(p, t, lo, hi, [&](float pv, float tv) {
+        const float d = fabsf(tv - pv);
+        if (d == d) {
+            const unsigned key = __float_as_uint(d), top = key >> (SHIFT + 10), bin = (key >> SHIFT) & (NB - 1);
+            if (top == pre0) atomicAdd(&hist[0][bin], 1u);
+            else if (top == pre1) atomicAdd(&hist[1][bin], 1u);
+        }
+    });
+    __syncthreads();
+    if (!bm_arrive(hist, two ? 2 : 1, NB, slab, g, P, wg, tickets, &flag)) return;
+
+    bm_join_slabs<NB>(slab, g, P, 0, hist[0]);
+    bm_select(hist[0], NB, rank0, scan, res);
+    const unsigned a = (pre0 << 10) | res[0], ra = res[1];
+    __syncthreads();
+    if (two) bm_join_slabs<NB>(slab, g, P, 1, hist[0]);
+    bm_select(hist[0], NB, rank1, scan, res);
+    const unsigned b = (pre1 << 10) | res[0], rb = res[1];
+    if (threadIdx.x == 0) {
+        if (SHIFT) {
+            st[0] = a, st[1] = ra, st[2] = b, st[3] = rb;
+        } else {
+            const float fa = __uint_as_float(a), fb = __uint_as_float(b);
+            const float med = (total & 1u) ? fa : (fa + fb) * 0.5f;
+            out[g * 10 + 8] = total ? (double)med : (double)__uint_as_float(0x7fc00000u);
+        }
+        atomicExch(tickets + g, 0u);
+    }
+}
+
+}  // namespace ramnet
+
+using namespace ramnet;
+
+extern "C" size_t ramnet_batch_metrics_workspace(int G, int N, size_t npix) {
+    if (G <= 0 || N <= 0 || npix == 0 || G > 65535 || N > 65535 || (size_t)N * npix >= ((size_t)1 << 31)) return 0;
+    return bm_plan(G, N, npix).total;
+}
+
+extern "C" int ramnet_batch_metrics(const float *const *pred, const float *const *target, int G, int N, size_t npix, void *workspace, double *out,
+                                    void *stream) {
+    RAMNET_CHECK_ARG(G >= 0 && G <= 65535 && N > 0 && N <= 65535 && npix > 0);
+    RAMNET_CHECK_ARG((size_t)N * npix < ((size_t)1 << 31));
+    if (G == 0) return 0;
+    RAMNET_CHECK_ARG(pred && target && workspace && out);
+    RAMNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0);
+    const bm_plan_t pl = bm_plan(G, N, npix);
+    char *ws = static_cast<char *>(workspace);
+    unsigned *tickets = reinterpret_cast<unsigned *>(ws), *state = reinterpret_cast<unsigned *>(ws + pl.off_state);
+    double *part = reinterpret_cast<double *>(ws + pl.off_part);
+    unsigned *slab = reinterpret_cast<unsigned *>(ws + pl.off_slab);
+    const dim3 grid(pl.Ws, N, G);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(bm_sums_kernel, grid, dim3(BM_T), 0, st, pred, target, N, (unsigned)npix, pl.Ws, tickets, state, part, slab, out);
+    hipLaunchKernelGGL(bm_select_kernel<10>, grid, dim3(BM_T), 0, st, pred, target, N, (unsigned)npix, pl.Ws, tickets, state, slab, out);
+    hipLaunchKernelGGL(bm_select_kernel<0>, grid, dim3(BM_T), 0, st, pred, target, N, (unsigned)npix, pl.Ws, tickets, state, slab, out);
+    RAMNET_LAUNCH_CHECK();
+    note_kernel("bm_sums_kernel + bm_select_kernel<10> + bm_select_kernel<0>");
+    return 0;
+}

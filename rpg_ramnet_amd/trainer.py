@@ -40,7 +40,7 @@ def _nominal_loss(loss_type, value, target, loss_params):
 
 
 def sequence_loss(model, sequence, loss_composition, loss_weights, loss_params=None, grad_loss_weight=None, dp_exact=False,
-                  process_group=None, loss_type="scale_invariant_loss", mse_loss=None):
+                  process_group=None, loss_type="scale_invariant_loss", mse_loss=None, parts=False):
     """BPTT over the L packages of `sequence` (list of item dicts with 'depth_<key>' targets).
     grad_loss_weight: weight of the multi-scale gradient loss (config['grad_loss']['weight'], 0.25 in the released
     recipe; lstm_trainer.py:162-168, :197-199) or None for the SI loss alone.
@@ -54,25 +54,29 @@ def sequence_loss(model, sequence, loss_composition, loss_weights, loss_params=N
     or 'mse_loss' (:18-19); loss_params = config['loss']['config'].
     mse_loss: config['mse_loss'] (lstm_trainer.py:76-90) — {'weight': 1.0, 'downsampling_factor': 0.5} — adds
     weight * sum_terms w_key * mse(bilinear x factor of prediction and target) / L (lstm_trainer.py:169-185, :205-208), or None.
-    Returns (loss to call .backward() on, loss value the reference would report)."""
+    Returns (loss to call .backward() on, loss value the reference would report).
+    parts=True: a third value, the dict `loss_parts` describes plus 'predictions': [(package index, key, detached prediction)] of EVERY
+    key the model returned (what the reference's calculate_total_metrics loop sees, lstm_trainer.py:290-294)."""
     if loss_params is None:
         loss_params = {"weight": 1.0, "n_lambda": 1.0} if loss_type == "scale_invariant_loss" else {}
     if dp_exact:
         assert loss_type == "scale_invariant_loss" and mse_loss is None, "dp_exact: the scale-invariant loss only"
         if any('num_events' in it for it in sequence):
             raise NotImplementedError("dp_exact: batches of irregular packages (num_events) are not supported")
+        if parts:
+            raise NotImplementedError("dp_exact: parts=True is not supported")
         return _sequence_loss_dp_exact(model, sequence, loss_composition, loss_weights, loss_params, grad_loss_weight, process_group)
     gterms, mterms = [], []
     L = len(sequence)
     assert L > 0
     K = model.every_x_rgb_frame
     prev_super, prev_lstm = None, empty_states_lstm(K)
-    terms, keys_seen = [], []
+    terms, keys_seen, seen = [], [], []
     # the scale-invariant loss of the supervised predictions inside the prediction layer's own launches (ops.PredSigmoidSI): the model is
     # told which keys and parameters for the duration of its forward call and hangs the loss term on the prediction it returns
     si_par = (float(loss_params.get("weight", 1.0)), float(loss_params.get("n_lambda", 1.0))) if loss_type == "scale_invariant_loss" else None
     ask = si_par is not None and ops.si_fusion() and isinstance(loss_composition, (list, tuple)) and hasattr(model, "_si_request")
-    for item in sequence:
+    for l, item in enumerate(sequence):
         if ask:
             model._si_fuse = {"weight": si_par[0], "n_lambda": si_par[1], "keys": list(loss_composition)}
             # the supervised targets move to the device ONCE (a DataLoader item holds CPU tensors): the model's fused loss and the term below
@@ -90,6 +94,8 @@ def sequence_loss(model, sequence, loss_composition, loss_weights, loss_params=N
             if ask:
                 model._si_fuse = None
         for key, value in preds.items():
+            if parts:
+                seen.append((l, key, value.detach()))
             if not loss_composition or key in loss_composition:
                 w = loss_weights[loss_composition.index(key)]
                 target = item['depth_' + key].to(model.gpu)
@@ -105,12 +111,29 @@ def sequence_loss(model, sequence, loss_composition, loss_weights, loss_params=N
                 if key not in keys_seen:
                     keys_seen.append(key)
         prev_super, prev_lstm = supers['image'], lstms
-    total = torch.stack(terms).sum() / float(L)
+    total = si = torch.stack(terms).sum() / float(L)
+    gl = ml = None
     if grad_loss_weight is not None:
-        total = total + grad_loss_weight * torch.stack(gterms).sum() / float(L)
+        gl = grad_loss_weight * torch.stack(gterms).sum() / float(L)
+        total = total + gl
     if mse_loss is not None:
-        total = total + float(mse_loss.get('weight', 1.0)) * torch.stack(mterms).sum() / float(L)
+        ml = float(mse_loss.get('weight', 1.0)) * torch.stack(mterms).sum() / float(L)
+        total = total + ml
+    if parts:
+        return total, total.detach() * len(keys_seen), dict(loss_parts(len(keys_seen), total, si, gl, ml), predictions=seen)
     return total, total.detach() * len(keys_seen)
+
+
+def loss_parts(n_keys, total, si, grad=None, mse=None):
+    """The reference's `total_batch_losses` (lstm_trainer.py:189-226, :381-383): calculate_total_batch_loss runs once per supervised key
+    on the ONE aliased loss dict, so EVERY entry — 'loss', 'L_si', and 'L_grad' / 'L_mse' when configured — is (#supervised keys) x the
+    differentiated part.  Detached tensors; nothing is read back."""
+    out = {'loss': total.detach() * n_keys, 'L_si': si.detach() * n_keys}
+    if grad is not None:
+        out['L_grad'] = grad.detach() * n_keys
+    if mse is not None:
+        out['L_mse'] = mse.detach() * n_keys
+    return out
 
 
 def _sequence_loss_dp_exact(model, sequence, loss_composition, loss_weights, loss_params, grad_loss_weight, group):
@@ -214,3 +237,186 @@ class EpochTrainer:
                 self.lr_scheduler.step()
             self.lr_history.append(self.lr_scheduler.get_last_lr()[0] if self.lr_scheduler else self.optimizer.param_groups[0]['lr'])
         return self.train_logger
+
+
+def select_evenly_spaced_elements(num_elements, sequence_length):
+    """Preview indices (utils/training_utils.py:11-12)."""
+    return [i * sequence_length // num_elements + sequence_length // (2 * num_elements) for i in range(num_elements)]
+
+
+class SequenceTrainer:
+    """The epoch loops of the reference's LSTMTrainer (`_train_epoch`, lstm_trainer.py:392-572, and `_valid_epoch`, :574-644) around
+    `sequence_loss`, with the training metrics (model/metric.py) on the device — no TensorBoard, preview images, movies or gradient
+    plots.  `train_epoch(epoch)` returns the reference's log entries ('loss', 'losses', 'metrics' and, with a validation loader,
+    'val_loss', 'val_losses', 'val_metrics'), which is what `EpochTrainer(model, config, train_epoch=st.train_epoch)` monitors and
+    stores in its checkpoints; `epoch_trainer()` builds that EpochTrainer and shares its optimizer.
+
+    config keys, read as the reference reads them: config['trainer']['num_previews' | 'num_val_previews' | 'loss_composition' |
+    'loss_weights'], config['loss'] ('type', 'config'), optional config['grad_loss'] / config['mse_loss'], config['metrics'],
+    config['data_loader']['train']['every_x_rgb_frame'].
+
+    Mirrored semantics.  Every entry of 'losses' carries the aliasing factor (`loss_parts`); an epoch value is the sum over the
+    batches / len(loader).  'metrics' = sum over the preview sequences and over ALL prediction keys of the metrics of (prediction of
+    package 0, target of the last supervised key of package 0) / num_previews; the preview indices come from the number of BATCHES
+    and index the DATASET (lstm_trainer.py:96, :490), items get a batch dimension, and the whole preview sequence is forwarded under
+    no_grad in the mode the model is in (train mode in train_epoch: a BN model updates its running statistics, as the reference's).
+    `valid_epoch` runs in eval mode under no_grad and leaves the model in eval mode.
+
+    The batch loops do not synchronise with the host: loss parts go to rows of a device table, preview metrics to ONE
+    metrics.batch_metrics call, and each epoch half reads back once at its end.  step_metrics=True adds the reference's never-reported
+    `calculate_total_metrics` (:290-294: every prediction of every package against 'depth_<key>') as one batch_metrics call per step,
+    averaged into 'step_metrics' / 'val_step_metrics'.  With a process group the float64 table of sums and batch counts is all-reduced
+    at the end of each half, and the previews are chosen from the GLOBAL number of batches, so every rank logs the same values."""
+
+    def __init__(self, config, model, data_loader, valid_data_loader=None, optimizer=None, reducer=None, process_group=None,
+                 step_metrics=False):
+        from . import metrics as M
+        self.config, self.model, self.optimizer, self.reducer, self.group = config, model, optimizer, reducer, process_group
+        self.data_loader, self.valid_data_loader = data_loader, valid_data_loader
+        tr = config['trainer']
+        self.num_previews, self.num_val_previews = tr['num_previews'], tr['num_val_previews']
+        self.loss_composition, self.loss_weights = tr['loss_composition'], tr['loss_weights']
+        self.loss_type = config['loss']['type']
+        if self.loss_type not in LOSS_TYPES:
+            raise KeyError("config['loss']['type'] = %r; known: %s" % (self.loss_type, ", ".join(LOSS_TYPES)))
+        self.loss_params = config['loss'].get('config')
+        self.grad_loss_weight = config['grad_loss'].get('weight', 1.0) if 'grad_loss' in config else None
+        self.mse_loss = None
+        if 'mse_loss' in config:
+            self.mse_loss = {'weight': config['mse_loss'].get('weight', 1.0),
+                             'downsampling_factor': config['mse_loss'].get('downsampling_factor', 0.5)}
+        self.metrics = M.resolve_metrics(config['metrics'])
+        self.every_x_rgb_frame = config['data_loader']['train']['every_x_rgb_frame']
+        self.step_metrics = bool(step_metrics)
+        self.loss_names = ['loss', 'L_si'] + (['L_grad'] if self.grad_loss_weight is not None else []) + (['L_mse'] if self.mse_loss else [])
+        self.preview_indices = select_evenly_spaced_elements(self.num_previews, self._global_batches(data_loader))
+        if valid_data_loader is not None:
+            self.val_preview_indices = select_evenly_spaced_elements(self.num_val_previews, self._global_batches(valid_data_loader))
+
+    def epoch_trainer(self, **kwargs):
+        """EpochTrainer(model, config, train_epoch=self.train_epoch, reducer=self.reducer, **kwargs); this trainer steps ITS optimizer (the
+        one its checkpoints store and a resume restores)."""
+        et = EpochTrainer(self.model, self.config, self.train_epoch, reducer=self.reducer, **kwargs)
+        self.optimizer = et.optimizer
+        return et
+
+    # ---- data parallel: sums over the ranks (one small float64 table per epoch half)
+    def _world(self):
+        import torch.distributed as dist
+        return dist.get_world_size(self.group) if self.group is not None or (dist.is_available() and dist.is_initialized()) else 1
+
+    def _global_batches(self, loader):
+        n = len(loader)
+        if self._world() > 1:
+            import torch.distributed as dist
+            t = torch.tensor([n], dtype=torch.int64)
+            if dist.get_backend(self.group) == "nccl":
+                t = t.to(self.model.gpu)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+            n = int(t.item())
+        return n
+
+    def _all_reduce(self, table):
+        if self._world() > 1:
+            import torch.distributed as dist
+            dist.all_reduce(table, op=dist.ReduceOp.SUM, group=self.group)
+        return table
+
+    # ---- one pass over a loader
+    def _loss(self, sequence):
+        return sequence_loss(self.model, sequence, self.loss_composition, self.loss_weights, loss_params=self.loss_params,
+                             grad_loss_weight=self.grad_loss_weight, loss_type=self.loss_type, mse_loss=self.mse_loss, parts=True)
+
+    def _step_metrics(self, sequence, predictions, acc):
+        from . import metrics as M
+        tab = M.batch_metrics([p for _, _, p in predictions], [sequence[l]['depth_' + key] for l, key, _ in predictions], self.metrics)
+        acc[:-1] += tab.sum(0)
+        acc[-1] += tab.shape[0]
+
+    def _previews(self, dataset, indices):
+        """-> float64 [len(metrics)] on the device: the preview metrics summed over sequences and keys (not yet / num_previews)."""
+        from . import metrics as M
+        preds, targets = [], []
+        K = self.model.every_x_rgb_frame
+        with torch.no_grad():
+            for idx in indices:
+                sequence = dataset[idx]
+                prev_super, prev_lstm, first = None, empty_states_lstm(K), True
+                for item in sequence:
+                    # [C, H, W] items get the batch dimension (lstm_trainer.py:497-500: every key but an already batched 'depth_image')
+                    item = {k: (v.unsqueeze(0) if torch.is_tensor(v) and (k != 'depth_image' or v.dim() < 4) else v) for k, v in item.items()}
+                    out, supers, lstms = self.model(item, prev_super, prev_lstm)
+                    if first:
+                        target = None
+                        for key in out:
+                            if not self.loss_composition or key in self.loss_composition:
+                                target = item['depth_' + key]          # `new_target`: the last supervised key iterated (:282, :377)
+                        if target is None:
+                            raise ValueError("preview %d: package 0 has no supervised prediction (loss_composition %r, predictions %r)"
+                                             % (idx, self.loss_composition, list(out)))
+                        for key, value in out.items():
+                            preds.append(value.detach())
+                            targets.append(target)
+                        first = False
+                    prev_super, prev_lstm = supers['image'], lstms
+            if not preds:
+                return torch.zeros(len(self.metrics), device=self.model.gpu, dtype=torch.float64)
+            return M.batch_metrics(preds, targets, self.metrics).sum(0)
+
+    def _run(self, loader, dataset_indices, n_previews, train):
+        """-> (losses dict, metrics list, step metrics list or None); one device -> host copy."""
+        dev = self.model.gpu
+        nl, nm = len(self.loss_names), len(self.metrics)
+        n_batches = len(loader)
+        rows = torch.zeros((max(n_batches, 1), nl), device=dev, dtype=torch.float64)
+        step_acc = torch.zeros(nm + 1, device=dev, dtype=torch.float64) if self.step_metrics else None
+        for i, sequence in enumerate(loader):
+            if train:
+                if self.reducer is not None:
+                    self.reducer.zero()
+                else:
+                    self.optimizer.zero_grad()
+            total, _, parts = self._loss(sequence)
+            if train:
+                total.backward()
+                if self.reducer is not None:
+                    self.reducer.all_reduce()
+                    self.reducer.wait()
+                self.optimizer.step()
+            if i >= rows.shape[0]:
+                raise RuntimeError("the loader yielded more batches than len(loader) = %d" % n_batches)
+            rows[i].copy_(torch.stack([parts[k].reshape(()) for k in self.loss_names]))
+            if step_acc is not None:
+                with torch.no_grad():
+                    self._step_metrics(sequence, parts['predictions'], step_acc)
+        previews = self._previews(loader.dataset, dataset_indices)
+        # [loss sums | batches | preview metric sums | step metric sums, pairs]: the ranks' tables add up
+        table = torch.cat([rows.sum(0), torch.full((1,), float(n_batches), device=dev, dtype=torch.float64), previews]
+                          + ([step_acc] if step_acc is not None else []))
+        world = self._world()
+        host = self._all_reduce(table).cpu().tolist()
+        losses = {k: host[j] / host[nl] for j, k in enumerate(self.loss_names)}
+        metrics = [v / world / n_previews for v in host[nl + 1:nl + 1 + nm]]          # (every rank forwards the same previews)
+        steps = [v / host[-1] for v in host[nl + 1 + nm:-1]] if step_acc is not None else None
+        return losses, metrics, steps
+
+    def train_epoch(self, epoch):
+        if self.optimizer is None:
+            raise RuntimeError("SequenceTrainer: no optimizer (pass one, or build the EpochTrainer with epoch_trainer())")
+        self.model.train()
+        losses, metrics, steps = self._run(self.data_loader, self.preview_indices, self.num_previews, True)
+        log = {'loss': losses['loss'], 'losses': losses, 'metrics': metrics}
+        if steps is not None:
+            log['step_metrics'] = steps
+        if self.valid_data_loader is not None:
+            log.update(self.valid_epoch(epoch))
+        return log
+
+    def valid_epoch(self, epoch=0):
+        self.model.eval()
+        with torch.no_grad():
+            losses, metrics, steps = self._run(self.valid_data_loader, self.val_preview_indices, self.num_val_previews, False)
+        log = {'val_loss': losses['loss'], 'val_losses': losses, 'val_metrics': metrics}
+        if steps is not None:
+            log['val_step_metrics'] = steps
+        return log

@@ -568,6 +568,37 @@ size_t ramnet_batch_metrics_workspace(int G, int N, size_t npix);
 int ramnet_batch_metrics(const float *const *pred, const float *const *target, int G, int N, size_t npix, void *workspace,
                          double *out, void *stream);
 
+/* ---- multi-scale gradient loss of G pairs together (csrc/grad_loss.hip): the semantics of the per-pair entry points above (model/loss.py:22-70
+ * as oracle/loss_ref.py restates it; kornia parity unpinned), batched, without a saved pyramid, a zero-fill or a floating-point atomic: the
+ * same input gives the same bits on every call.  pred / target: DEVICE tables of G device pointers, pair g a contiguous [B][H][W] fp32
+ * prediction and target (NaN in the target = no ground truth); both are only read, 16-byte aligned maps with W % 4 == 0 are read with
+ * 16-byte loads.  num_scales 1..4, H >> (num_scales - 1) >= 1 and W likewise, B * H * W < 2^31, G <= 65535; G = 0 is a no-op.
+ *
+ * statistics: stats[G][num_scales][2] doubles = (S_s, C_s): sum of |g| over the non-NaN Sobel components of scale s and their count.
+ *   One workgroup per 64 x 64 tile and sample stages diff = pred - target with an 8-pixel halo in LDS, builds the pyramid there and stores
+ *   its sums to its own slot of `workspace` (the size function below, in bytes; 8-byte aligned, nothing to initialise, written before it
+ *   is read); a second launch adds the slots of a pair in a fixed order.  Statistics of shards of a batch ADD UP to those of the whole
+ *   batch (the data-parallel form: all-reduce them).  loss != NULL: a third launch forms the loss with Bg = B, as the from-stats entry.
+ * loss from statistics: loss[g] = w_g * mean_s (S_s / C_s * Bg * 2) (weights: device [G] fp32 or NULL = 1; Bg = the batch count the
+ *   statistics cover — Bg_dev != NULL: read from that device double instead, e.g. an all-reduced sum of the ranks' B), wsum (optional) = sum_g loss[g] in index order.  A scale with C_s = 0 makes the pair's loss NaN (0 / 0, as the
+ *   reference's); the other pairs are not affected.
+ * backward: dpred[g][B][H][W] (ONE buffer, pairs B * H * W floats apart; every element written exactly once) =
+ *   (up[g] + *up_sum) * w_g * gain * sum_s (Bg * 2 / C_s / num_scales) / 4^s * dP_s[Y >> s, X >> s]: a gather — every workgroup re-stages
+ *   its tile with a 16-pixel halo, rebuilds the pyramid and the signs of the Sobel components in LDS and applies the transposed stencil
+ *   (replicate padding: a clamped tap lands on the edge cell) in integer arithmetic.  up (device [G]) / up_sum (device scalar): upstream
+ *   gradients of loss[g] / of wsum, either may be NULL.  A scale with C_s = 0 contributes nothing; pixels under a NaN target get 0.
+ * The pointer-table entry writes n pointers of a HOST array to a device table by kernel argument (no host buffer has to outlive the
+ * call: usable inside a stream capture).                                                                                             */
+int ramnet_fill_pointer_table(const void **table, const void *const *host_ptrs, int n, void *stream);
+size_t ramnet_grad_loss_workspace(int G, int B, int H, int W);
+int ramnet_grad_loss_stats(const float *const *pred, const float *const *target, int G, int B, int H, int W, int num_scales,
+                           void *workspace, double *stats, const float *weights, float *loss, float *wsum, void *stream);
+int ramnet_grad_loss_from_stats(const double *stats, int G, int num_scales, double Bg, const double *Bg_dev, const float *weights,
+                                float *loss, float *wsum, void *stream);
+int ramnet_grad_loss_bwd(const float *const *pred, const float *const *target, int G, int B, int H, int W, int num_scales,
+                         const double *stats, double Bg, const double *Bg_dev, double gain, const float *weights, const float *up,
+                         const float *up_sum, float *dpred, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

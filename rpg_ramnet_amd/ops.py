@@ -2341,6 +2341,217 @@ def multi_scale_grad_loss(prediction, target, num_scales=4):
     return MSGLoss.apply(prediction.float(), target.to(prediction.device).float(), int(num_scales))
 
 
+# ---- the gradient loss of a whole sequence as one batched operation (csrc/grad_loss.hip)
+_GRAD_LOSS_BATCHED = True
+_msg_tables = {}        # (device index, pointers of the pairs) -> int64 [2][G] device table
+_msg_workspaces = {}    # (device index, raw stream) -> float64 workspace of ramnet_grad_loss_stats (per-workgroup slots)
+
+
+def set_grad_loss_batched(on):
+    """trainer.sequence_loss forms the multi-scale gradient loss of all supervised maps of a sequence in ONE batched call after the
+    forward loop (multi_scale_grad_loss_batch: deterministic, no saved pyramid) — on by default; off: one multi_scale_grad_loss per
+    map, as before (A/B runs and the per-pair path's tests)."""
+    global _GRAD_LOSS_BATCHED
+    _GRAD_LOSS_BATCHED = bool(on)
+
+
+def grad_loss_batched():
+    return _GRAD_LOSS_BATCHED
+
+
+def _msg_pairs(preds, targets, what):
+    """Argument checks of the batched gradient loss, BEFORE the library is touched -> (device, B, H, W)."""
+    if len(preds) != len(targets):
+        raise ValueError("%s: %d predictions, %d targets" % (what, len(preds), len(targets)))
+    if not preds:
+        raise ValueError("%s: no pairs" % what)
+    device = preds[0].device
+    shape = tuple(preds[0].shape)
+    if len(shape) != 4 or shape[1] != 1:
+        raise ValueError("%s: maps are B x 1 x H x W, got %s" % (what, shape))
+    for p, t in zip(preds, targets):
+        if tuple(p.shape) != shape or tuple(t.shape) != shape:
+            raise ValueError("%s: every prediction and target must be %s, got %s / %s" % (what, shape, tuple(p.shape), tuple(t.shape)))
+        if p.device != device:
+            raise ValueError("%s: predictions on %s and %s" % (what, device, p.device))
+    if device.type != "cuda":
+        raise ValueError("%s: predictions must live on the GPU (no CPU fallback)" % what)
+    return device, shape[0], shape[2], shape[3]
+
+
+def _msg_table(device, ps, ts):
+    """Device table [2][G] of the pairs' pointers, cached by the pointers themselves (a training step meets the same addresses again).
+    Filled by kernel argument: nothing on the host has to outlive the call, so a stream capture records the fill; a capture never
+    takes a table from the cache (the graph must own, and refill, what it reads)."""
+    capturing = torch.cuda.is_current_stream_capturing()
+    key = (device.index,) + tuple(ps) + tuple(ts)
+    tab = None if capturing else _msg_tables.get(key)
+    if tab is None:
+        tab = torch.empty((2, len(ps)), device=device, dtype=torch.int64)
+        host = (C.c_void_p * (2 * len(ps)))(*(list(ps) + list(ts)))
+        H.check(H.lib().ramnet_fill_pointer_table(C.c_void_p(tab.data_ptr()), host, 2 * len(ps), _st()), "fill_pointer_table")
+        if not capturing:
+            if len(_msg_tables) >= 256:
+                _msg_tables.clear()
+            _msg_tables[key] = tab
+    return tab
+
+
+def _msg_workspace(device, nbytes):
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(nbytes // 8, device=device, dtype=torch.float64)
+    key = (device.index, _st().value or 0)
+    ws = _msg_workspaces.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = _msg_workspaces[key] = torch.empty(nbytes // 8, device=device, dtype=torch.float64)
+    return ws
+
+
+def _msg_prepare(preds, targets, what):
+    device, B, Hh, W = _msg_pairs(preds, targets, what)
+    ps = [p.float().contiguous() for p in preds]
+    ts = [t.detach().to(device=device, dtype=torch.float32).contiguous() for t in targets]
+    return device, B, Hh, W, ps, ts
+
+
+def _msg_weights(weights, G, device):
+    if weights is None:
+        return None
+    if torch.is_tensor(weights):
+        w = weights.detach().to(device=device, dtype=torch.float32).contiguous()
+    else:
+        w = _msg_weight_tensor(tuple(float(x) for x in weights), device)
+    if w.numel() != G:
+        raise ValueError("multi_scale_grad_loss_batch: %d weights for %d pairs" % (w.numel(), G))
+    return w
+
+
+_msg_weight_cache = {}
+
+
+def _msg_weight_tensor(values, device):
+    key = (device.index, values)
+    w = _msg_weight_cache.get(key)
+    if w is None:            # (never evicted: a captured graph may read it; the tuples are configuration constants)
+        w = _msg_weight_cache[key] = torch.tensor(values, dtype=torch.float32, device=device)
+    return w
+
+
+def _msg_stats(device, ps, ts, B, Hh, W, ns, weights=None, want_loss=False, out=None):
+    """-> (pointer table, stats [G, ns, 2] float64[, loss [G], wsum []]) on the current stream; two or three launches whatever G is."""
+    G = len(ps)
+    with torch.cuda.device(device):
+        L = H.lib()
+        tab = _msg_table(device, [p.data_ptr() for p in ps], [t.data_ptr() for t in ts])
+        ws = _msg_workspace(device, L.ramnet_grad_loss_workspace(G, B, Hh, W))
+        stats = torch.empty((G, ns, 2), device=device, dtype=torch.float64) if out is None else out
+        loss = torch.empty(G + 1, device=device) if want_loss else None
+        H.check(L.ramnet_grad_loss_stats(_p(tab[0]), _p(tab[1]), G, B, Hh, W, ns, C.c_void_p(ws.data_ptr()), _p(stats), _p(weights),
+                                         _p(loss), _p(loss, G) if want_loss else None, _st()), "grad_loss_stats")
+    return (tab, stats, loss[:G], loss[G]) if want_loss else (tab, stats)
+
+
+def _msg_backward(ctx, g_loss, g_sum):
+    saved = ctx.saved_tensors
+    tab, stats, weights = saved[:3] if ctx.has_w else tuple(saved[:2]) + (None,)
+    G, B, Hh, W, ns, Bg, gain = ctx.dims
+    device = stats.device
+    with torch.cuda.device(device):
+        d = torch.empty((G, B, 1, Hh, W), device=device)
+        up = g_loss.contiguous().float() if g_loss is not None else None
+        us = g_sum.contiguous().float() if g_sum is not None else None
+        bg_dev = saved[-1] if ctx.bg_dev else None
+        H.check(H.lib().ramnet_grad_loss_bwd(_p(tab[0]), _p(tab[1]), G, B, Hh, W, ns, _p(stats), float(Bg), _p(bg_dev), float(gain), _p(weights),
+                                             _p(up), _p(us), _p(d), _st()), "grad_loss_bwd")
+    return tuple(d[i] if need else None for i, need in enumerate(ctx.needs_input_grad[ctx.first:ctx.first + G]))
+
+
+class MSGLossBatch(Function):
+    """multi_scale_grad_loss of G pairs in one operation: forward(ns, weights or None, targets tuple, *preds) -> (loss [G] = w_g x the
+    pair's loss, their sum).  The backward re-reads predictions and targets (a gather: nothing but the [G, ns, 2] statistics is saved
+    beside them) and writes all G gradient maps in one launch."""
+
+    @staticmethod
+    def forward(ctx, ns, weights, targets, *preds):
+        device, B, Hh, W = preds[0].device, preds[0].shape[0], preds[0].shape[2], preds[0].shape[3]
+        tab, stats, loss, wsum = _msg_stats(device, preds, targets, B, Hh, W, ns, weights, True)
+        ctx.has_w, ctx.first, ctx.bg_dev = weights is not None, 3, False
+        ctx.dims = (len(preds), B, Hh, W, ns, float(B), 1.0)
+        ctx.set_materialize_grads(False)
+        # (predictions and targets are saved because the table holds their addresses: the backward reads them through it)
+        ctx.save_for_backward(*((tab, stats) + ((weights,) if weights is not None else ()) + tuple(preds) + tuple(targets)))
+        return loss, wsum
+
+    @staticmethod
+    def backward(ctx, g_loss, g_sum):
+        return (None, None, None) + _msg_backward(ctx, g_loss, g_sum)
+
+
+class MSGLossBatchFromStats(Function):
+    """The counterpart of SILossFromStats: value from GIVEN statistics [G, ns, 2] (e.g. all-reduced over the ranks) and the global batch
+    count Bg; backward = this rank's share of the single-process gradient on the concatenated batch, times `gain` (= world size: the
+    reducer AVERAGES gradients over ranks, and the shares have to ADD UP).  forward(stats, Bg, gain, weights or None, targets, *preds)."""
+
+    @staticmethod
+    def forward(ctx, stats, Bg, gain, weights, targets, *preds):
+        device, B, Hh, W = preds[0].device, preds[0].shape[0], preds[0].shape[2], preds[0].shape[3]
+        G, ns = len(preds), stats.shape[1]
+        stats = stats.contiguous()
+        with torch.cuda.device(device):
+            tab = _msg_table(device, [p.data_ptr() for p in preds], [t.data_ptr() for t in targets])
+            loss = torch.empty(G + 1, device=device)
+            bg_dev = Bg if torch.is_tensor(Bg) else None
+            H.check(H.lib().ramnet_grad_loss_from_stats(_p(stats), G, ns, 0.0 if bg_dev is not None else float(Bg), _p(bg_dev), _p(weights),
+                                                        _p(loss), _p(loss, G), _st()), "grad_loss_from_stats")
+        ctx.has_w, ctx.first, ctx.bg_dev = weights is not None, 5, bg_dev is not None
+        ctx.dims = (G, B, Hh, W, ns, 0.0 if bg_dev is not None else float(Bg), float(gain))
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(*((tab, stats) + ((weights,) if weights is not None else ()) + tuple(preds) + tuple(targets)
+                                + ((bg_dev,) if bg_dev is not None else ())))
+        return loss[:G], loss[G]
+
+    @staticmethod
+    def backward(ctx, g_loss, g_sum):
+        return (None, None, None, None, None) + _msg_backward(ctx, g_loss, g_sum)
+
+
+def multi_scale_grad_loss_batch(preds, targets, weights=None, num_scales=4, with_sum=False):
+    """The multi-scale gradient loss (model/loss.py:22-70, non-preview branch) of G pairs of B x 1 x H x W maps in one batched,
+    bit-reproducible operation: fp32 [G] on the device, loss[g] = weights[g] x multi_scale_grad_loss(preds[g], targets[g]) (weights:
+    sequence of floats, fp32 tensor [G] or None = 1), differentiable with respect to every prediction.  Three launches forward and one
+    backward whatever G is; nothing is read back.  with_sum=True: (loss [G], their sum in index order as a device scalar)."""
+    device, B, Hh, W, ps, ts = _msg_prepare(preds, targets, "multi_scale_grad_loss_batch")
+    loss, wsum = MSGLossBatch.apply(int(num_scales), _msg_weights(weights, len(ps), device), tuple(ts), *ps)
+    return (loss, wsum) if with_sum else loss
+
+
+def msg_local_stats(preds, targets, num_scales=4, out=None):
+    """(S_s, C_s) of every pair and scale: float64 [G, num_scales, 2] on the device — the per-rank half of the exact data-parallel gradient
+    loss (statistics of batch shards add up).  Not differentiated: multi_scale_grad_loss_from_stats carries the gradient.
+    out: a contiguous float64 [G, num_scales, 2] to write into (e.g. a slice of the table a trainer all-reduces)."""
+    device, B, Hh, W, ps, ts = _msg_prepare(preds, targets, "msg_local_stats")
+    if out is not None and (tuple(out.shape) != (len(ps), int(num_scales), 2) or out.dtype != torch.float64 or out.device != device
+                            or not out.is_contiguous()):
+        raise ValueError("msg_local_stats: out must be a contiguous float64 [%d, %d, 2] on %s" % (len(ps), int(num_scales), device))
+    return _msg_stats(device, [p.detach() for p in ps], ts, B, Hh, W, int(num_scales), out=out)[1]
+
+
+def multi_scale_grad_loss_from_stats(preds, targets, stats, batch, gain=1.0, weights=None, with_sum=False):
+    """loss [G] (and their sum) of the GLOBAL batch from given statistics [G, ns, 2] and the global batch count `batch` (a number, or ONE
+    float64 on the device — e.g. the all-reduced sum of the ranks' B, used without a read-back); the gradient of every prediction is its
+    share of the global one times `gain` (MSGLossBatchFromStats)."""
+    device, B, Hh, W, ps, ts = _msg_prepare(preds, targets, "multi_scale_grad_loss_from_stats")
+    if tuple(stats.shape[::2]) != (len(ps), 2) or stats.dtype != torch.float64 or stats.device != device:
+        raise ValueError("multi_scale_grad_loss_from_stats: stats must be float64 [%d, ns, 2] on %s" % (len(ps), device))
+    if torch.is_tensor(batch):
+        if batch.numel() != 1 or batch.dtype != torch.float64 or batch.device != device:
+            raise ValueError("multi_scale_grad_loss_from_stats: a tensor `batch` is ONE float64 on %s" % (device,))
+    else:
+        batch = float(batch)
+    loss, wsum = MSGLossBatchFromStats.apply(stats, batch, float(gain), _msg_weights(weights, len(ps), device), tuple(ts), *ps)
+    return (loss, wsum) if with_sum else loss
+
+
 def nhwc_add(a, b):
     """a + b on NHWC tensors (UNet head skip, unet.py:129)."""
     a, b = dense(a).contiguous(), dense(b).contiguous()

@@ -48,8 +48,11 @@ def sequence_loss(model, sequence, loss_composition, loss_weights, loss_params=N
     which an average of per-rank losses is not.  With dp_exact every rank computes (sum d, sum d^2, n) of each of its supervised
     maps, ONE all-reduce sums the [terms x 4] table over the ranks before the backward, and every term's value and gradient follow
     from the global sums (ops.SILossFromStats) — after the reducer's gradient average the N-rank gradient is the single-rank one on
-    the concatenated batch, and every rank reports the global loss.  (The multi-scale gradient loss normalises per scale by its own
-    valid-pixel count: it stays per rank.)
+    the concatenated batch, and every rank reports the global loss.  The multi-scale gradient loss normalises every scale by its own
+    count of valid components: its per-scale (sum |g|, count) statistics ride in the same table and all-reduce, and its value and
+    gradient follow from the global sums and the global batch count (ops.MSGLossBatchFromStats).
+    The gradient loss of all supervised maps is ONE batched call after the forward loop (ops.multi_scale_grad_loss_batch; one per
+    distinct map shape) unless ops.set_grad_loss_batched(False) restores one call per map.
     loss_type: config['loss']['type'] — 'scale_invariant_loss' (every shipped config), 'scale_invariant_log_loss' (model/loss.py:12-15)
     or 'mse_loss' (:18-19); loss_params = config['loss']['config'].
     mse_loss: config['mse_loss'] (lstm_trainer.py:76-90) — {'weight': 1.0, 'downsampling_factor': 0.5} — adds
@@ -66,7 +69,8 @@ def sequence_loss(model, sequence, loss_composition, loss_weights, loss_params=N
         if parts:
             raise NotImplementedError("dp_exact: parts=True is not supported")
         return _sequence_loss_dp_exact(model, sequence, loss_composition, loss_weights, loss_params, grad_loss_weight, process_group)
-    gterms, mterms = [], []
+    gterms, mterms, gtriples = [], [], []
+    gbatched = grad_loss_weight is not None and ops.grad_loss_batched()
     L = len(sequence)
     assert L > 0
     K = model.every_x_rgb_frame
@@ -104,7 +108,9 @@ def sequence_loss(model, sequence, loss_composition, loss_weights, loss_params=N
                     terms.append(w * fused[0])
                 else:
                     terms.append(w * _nominal_loss(loss_type, value, target, loss_params))
-                if grad_loss_weight is not None:
+                if gbatched:
+                    gtriples.append((w, value, target))
+                elif grad_loss_weight is not None:
                     gterms.append(w * ops.multi_scale_grad_loss(value, target))
                 if mse_loss is not None:
                     mterms.append(w * ops.mse_loss(value, target, mse_loss.get('downsampling_factor', 0.5)))
@@ -113,7 +119,10 @@ def sequence_loss(model, sequence, loss_composition, loss_weights, loss_params=N
         prev_super, prev_lstm = supers['image'], lstms
     total = si = torch.stack(terms).sum() / float(L)
     gl = ml = None
-    if grad_loss_weight is not None:
+    if gbatched:
+        gl = grad_loss_weight * _batched_grad_loss(gtriples) / float(L)
+        total = total + gl
+    elif grad_loss_weight is not None:
         gl = grad_loss_weight * torch.stack(gterms).sum() / float(L)
         total = total + gl
     if mse_loss is not None:
@@ -122,6 +131,21 @@ def sequence_loss(model, sequence, loss_composition, loss_weights, loss_params=N
     if parts:
         return total, total.detach() * len(keys_seen), dict(loss_parts(len(keys_seen), total, si, gl, ml), predictions=seen)
     return total, total.detach() * len(keys_seen)
+
+
+def _by_shape(triples):
+    """(w, prediction, target) triples grouped by map shape, in order of first appearance (every shipped configuration: one group)."""
+    groups = {}
+    for tr in triples:
+        groups.setdefault(tuple(tr[1].shape), []).append(tr)
+    return list(groups.values())
+
+
+def _batched_grad_loss(triples):
+    """sum of w x multi_scale_grad_loss over the supervised (w, prediction, target) triples: one batched call per distinct map shape."""
+    sums = [ops.multi_scale_grad_loss_batch([v for _, v, _ in grp], [t for _, _, t in grp], [w for w, _, _ in grp], with_sum=True)[1]
+            for grp in _by_shape(triples)]
+    return sums[0] if len(sums) == 1 else torch.stack(sums).sum()
 
 
 def loss_parts(n_keys, total, si, grad=None, mse=None):
@@ -143,6 +167,7 @@ def _sequence_loss_dp_exact(model, sequence, loss_composition, loss_weights, los
     K = model.every_x_rgb_frame
     prev_super, prev_lstm = None, empty_states_lstm(K)
     sup, gterms, keys_seen = [], [], []
+    gbatched = grad_loss_weight is not None and ops.grad_loss_batched()
     for item in sequence:
         preds, supers, lstms = model(item, prev_super, prev_lstm)
         for key, value in preds.items():
@@ -150,22 +175,37 @@ def _sequence_loss_dp_exact(model, sequence, loss_composition, loss_weights, los
                 w = loss_weights[loss_composition.index(key)]
                 target = item['depth_' + key].to(model.gpu).float()
                 sup.append((w, value.float(), target))
-                if grad_loss_weight is not None:
+                if grad_loss_weight is not None and not gbatched:
                     gterms.append(w * ops.multi_scale_grad_loss(value, target))
                 if key not in keys_seen:
                     keys_seen.append(key)
         prev_super, prev_lstm = supers['image'], lstms
-    table = torch.empty(len(sup), 4, device=model.gpu, dtype=torch.float64)
+    # [terms x 4 SI sums | per shape group: pairs x 4 scales x (sum |g|, count) | local batch count]: ONE all-reduce for everything
+    groups = _by_shape(sup) if gbatched else []
+    nsi = 4 * len(sup)
+    flat = torch.empty(nsi + (sum(8 * len(grp) for grp in groups) + 1 if gbatched else 0), device=model.gpu, dtype=torch.float64)
+    table = flat[:nsi].view(len(sup), 4)
     for i, (_, value, target) in enumerate(sup):
         ops.si_local_stats(value.detach(), target, table[i])
+    gstats, o = [], nsi
+    for grp in groups:
+        gstats.append(ops.msg_local_stats([v for _, v, _ in grp], [t for _, _, t in grp], out=flat[o:o + 8 * len(grp)].view(len(grp), 4, 2)))
+        o += 8 * len(grp)
+    if gbatched:
+        flat[-1] = float(sup[0][1].shape[0])
     world = 1
     if dist.is_available() and dist.is_initialized():
         world = dist.get_world_size(group)
-        dist.all_reduce(table, op=dist.ReduceOp.SUM, group=group)       # stream-ordered on the compute stream: 32 B per term
+        dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)        # stream-ordered on the compute stream: 32 B per term, 96 B with the gradient loss
     terms = [w * ops.SILossFromStats.apply(value, target, table[i], float(loss_params["weight"]), float(loss_params["n_lambda"]),
                                            float(world)) for i, (w, value, target) in enumerate(sup)]
     total = torch.stack(terms).sum() / float(L)
-    if grad_loss_weight is not None:
+    if gbatched:
+        # the global batch count (the sum of the ranks' B) is the last entry of the reduced table: the kernels read it on the device
+        sums = [ops.multi_scale_grad_loss_from_stats([v for _, v, _ in grp], [t for _, _, t in grp], g, flat[-1:], gain=float(world),
+                                                     weights=[w for w, _, _ in grp], with_sum=True)[1] for grp, g in zip(groups, gstats)]
+        total = total + grad_loss_weight * (sums[0] if len(sums) == 1 else torch.stack(sums).sum()) / float(L)
+    elif grad_loss_weight is not None:
         total = total + grad_loss_weight * torch.stack(gterms).sum() / float(L)
     # value: SILossFromStats.forward returns the global loss itself (the gain only scales its backward)
     return total, total.detach() * len(keys_seen)

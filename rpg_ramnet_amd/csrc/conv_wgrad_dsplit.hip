@@ -19,6 +19,7 @@
 #include <type_traits>
 #include <utility>
 #include "common.hpp"
+#include "conv_plan.hpp"
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -458,24 +459,9 @@ static int dsplit_splits(int Cin, int Cout) {
 
 int launch_wgrad_dsplit(const ramnet_wgrad_desc &d, hipStream_t st) {
     RAMNET_CHECK_ARG(wgrad_dsplit_eligible(d));
-    int dymin = 127, dxmin = 127;
-    for (int t = 0; t < 9; ++t) {
-        dymin = d.dy[t] < dymin ? d.dy[t] : dymin;
-        dxmin = d.dx[t] < dxmin ? d.dx[t] : dxmin;
-    }
-    for (int t = 0; t < 9; ++t) RAMNET_CHECK_ARG(d.dy[t] - dymin == t / 3 && d.dx[t] - dxmin == t % 3);      // the forward tap order kh*3 + kw
-    const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
-    WgradDsParams q;
-    q.src.x0 = d.x0, q.src.x1 = d.x1, q.src.xm = d.xm;
-    q.src.ld0 = d.ld0, q.src.ld1 = d.ld1, q.src.ldm = d.ldm;
-    q.src.C0 = d.C0, q.src.Cin = d.C0 + (cat ? d.C1 : 0);
-    q.src.mode = d.in_mode, q.src.Hin = d.Hin, q.src.Win = d.Win;
-    if (d.in_mode == RAMNET_IN_S2D) {       // Cin = the four parity groups; ld1 carries log2 C0
-        int sh = 0;
-        while ((1 << sh) < d.C0) ++sh;
-        q.src.Cin = 4 * d.C0, q.src.ld1 = sh;
-    }
-    q.dy0 = dymin, q.dx0 = dxmin;
+    WgradDsParams q{};
+    RAMNET_CHECK_ARG(taps_3x3(d.dy, d.dx, true, q.dy0, q.dx0));      // the forward tap order kh*3 + kw
+    fill_in_src(d, q.src);
     q.bx_n = cdiv(d.Wo, 8), q.ty_n = cdiv(d.Ho, 4), q.nbatch = q.bx_n * q.ty_n * d.B;
     const int gy = cdiv(q.src.Cin, 64), gz = cdiv(d.Cout, 64);
     int splits = dsplit_splits(q.src.Cin, d.Cout);
@@ -531,10 +517,5 @@ extern "C" size_t ramnet_wgrad_dsplit_ws_floats(int Cin, int Cout) { return (siz
 
 extern "C" int ramnet_unpack_wgrad_dsplit(const float *ws, float *grad, int Cout, int Cin, int CinWs, int CoutWs, int n_off, void *stream) {
     RAMNET_CHECK_ARG(ws && grad && Cout > 0 && Cin > 0 && CinWs >= Cin && n_off >= 0 && CoutWs >= n_off + Cout);
-    const size_t total = (size_t)Cout * Cin;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(unpack_wgrad_dsplit_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ws, grad, Cout, Cin, CinWs, CoutWs, n_off, total);
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return launch_1d(unpack_wgrad_dsplit_kernel, (size_t)Cout * Cin, stream, ws, grad, Cout, Cin, CinWs, CoutWs, n_off, (size_t)Cout * Cin);
 }

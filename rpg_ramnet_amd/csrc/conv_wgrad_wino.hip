@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.hpp"
+#include "conv_plan.hpp"
 
 namespace ramnet {
 
@@ -407,29 +408,13 @@ int launch_wgrad_wino(const ramnet_wgrad_desc &d, hipStream_t st) {
     RAMNET_CHECK_ARG(d.in_mode != RAMNET_IN_UP2X && d.in_mode != RAMNET_IN_UP2X_SKIP);
     RAMNET_CHECK_ARG(d.Ho == d.Hin && d.Wo == d.Win);
     if (d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL) RAMNET_CHECK_ARG(d.C0 % 32 == 0);   // a workgroup's channels come from one tensor
-    auto log2_exact = [](int v) { int sh = 0; while ((1 << sh) < v) ++sh; return (1 << sh) == v ? sh : -1; };
     if (d.in_mode == RAMNET_IN_S2D) RAMNET_CHECK_ARG(d.C0 >= 32 && log2_exact(d.C0) > 0);                 // ... or one parity group
-    int dymin = 127, dxmin = 127;
-    unsigned seen = 0;
-    for (int t = 0; t < 9; ++t) {
-        dymin = d.dy[t] < dymin ? d.dy[t] : dymin;
-        dxmin = d.dx[t] < dxmin ? d.dx[t] : dxmin;
-    }
-    for (int t = 0; t < 9; ++t) {   // the workspace rows follow the forward tap order (kh*3 + kw): require exactly that list
-        RAMNET_CHECK_ARG(d.dy[t] - dymin == t / 3 && d.dx[t] - dxmin == t % 3);
-        seen |= 1u << t;
-    }
-    RAMNET_CHECK_ARG(seen == 0x1ffu);
-    const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
-    WgradWinoParams q;
-    q.src.x0 = d.x0, q.src.x1 = d.x1, q.src.xm = d.xm;
-    q.src.ld0 = d.ld0, q.src.ld1 = d.ld1, q.src.ldm = d.ldm;
-    q.src.C0 = d.C0, q.src.Cin = d.C0 + (cat ? d.C1 : 0);
-    q.src.mode = d.in_mode, q.src.Hin = d.Hin, q.src.Win = d.Win;
-    if (d.in_mode == RAMNET_IN_S2D) q.src.Cin = 4 * d.C0, q.src.ld1 = log2_exact(d.C0);
+    WgradWinoParams q{};
+    // the workspace rows follow the forward tap order (kh*3 + kw): require exactly that list
+    RAMNET_CHECK_ARG(taps_3x3(d.dy, d.dx, true, q.dy0, q.dx0));
+    fill_in_src(d, q.src);
     q.bx_n = cdiv(d.Wo, 16), q.ty_n = cdiv(d.Ho, 2);
     q.nbatch = q.bx_n * q.ty_n * d.B;
-    q.dy0 = dymin, q.dx0 = dxmin;
     // batches of 8 tiles: a 2 x 16 or an 8 x 4 pixel strip, whichever pads the map less
     const bool tall = (long)cdiv(d.Wo, 4) * 4 * cdiv(d.Ho, 8) * 8 < (long)cdiv(d.Wo, 16) * 16 * cdiv(d.Ho, 2) * 2;
     if (tall) q.bx_n = cdiv(d.Wo, 4), q.ty_n = cdiv(d.Ho, 8), q.nbatch = q.bx_n * q.ty_n * d.B;
@@ -493,10 +478,5 @@ extern "C" int ramnet_reduce_slabs(float *ws, int slabs, size_t n, void *stream)
 
 extern "C" int ramnet_unpack_wgrad_wino(const float *ws, float *grad, int Cout, int Cin, int CinWs, int CoutWs, int n_off, void *stream) {
     RAMNET_CHECK_ARG(ws && grad && Cout > 0 && Cin > 0 && CinWs >= Cin && n_off >= 0 && CoutWs >= n_off + Cout);
-    const size_t total = (size_t)Cout * Cin;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(unpack_wgrad_wino_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ws, grad, Cout, Cin, CinWs, CoutWs, n_off, total);
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return launch_1d(unpack_wgrad_wino_kernel, (size_t)Cout * Cin, stream, ws, grad, Cout, Cin, CinWs, CoutWs, n_off, (size_t)Cout * Cin);
 }

@@ -26,7 +26,7 @@
 #include <type_traits>
 #include "common.hpp"
 #include "conv_epilogue.hpp"
-#include "conv_wino_common.hpp"
+#include "conv_plan.hpp"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -493,57 +493,32 @@ static void wino_geometry(int Cout, int Cin, int transposed, int gates, int &R, 
 // Geometry and variant of a launch: everything launch_wino needs, and what ramnet_conv_splitk_bytes sizes the workspace from.
 // ksplit = the split of the reduction the launch WANTS (1 = none); it is used when the descriptor carries a workspace.
 static int wino_plan(const ramnet_conv_desc &d, WinoParams &q, bool &tall, int &nf, int &ksplit, unsigned &gridx) {
+    q = WinoParams{};                                               // (launch_wino adds the workspace of a split reduction)
     RAMNET_CHECK_ARG(d.ntaps == 9 && d.stride == 1);
     RAMNET_CHECK_ARG(d.in_mode != RAMNET_IN_UP2X && d.in_mode != RAMNET_IN_UP2X_SKIP);
     if (d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL) RAMNET_CHECK_ARG(d.C0 % WK == 0);   // chunks do not straddle the concatenation
-    auto log2_exact = [](int v) { int sh = 0; while ((1 << sh) < v) ++sh; return (1 << sh) == v ? sh : -1; };
     if (d.in_mode == RAMNET_IN_S2D) RAMNET_CHECK_ARG(d.C0 >= WK && log2_exact(d.C0) > 0);                 // a chunk lies in one parity group
     // the taps must be the dense 3x3 window; which weight slice each one reads is baked into the Winograd pack
-    int dymin = 127, dxmin = 127;
-    unsigned seen = 0;
-    for (int t = 0; t < 9; ++t) {
-        dymin = d.dy[t] < dymin ? d.dy[t] : dymin;
-        dxmin = d.dx[t] < dxmin ? d.dx[t] : dxmin;
-    }
-    for (int t = 0; t < 9; ++t) {
-        const int a = d.dy[t] - dymin, c = d.dx[t] - dxmin;
-        RAMNET_CHECK_ARG(a >= 0 && a < 3 && c >= 0 && c < 3);
-        seen |= 1u << (a * 3 + c);
-    }
-    RAMNET_CHECK_ARG(seen == 0x1ffu);
-    const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
-    q.src.x0 = d.x0, q.src.x1 = d.x1, q.src.xm = d.xm;
-    q.src.ld0 = d.ld0, q.src.ld1 = d.ld1, q.src.ldm = d.ldm;
-    q.src.C0 = d.C0, q.src.Cin = d.C0 + (cat ? d.C1 : 0);
-    q.src.mode = d.in_mode, q.src.Hin = d.Hin, q.src.Win = d.Win;
-    if (d.in_mode == RAMNET_IN_S2D) q.src.Cin = 4 * d.C0, q.src.ld1 = log2_exact(d.C0);
+    RAMNET_CHECK_ARG(taps_3x3(d.dy, d.dx, false, q.dy0, q.dx0));
+    fill_in_src(d, q.src);
     q.nchunks = cdiv(q.src.Cin, WK), q.nblk = d.epi == RAMNET_EPI_LSTM ? cdiv(d.Cout, 16) : cdiv(d.Cout, WBN);
     q.tiles_x = cdiv(d.Wo, WTW), q.tiles_y = cdiv(d.Ho, WTH);
     // 8 x 16 or 32 x 4 output pixels per workgroup, whichever pads the map less
     tall = (long)cdiv(d.Wo, 4) * 4 * cdiv(d.Ho, 32) * 32 < (long)cdiv(d.Wo, 16) * 16 * cdiv(d.Ho, 8) * 8;
     if (tall) q.tiles_x = cdiv(d.Wo, 4), q.tiles_y = cdiv(d.Ho, 32);
-    q.dy0 = dymin, q.dx0 = dxmin;
-    auto al16 = [](const void *ptr) { return ptr == nullptr || ((uintptr_t)ptr & 15) == 0; };
-    q.vec4 = d.Cout % 4 == 0 && d.ldo % 4 == 0 && al16(d.out) && al16(d.bias) && (!d.o1 || (d.ldo1 % 4 == 0 && al16(d.o1))) &&
-             (!d.e0 || (d.lde0 % 4 == 0 && al16(d.e0))) && (!d.e1 || (d.lde1 % 4 == 0 && al16(d.e1))) &&
-             (!d.o2 || (d.ldo2 % 4 == 0 && al16(d.o2)));
+    q.vec4 = conv_vec4(d, true);
     if (d.epi == RAMNET_EPI_LSTM) RAMNET_CHECK_ARG(q.vec4);      // the cell epilogue works on channel quads of the staged tile
     if (d.epi == RAMNET_EPI_GRU_BWD) RAMNET_CHECK_ARG(q.vec4 && d.Cout % 128 == 0);      // a 64-channel block lies in one half of [dx | d(h.r)]
-    q.s2d_shift = 0;
-    q.sparse = 0;
     if (d.s2d_5x5) {
         RAMNET_CHECK_ARG(d.in_mode == RAMNET_IN_S2D || d.out_s2d);
         q.sparse = d.in_mode == RAMNET_IN_S2D ? 1 : (d.out_s2d >= 32 ? 2 : 0);      // (a 32-channel block must lie in one parity group)
     }
     if (d.out_s2d) {
-        RAMNET_CHECK_ARG(d.out_s2d >= 8 && log2_exact(d.out_s2d) > 0 && d.Cout == 4 * d.out_s2d && q.vec4 && d.epi == RAMNET_EPI_LINEAR &&
-                         !d.bias && d.beta == 0.f && d.HoF == 2 * d.Ho && d.WoF == 2 * d.Wo);
+        RAMNET_CHECK_ARG(out_s2d_ok(d) && q.vec4);
         q.s2d_shift = log2_exact(d.out_s2d);
     }
     // XCD-pinned channel groups for weights that do not fit an L2: 2 groups above 3 MB, 4 above 12 MB (when nblk divides)
-    const size_t wbytes = (size_t)q.nchunks * q.nblk * WU_FLOATS * sizeof(float);
-    q.xg = wbytes > (12u << 20) ? 2 : wbytes > (3u << 20) ? 1 : 0;
-    while (q.xg > 0 && (q.nblk % (1 << q.xg)) != 0) --q.xg;
+    q.xg = xcd_groups((size_t)q.nchunks * q.nblk * WU_FLOATS * sizeof(float), q.nblk);
     const int lanes = 8 >> q.xg;
     // Less than one full round of 64-channel workgroups (2 per CU: 512 slots) -> 32-channel workgroups, twice as many: at batch 1
     // (44-176 workgroups) the launch is bound by the latency of a workgroup's chunk chain, which halves; at the training batch the
@@ -560,7 +535,9 @@ static int wino_plan(const ramnet_conv_desc &d, WinoParams &q, bool &tall, int &
     // a launch of fewer workgroups than CUs is latency-bound: skipping the MFMAs of the zero slices buys nothing there, the
     // wave-uniform tests around them cost (enc2 at batch 1: 1.7 instead of 0.9 us per chunk) -> dense
     if (nf == 1 && q.sparse == 1 && wgs2 < 256) q.sparse = 0;
-    gridx = cdiv(q.tiles_x * q.tiles_y * d.B, lanes) * 8 * ((q.nblk * (2 / nf)) >> q.xg);
+    const int nbl = (q.nblk * (2 / nf)) >> q.xg;                    // channel blocks of one XCD group
+    gridx = cdiv(q.tiles_x * q.tiles_y * d.B, lanes) * 8 * nbl;
+    q.inv_nbl = 1.0f / (float)nbl, q.inv_tx = 1.0f / (float)q.tiles_x, q.inv_ty = 1.0f / (float)q.tiles_y;      // (read by the F(2x4) kernels only)
     // Split reduction: a launch of 32-channel workgroups that does not fill the chip's 512 workgroup slots (batch-1 streaming on the two
     // coarse scales: 88-352 workgroups of 32-64 chunks each) is bound by the length of ONE workgroup's chunk chain (0.65 us per chunk) —
     // split it 2-4 ways towards ~704 workgroups, not below 8 chunks per split.  Only the channel-quad epilogue joins partials.
@@ -577,24 +554,14 @@ static int wino_plan(const ramnet_conv_desc &d, WinoParams &q, bool &tall, int &
         if (ksplit < 1) ksplit = 1;
         while (ksplit > 1 && (ksplit - 1) * cdiv(q.nchunks, ksplit) >= q.nchunks) --ksplit;      // (every split owns at least one chunk)
     }
-    {
-        const unsigned long long px = (unsigned long long)d.Hin * d.Win * (d.in_mode == RAMNET_IN_S2D ? 4 : 1);
-        int ldmax = d.ld0 > d.ld1 ? d.ld0 : d.ld1;
-        ldmax = ldmax > d.ldm ? ldmax : d.ldm;
-        RAMNET_CHECK_ARG(px * ldmax * 4ull < (unsigned long long)WOOB);        // per-image 32-bit byte offsets
-        int lo = d.ldo > d.ldo1 ? d.ldo : d.ldo1;                              // ... of the epilogue's tensors too
-        lo = lo > d.lde0 ? lo : d.lde0;
-        lo = lo > d.lde1 ? lo : d.lde1;
-        RAMNET_CHECK_ARG((unsigned long long)d.HoF * d.WoF * lo * 4ull < (unsigned long long)WOOB);
-    }
-    return 0;
+    return check_offsets32(d, false, false);                        // per-image 32-bit byte offsets
 }
 
 // workspace of a split launch: [gridx counters, padded to 64][gridx][ksplit][128 pixels x 32 channels]
 static size_t wino_ksplit_floats(unsigned gridx, int ksplit) { return (size_t)cdiv((int)gridx, 64) * 64 + (size_t)gridx * ksplit * 4096; }
 
 int launch_wino(const ramnet_conv_desc &d, hipStream_t st) {
-    WinoParams q;
+    WinoParams q{};
     bool tall;
     int nf, ksplit;
     unsigned gridx;
@@ -651,7 +618,7 @@ using namespace ramnet;
 extern "C" size_t ramnet_conv_splitk_floats(const ramnet_conv_desc *d) {
     if (d && d->algo == RAMNET_ALGO_WINOGRAD24) return wino24_splitk_floats(*d);
     if (!d || d->algo != RAMNET_ALGO_WINOGRAD) return 0;
-    WinoParams q;
+    WinoParams q{};
     bool tall;
     int nf, ksplit;
     unsigned gridx;
@@ -671,10 +638,5 @@ extern "C" int ramnet_pack_weight_wino(const float *w, float *wp, int Cout, int 
     int R, N, nchunks, nblk;
     wino_geometry(Cout, Cin, transposed, gates, R, N, nchunks, nblk);
     const size_t total = (size_t)nchunks * nblk * WU_FLOATS;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(pack_weight_wino_r_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin,
-                       transposed, gates, R, N, nchunks, nblk, total);
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return launch_1d(pack_weight_wino_r_kernel, total, stream, w, wp, Cout, Cin, transposed, gates, R, N, nchunks, nblk, total);
 }

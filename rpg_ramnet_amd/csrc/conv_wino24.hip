@@ -21,6 +21,7 @@
 // positions (2 x 61.4 KB).  Training-batch launches only (ramnet_fold_wino_variant): no split reduction.
 #include <stdlib.h>
 #include "common.hpp"
+#include "conv_plan.hpp"
 #include "conv_epilogue.hpp"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -802,22 +803,13 @@ extern "C" int ramnet_pack_weight_fold_wino(const float *w, float *wp, int Cout,
     int kc, ncq;
     RAMNET_CHECK_ARG(w && wp && Cout > 0 && Cin > 0 && fold_wino_geometry(Cout, Cin, kc, ncq));
     const size_t total = (size_t)100 * Cout * Cin;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(pack_weight_fold_wino_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin, kc, ncq,
-                       (int)fold_wino_pair(Cout, Cin), total);
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return launch_1d(pack_weight_fold_wino_kernel<2>, total, stream, w, wp, Cout, Cin, kc, ncq, (int)fold_wino_pair(Cout, Cin), total);
 }
 
 extern "C" int ramnet_pack_weight_fold_wino_dgrad(const float *w, float *wp, int Cout, int Cin, void *stream) {
     RAMNET_CHECK_ARG(w && wp && Cout > 0 && Cin > 0 && Cin % 64 == 0 && (4 * Cout) % 16 == 0);
     const size_t total = (size_t)100 * Cout * Cin;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(pack_weight_fold_wino_dgrad_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin, total);
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return launch_1d(pack_weight_fold_wino_dgrad_kernel<2>, total, stream, w, wp, Cout, Cin, total);
 }
 
 extern "C" size_t ramnet_packed_weight_elems_fold_wino2x3(int Cout, int Cin) { return (size_t)120 * Cout * Cin; }
@@ -826,22 +818,13 @@ extern "C" int ramnet_pack_weight_fold_wino2x3(const float *w, float *wp, int Co
     int kc, ncq;
     RAMNET_CHECK_ARG(w && wp && Cout > 0 && Cin > 0 && fold_wino_geometry(Cout, Cin, kc, ncq) && kc == 16);
     const size_t total = (size_t)120 * Cout * Cin;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(pack_weight_fold_wino_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin, kc, ncq,
-                       (int)fold_wino_pair(Cout, Cin), total);
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return launch_1d(pack_weight_fold_wino_kernel<3>, total, stream, w, wp, Cout, Cin, kc, ncq, (int)fold_wino_pair(Cout, Cin), total);
 }
 
 extern "C" int ramnet_pack_weight_fold_wino2x3_dgrad(const float *w, float *wp, int Cout, int Cin, void *stream) {
     RAMNET_CHECK_ARG(w && wp && Cout > 0 && Cin > 0 && Cin % 64 == 0 && (4 * Cout) % 16 == 0);
     const size_t total = (size_t)120 * Cout * Cin;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(pack_weight_fold_wino_dgrad_kernel<3>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin, total);
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return launch_1d(pack_weight_fold_wino_dgrad_kernel<3>, total, stream, w, wp, Cout, Cin, total);
 }
 
 extern "C" int ramnet_fold_wino_variant(const ramnet_conv_desc *d, int force) { return d ? fold_wino_variant(*d, force) : 0; }
@@ -849,19 +832,11 @@ extern "C" int ramnet_fold_wino_variant(const ramnet_conv_desc *d, int force) { 
 extern "C" int ramnet_pack_border_weights(const float *w, float *rows, float *cols, float *rows_t, float *cols_t, int Cout, int Cin, void *stream) {
     RAMNET_CHECK_ARG(w && rows && cols && rows_t && cols_t && Cout > 0 && Cin > 0);
     const size_t total = (size_t)2 * 5 * Cin * 2 * Cout;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(pack_border_weights_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, rows, cols, rows_t, cols_t, Cout, Cin, total);
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return launch_1d(pack_border_weights_kernel, total, stream, w, rows, cols, rows_t, cols_t, Cout, Cin, total);
 }
 
 extern "C" int ramnet_fold_unpack_wgrad(float *w4, float *dU, float *wr, float *wc, float *grad, int Cout, int Cin, int CinWs, void *stream) {
     RAMNET_CHECK_ARG(w4 && wr && wc && grad && Cout > 0 && Cin > 0 && CinWs >= Cin);
     const size_t total = (size_t)Cout * Cin;
-    size_t blocks = (total + 127) / 128;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(fold_unpack_wgrad_kernel, dim3((unsigned)blocks), dim3(128), 0, (hipStream_t)stream, w4, dU, wr, wc, grad, Cout, Cin, CinWs);
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return launch_1d<128>(fold_unpack_wgrad_kernel, total, stream, w4, dU, wr, wc, grad, Cout, Cin, CinWs);
 }

@@ -21,7 +21,7 @@
 #include <type_traits>
 #include "common.hpp"
 #include "conv_epilogue.hpp"
-#include "conv_wino_common.hpp"
+#include "conv_plan.hpp"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -36,9 +36,6 @@ __device__ unsigned long long g_probe6[16384 * 16];
 #else
 #define RAMNET_STAMP(k) do { } while (0)
 #endif
-
-constexpr int W6_BN = 64;                        // output channels per 64-channel block of the packed weights
-constexpr int W6_U_FLOATS = 24 * W6_BN * WK;     // weights of one (chunk, 64-channel block): 24 positions x 64 x 8 = 48 KB
 
 // TXG = tiles per workgroup row: 4 (16 x 16 output pixels), 2 (32 rows x 8 columns) or 8 (8 x 32)
 // LDS layout of a patch plane: pixel (py, px) at slot py * PWS + px + ((py >> 1) & 3), PWS = PW + 3.  A lane reads the 16 bytes of pixel
@@ -533,153 +530,53 @@ static void wino6_geometry(int Cout, int Cin, int transposed, int &R, int &N, in
     nblk = cdiv(N, W6_BN);
 }
 
-// Workgroup tile of F(2x4,3x3) for an Ho x Wo map: 32 tiles of 2 x 4 pixels as 16 x 16 (TXG 4), 32 x 8 (TXG 2) or 8 x 32 (TXG 8),
-// whichever pads the map least; returns the padded area.
-static long wino6_tile(int Ho, int Wo, int &txg) {
-    const int shapes[3] = {4, 2, 8};
-    long best = -1;
-    for (int s = 0; s < 3; ++s) {
-        const int t = shapes[s], th = 2 * (32 / t), tw = 4 * t;
-        const long a = (long)cdiv(Ho, th) * th * cdiv(Wo, tw) * tw;
-        if (best < 0 || a < best) best = a, txg = t;
-    }
-    return best;
-}
-
-static bool wino6_vec4(const ramnet_conv_desc &d) {
-    auto al16 = [](const void *ptr) { return ptr == nullptr || ((uintptr_t)ptr & 15) == 0; };
-    return d.Cout % 4 == 0 && d.ldo % 4 == 0 && al16(d.out) && al16(d.bias) && (!d.o1 || (d.ldo1 % 4 == 0 && al16(d.o1))) &&
-           (!d.e0 || (d.lde0 % 4 == 0 && al16(d.e0))) && (!d.e1 || (d.lde1 % 4 == 0 && al16(d.e1)));
-}
-
-// What the ConvLSTM cell epilogue of conv_wino_r6_kernel needs beyond wino6_vec4: concatenated input on a chunk boundary, hidden size a
-// multiple of 16 (4C gate columns = whole 64-column blocks), bias and o1 present, 16-byte-accessible gates, dense output
-static bool wino6_lstm_ok(const ramnet_conv_desc &d) {
-    return d.in_mode == RAMNET_IN_CAT && d.C0 % WK == 0 && d.Cout > 0 && d.Cout % 16 == 0 && d.o1 && d.bias && !d.out_s2d && !d.frame &&
-           d.osy == 1 && d.osx == 1 && d.ooy == 0 && d.oox == 0 &&
-           (!d.o2 || (d.ldo2 % 4 == 0 && d.ldo2 >= 4 * d.Cout && ((uintptr_t)d.o2 & 15) == 0));
-}
-
-// Does this WINOGRAD-eligible launch run F(2x4,3x3)?  Dense 3x3 layers with plain / concatenated / masked inputs and the channel-quad
-// epilogues or the ConvLSTM cell (no space-to-depth view there), 64-column output blocks, on maps where (a) the 2 x 4 tiling wastes less than
-// a quarter of what it saves and (b) the launch still fills the chip with 64-channel workgroups at ONE per CU.
+// Does this WINOGRAD-eligible launch run F(2x4,3x3)?  Whatever wino6_plan accepts (chunk = WK; WKS: the question of conv_wino6s.hip) — dense
+// 3x3 layers with plain / concatenated / masked inputs and the channel-quad epilogues or the ConvLSTM cell, 64-column output blocks — on maps
+// where (a) the 2 x 4 tiling wastes less than a quarter of what it saves and (b) the launch still fills the chip with 64-channel workgroups
+// at ONE per CU.  Never touches ramnet_last_error().
 static int g_w6_min_wgs = 150;                  // ramnet_wino2x4_config(): launch-size threshold (64-channel workgroups of 256 pixels)
 
-int wino6_eligible(const ramnet_conv_desc &d, int force) {
-    if (d.ntaps != 9 || d.stride != 1 || d.frame) return 0;
+int wino6_eligible(const ramnet_conv_desc &d, int chunk, int force) {
+    Wino6Plan pl;
+    if (wino6_plan(d, chunk, pl, true) != 0) return 0;
     // (space-to-depth views of the stride-2 5x5 encoders, round 5: dense — the zero slices of the view are not skipped here; 3.0 products per
     // output against the 3.5 the F(2x2) kernel realises with its column masks)
-    if (d.in_mode != RAMNET_IN_PLAIN && d.in_mode != RAMNET_IN_CAT && d.in_mode != RAMNET_IN_CAT_MUL && d.in_mode != RAMNET_IN_RELUMASK &&
-        d.in_mode != RAMNET_IN_S2D) return 0;
-    if (d.in_mode == RAMNET_IN_S2D && (d.C0 < WK || (d.C0 & (d.C0 - 1)) != 0)) return 0;
-    if (d.out_s2d && (d.out_s2d < 8 || (d.out_s2d & (d.out_s2d - 1)) != 0 || d.Cout != 4 * d.out_s2d || d.epi != RAMNET_EPI_LINEAR || d.bias || d.beta != 0.f ||
-                      d.HoF != 2 * d.Ho || d.WoF != 2 * d.Wo || (d.in_mode != RAMNET_IN_PLAIN && d.in_mode != RAMNET_IN_RELUMASK))) return 0;
-    // ConvLSTM cell (ABI 27): Cout is the hidden size C, the launch has 4C gate columns — 16 hidden channels x (i, f, o, g) per 64-column block
-    const bool lstm = d.epi == RAMNET_EPI_LSTM;
-    if (lstm && !wino6_lstm_ok(d)) return 0;
-    const int ncol = lstm ? 4 * d.Cout : d.Cout;
-    if (ncol % 64 != 0 || !wino6_vec4(d)) return 0;
-    if (d.epi == RAMNET_EPI_GRU_BWD && d.Cout % 128 != 0) return 0;          // a 64-channel block lies in one half of [dx | d(h.r)]
+    if (d.out_s2d && d.in_mode != RAMNET_IN_PLAIN && d.in_mode != RAMNET_IN_RELUMASK) return 0;
+    if (force) return 1;                                            // (tests: every structurally eligible launch)
     int txg;
     const long a6 = wino6_tile(d.Ho, d.Wo, txg);
     const long a4t = (long)cdiv(d.Wo, 4) * 4 * cdiv(d.Ho, 32) * 32, a4w = (long)cdiv(d.Wo, 16) * 16 * cdiv(d.Ho, 8) * 8;
     const long a4 = a4t < a4w ? a4t : a4w;
-    if (force) return 1;                                            // (tests: every structurally eligible launch)
     if (3 * a6 > 4 * a4 * 0.9) return 0;                            // less than 10 % fewer MFMAs: not worth the larger tiles
-    const long wgs = a6 / 256 * d.B * cdiv(ncol, 64);             // (ConvLSTM: the same rule on its 4C gate columns)
+    const long wgs = a6 / 256 * d.B * pl.q.nblk;                    // (ConvLSTM: the same rule on its 4C gate columns)
     return wgs >= g_w6_min_wgs ? 1 : 0;
 }
 
 int launch_wino6(const ramnet_conv_desc &d, hipStream_t st) {
-    RAMNET_CHECK_ARG(d.ntaps == 9 && d.stride == 1 && !d.frame);
+    Wino6Plan pl;
+    if (int rc = wino6_plan(d, WK, pl)) return rc;
     const bool lstm = d.epi == RAMNET_EPI_LSTM;
-    if (lstm) RAMNET_CHECK_ARG(wino6_lstm_ok(d) && (!d.active || d.e0));
-    const int ncol = lstm ? 4 * d.Cout : d.Cout;                    // (ConvLSTM: Cout = hidden size, the weights hold 4C gate columns)
-    RAMNET_CHECK_ARG(ncol % 64 == 0);
-    RAMNET_CHECK_ARG(d.in_mode == RAMNET_IN_PLAIN || d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL || d.in_mode == RAMNET_IN_RELUMASK ||
-                     d.in_mode == RAMNET_IN_S2D);
-    auto log2_exact = [](int v) { int sh = 0; while ((1 << sh) < v) ++sh; return (1 << sh) == v ? sh : -1; };
-    if (d.in_mode == RAMNET_IN_S2D) RAMNET_CHECK_ARG(d.C0 >= WK && log2_exact(d.C0) > 0);                 // a chunk lies in one parity group
-    if (d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL) RAMNET_CHECK_ARG(d.C0 % WK == 0);   // chunks do not straddle the concatenation
-    RAMNET_CHECK_ARG(wino6_vec4(d) && d.osy == 1 && d.osx == 1 && d.ooy == 0 && d.oox == 0);
-    if (d.out_s2d) RAMNET_CHECK_ARG(d.out_s2d >= 8 && log2_exact(d.out_s2d) > 0 && d.Cout == 4 * d.out_s2d && d.epi == RAMNET_EPI_LINEAR && !d.bias &&
-                                    d.beta == 0.f && d.HoF == 2 * d.Ho && d.WoF == 2 * d.Wo);
-    if (d.epi == RAMNET_EPI_GRU_BWD) RAMNET_CHECK_ARG(d.Cout % 128 == 0);
-    int dymin = 127, dxmin = 127;
-    unsigned seen = 0;
-    for (int t = 0; t < 9; ++t) {
-        dymin = d.dy[t] < dymin ? d.dy[t] : dymin;
-        dxmin = d.dx[t] < dxmin ? d.dx[t] : dxmin;
-    }
-    for (int t = 0; t < 9; ++t) {
-        const int a = d.dy[t] - dymin, c = d.dx[t] - dxmin;
-        RAMNET_CHECK_ARG(a >= 0 && a < 3 && c >= 0 && c < 3);
-        seen |= 1u << (a * 3 + c);
-    }
-    RAMNET_CHECK_ARG(seen == 0x1ffu);
-    const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
-    WinoParams q;
-    q.src.x0 = d.x0, q.src.x1 = d.x1, q.src.xm = d.xm;
-    q.src.ld0 = d.ld0, q.src.ld1 = d.ld1, q.src.ldm = d.ldm;
-    q.src.C0 = d.C0, q.src.Cin = d.C0 + (cat ? d.C1 : 0);
-    q.src.mode = d.in_mode, q.src.Hin = d.Hin, q.src.Win = d.Win;
-    if (d.in_mode == RAMNET_IN_S2D) q.src.Cin = 4 * d.C0, q.src.ld1 = log2_exact(d.C0);
-    q.nchunks = cdiv(q.src.Cin, WK), q.nblk = cdiv(ncol, W6_BN);
-    int txg;
-    wino6_tile(d.Ho, d.Wo, txg);
-    q.tiles_x = cdiv(d.Wo, 4 * txg), q.tiles_y = cdiv(d.Ho, 2 * (32 / txg));
-    q.dy0 = dymin, q.dx0 = dxmin;
-    q.vec4 = 1, q.s2d_shift = d.out_s2d ? log2_exact(d.out_s2d) : 0, q.sparse = 0;
-    // XCD-pinned channel groups for weights that do not fit an L2 (conv_wino.hip)
-    const size_t wbytes = (size_t)q.nchunks * q.nblk * W6_U_FLOATS * sizeof(float);
-    q.xg = wbytes > (12u << 20) ? 2 : wbytes > (3u << 20) ? 1 : 0;
-    while (q.xg > 0 && (q.nblk % (1 << q.xg)) != 0) --q.xg;
-    const int lanes = 8 >> q.xg;
-    const int nf = 1;                                               // 32-channel workgroups
-    q.inv_nbl = 1.0f / (float)((q.nblk * (2 / nf)) >> q.xg), q.inv_tx = 1.0f / (float)q.tiles_x, q.inv_ty = 1.0f / (float)q.tiles_y;
-    dim3 grid(cdiv(q.tiles_x * q.tiles_y * d.B, lanes) * 8 * ((q.nblk * (2 / nf)) >> q.xg));
-    const size_t ex = (size_t)4 * 4 * 32 * (nf * 32 + 4) * sizeof(float);
-    {
-        const unsigned long long px = (unsigned long long)d.Hin * d.Win * (d.in_mode == RAMNET_IN_S2D ? 4 : 1);
-        int ldmax = d.ld0 > d.ld1 ? d.ld0 : d.ld1;
-        ldmax = ldmax > d.ldm ? ldmax : d.ldm;
-        RAMNET_CHECK_ARG(px * ldmax * 4ull < (unsigned long long)WOOB);        // per-image 32-bit byte offsets
-        int lo = d.ldo > d.ldo1 ? d.ldo : d.ldo1;                              // ... of the epilogue's tensors too
-        lo = lo > d.lde0 ? lo : d.lde0;
-        lo = lo > d.lde1 ? lo : d.lde1;
-        if (lstm && d.o2) lo = lo > d.ldo2 ? lo : d.ldo2;
-        RAMNET_CHECK_ARG((unsigned long long)d.HoF * d.WoF * lo * 4ull < (unsigned long long)WOOB);
-    }
-    if (lstm) note_kernel(d.active ? "conv_wino_r6_kernel<%d,%d,masked,lstm>" : "conv_wino_r6_kernel<%d,%d,lstm>", txg, d.in_mode);
-    else note_kernel(d.active ? "conv_wino_r6_kernel<%d,%d,masked>" : "conv_wino_r6_kernel<%d,%d>", txg, d.in_mode);
+    if (lstm) note_kernel(d.active ? "conv_wino_r6_kernel<%d,%d,masked,lstm>" : "conv_wino_r6_kernel<%d,%d,lstm>", pl.txg, d.in_mode);
+    else note_kernel(d.active ? "conv_wino_r6_kernel<%d,%d,masked>" : "conv_wino_r6_kernel<%d,%d>", pl.txg, d.in_mode);
     size_t probe_pad = 0;                       // (probe builds: RAMNET_PROBE_LDS_KB pads the allocation — 90: ONE workgroup per CU)
 #ifdef RAMNET_PROBE
     if (const char *e = getenv("RAMNET_PROBE_LDS_KB")) probe_pad = (size_t)atoi(e) * 1024;
 #endif
-#define RAMNET_GO6(TXv, MDv)                                                                                        \
-    case (TXv) * 100 + (MDv): {                                                                                     \
+#define RAMNET_GO6K(KEYv, TXv, ...)                                                                                 \
+    case (KEYv) + (TXv) * 100: {                                                                                    \
         const size_t pf = (size_t)(2 * R6Geom<TXv>::PFLOATS + 256 * 4) * sizeof(float);                             \
-        RAMNET_FULL_LDS((conv_wino_r6_kernel<TXv, MDv>));                                                           \
-        hipLaunchKernelGGL((conv_wino_r6_kernel<TXv, MDv>), grid, dim3(256), (ex > pf ? ex : pf) + probe_pad, st, d, q); \
+        RAMNET_FULL_LDS((conv_wino_r6_kernel<TXv, __VA_ARGS__>));                                                   \
+        hipLaunchKernelGGL((conv_wino_r6_kernel<TXv, __VA_ARGS__>), dim3(pl.grid), dim3(256), (pl.exchange > pf ? pl.exchange : pf) + probe_pad, st, d, pl.q); \
     } break;
-#define RAMNET_GO6M(TXv, MDv)                                                                                       \
-    case 100000 + (TXv) * 100 + (MDv): {                                                                            \
-        const size_t pf = (size_t)(2 * R6Geom<TXv>::PFLOATS + 256 * 4) * sizeof(float);                             \
-        RAMNET_FULL_LDS((conv_wino_r6_kernel<TXv, MDv, true>));                                                     \
-        hipLaunchKernelGGL((conv_wino_r6_kernel<TXv, MDv, true>), grid, dim3(256), (ex > pf ? ex : pf) + probe_pad, st, d, q); \
-    } break;
-#define RAMNET_GO6L(TXv, MSKv)                                                                                      \
-    case 200000 + (MSKv) * 100000 + (TXv) * 100 + RAMNET_IN_CAT: {                                                  \
-        const size_t pf = (size_t)(2 * R6Geom<TXv>::PFLOATS + 256 * 4) * sizeof(float);                             \
-        RAMNET_FULL_LDS((conv_wino_r6_kernel<TXv, RAMNET_IN_CAT, MSKv, true>));                                     \
-        hipLaunchKernelGGL((conv_wino_r6_kernel<TXv, RAMNET_IN_CAT, MSKv, true>), grid, dim3(256), (ex > pf ? ex : pf) + probe_pad, st, d, q); \
-    } break;
+#define RAMNET_GO6(TXv, MDv) RAMNET_GO6K(MDv, TXv, MDv)
+#define RAMNET_GO6M(TXv, MDv) RAMNET_GO6K(100000 + (MDv), TXv, MDv, true)
+#define RAMNET_GO6L(TXv, MSKv) RAMNET_GO6K(200000 + (MSKv) * 100000 + RAMNET_IN_CAT, TXv, RAMNET_IN_CAT, MSKv, true)
 #define RAMNET_GO6_TX(TXv)                                                                                          \
     RAMNET_GO6L(TXv, false) RAMNET_GO6L(TXv, true)                                                                  \
     RAMNET_GO6M(TXv, RAMNET_IN_CAT) RAMNET_GO6M(TXv, RAMNET_IN_CAT_MUL)                                             \
     RAMNET_GO6(TXv, RAMNET_IN_PLAIN) RAMNET_GO6(TXv, RAMNET_IN_CAT) RAMNET_GO6(TXv, RAMNET_IN_CAT_MUL) RAMNET_GO6(TXv, RAMNET_IN_RELUMASK) \
     RAMNET_GO6(TXv, RAMNET_IN_S2D)
-    switch (txg * 100 + d.in_mode + (d.active ? 100000 : 0) + (lstm ? 200000 : 0)) {
+    switch (pl.txg * 100 + d.in_mode + (d.active ? 100000 : 0) + (lstm ? 200000 : 0)) {
         RAMNET_GO6_TX(4)
         RAMNET_GO6_TX(2)
         RAMNET_GO6_TX(8)
@@ -690,6 +587,7 @@ int launch_wino6(const ramnet_conv_desc &d, hipStream_t st) {
 #undef RAMNET_GO6L
 #undef RAMNET_GO6M
 #undef RAMNET_GO6
+#undef RAMNET_GO6K
     RAMNET_LAUNCH_CHECK();
     return 0;
 }
@@ -709,7 +607,7 @@ extern "C" int ramnet_wino2x4_config(int min_wgs) {
     return 0;
 }
 
-extern "C" int ramnet_conv_wino_variant(const ramnet_conv_desc *d, int force) { return d ? wino6_eligible(*d, force) : 0; }
+extern "C" int ramnet_conv_wino_variant(const ramnet_conv_desc *d, int force) { return d ? wino6_eligible(*d, WK, force) : 0; }
 
 extern "C" size_t ramnet_packed_weight_elems_wino2x4_gates(int Cout, int Cin, int transposed, int gates) {
     int R, N, nchunks, nblk;
@@ -728,12 +626,7 @@ extern "C" int ramnet_pack_weight_wino2x4_gates(const float *w, float *wp, int C
     int R, N, nchunks, nblk;
     wino6_geometry(Cout, Cin, transposed, R, N, nchunks, nblk);
     const size_t total = (size_t)nchunks * nblk * W6_U_FLOATS;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(pack_weight_wino_r6_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, wp, Cout, Cin,
-                       transposed, gates, R, N, nchunks, nblk, total);
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return launch_1d(pack_weight_wino_r6_kernel, total, stream, w, wp, Cout, Cin, transposed, gates, R, N, nchunks, nblk, total);
 }
 
 extern "C" int ramnet_pack_weight_wino2x4(const float *w, float *wp, int Cout, int Cin, int transposed, void *stream) {

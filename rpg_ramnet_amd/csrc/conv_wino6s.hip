@@ -31,7 +31,7 @@
 #include <utility>
 #include "common.hpp"
 #include "conv_epilogue.hpp"
-#include "conv_wino_common.hpp"
+#include "conv_plan.hpp"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -57,10 +57,7 @@ __device__ unsigned long long g_probe6s[16384 * 16];
 #define ABL6S(bit) ((RAMNET_ABL6S & (bit)) != 0)
 #define ABL6S_KEEP(x) asm volatile("" : : "v"(x))
 
-constexpr int WKS = 16;                              // input channels per chunk = K of one v_mfma_f32_32x32x16_bf16
-constexpr int W6S_BN = 64;                           // output channels per workgroup
-constexpr int W6S_POS_BYTES = 2 * 3 * 1024;          // B operands of one (row, position): [32-channel half 2][plane 3][lane 64][8 bf16]
-constexpr int W6S_BLK_BYTES = 4 * 6 * W6S_POS_BYTES; // one (chunk, 64-channel block): 144 KB
+constexpr int W6S_BN = W6_BN;                        // output channels per workgroup
 
 template <class F, int... I>
 __device__ __forceinline__ void sfor_impl(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
@@ -606,97 +603,27 @@ static void wino6s_geometry(int Cout, int Cin, int transposed, int &R, int &N, i
     nblk = cdiv(N, W6S_BN);
 }
 
-int wino6_eligible(const ramnet_conv_desc &d, int force);          // conv_wino6.hip
+int wino6_eligible(const ramnet_conv_desc &d, int chunk, int force);          // conv_wino6.hip
 
 // The split-operand form runs what the exact-fp32 F(2x4,3x3) kernel runs, with 16-channel chunks: a chunk must lie in one tensor of a
-// concatenation and in one parity group of a space-to-depth view.
+// concatenation and in one parity group of a space-to-depth view (wino6_plan with chunk = WKS).
 int wino6s_eligible(const ramnet_conv_desc &d, int force) {
-    if (d.epi == RAMNET_EPI_LSTM || !wino6_eligible(d, force)) return 0;      // (the ConvLSTM cell: exact-fp32 F(2x4) kernel only)
-    if ((d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL) && d.C0 % WKS != 0) return 0;
-    if (d.in_mode == RAMNET_IN_S2D && d.C0 < WKS) return 0;
-    return 1;
+    return d.epi != RAMNET_EPI_LSTM && wino6_eligible(d, WKS, force);      // (the ConvLSTM cell: exact-fp32 F(2x4) kernel only)
 }
 
 int launch_wino6s(const ramnet_conv_desc &d, hipStream_t st) {
-    RAMNET_CHECK_ARG(d.ntaps == 9 && d.stride == 1 && !d.frame && d.epi != RAMNET_EPI_LSTM && d.Cout % 64 == 0);
-    RAMNET_CHECK_ARG(d.in_mode == RAMNET_IN_PLAIN || d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL || d.in_mode == RAMNET_IN_RELUMASK ||
-                     d.in_mode == RAMNET_IN_S2D);
-    auto log2_exact = [](int x) { int sh = 0; while ((1 << sh) < x) ++sh; return (1 << sh) == x ? sh : -1; };
-    auto al16 = [](const void *ptr) { return ptr == nullptr || ((uintptr_t)ptr & 15) == 0; };
-    if (d.in_mode == RAMNET_IN_S2D) RAMNET_CHECK_ARG(d.C0 >= WKS && log2_exact(d.C0) > 0);                 // a chunk lies in one parity group
-    if (d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL) RAMNET_CHECK_ARG(d.C0 % WKS == 0);   // chunks do not straddle the concatenation
-    RAMNET_CHECK_ARG(d.Cout % 4 == 0 && d.ldo % 4 == 0 && al16(d.out) && al16(d.bias) && (!d.o1 || (d.ldo1 % 4 == 0 && al16(d.o1))) &&
-                     (!d.e0 || (d.lde0 % 4 == 0 && al16(d.e0))) && (!d.e1 || (d.lde1 % 4 == 0 && al16(d.e1))) && al16(d.w));
-    RAMNET_CHECK_ARG(d.osy == 1 && d.osx == 1 && d.ooy == 0 && d.oox == 0);
-    if (d.out_s2d) RAMNET_CHECK_ARG(d.out_s2d >= 8 && log2_exact(d.out_s2d) > 0 && d.Cout == 4 * d.out_s2d && d.epi == RAMNET_EPI_LINEAR && !d.bias &&
-                                    d.beta == 0.f && d.HoF == 2 * d.Ho && d.WoF == 2 * d.Wo);
-    if (d.epi == RAMNET_EPI_GRU_BWD) RAMNET_CHECK_ARG(d.Cout % 128 == 0);
-    int dymin = 127, dxmin = 127;
-    unsigned seen = 0;
-    for (int t = 0; t < 9; ++t) {
-        dymin = d.dy[t] < dymin ? d.dy[t] : dymin;
-        dxmin = d.dx[t] < dxmin ? d.dx[t] : dxmin;
-    }
-    for (int t = 0; t < 9; ++t) {
-        const int a = d.dy[t] - dymin, c = d.dx[t] - dxmin;
-        RAMNET_CHECK_ARG(a >= 0 && a < 3 && c >= 0 && c < 3);
-        seen |= 1u << (a * 3 + c);
-    }
-    RAMNET_CHECK_ARG(seen == 0x1ffu);
-    const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
-    WinoParams q;
-    q.src.x0 = d.x0, q.src.x1 = d.x1, q.src.xm = d.xm;
-    q.src.ld0 = d.ld0, q.src.ld1 = d.ld1, q.src.ldm = d.ldm;
-    q.src.C0 = d.C0, q.src.Cin = d.C0 + (cat ? d.C1 : 0);
-    q.src.mode = d.in_mode, q.src.Hin = d.Hin, q.src.Win = d.Win;
-    if (d.in_mode == RAMNET_IN_S2D) q.src.Cin = 4 * d.C0, q.src.ld1 = log2_exact(d.C0);
-    q.nchunks = cdiv(q.src.Cin, WKS), q.nblk = cdiv(d.Cout, W6S_BN);
-    // workgroup tile as in conv_wino6.hip: 16 x 16, 32 x 8 or 8 x 32 output pixels, whichever pads the map least
-    int txg = 4;
-    {
-        const int shapes[3] = {4, 2, 8};
-        long best = -1;
-        for (int s = 0; s < 3; ++s) {
-            const int t = shapes[s], th = 2 * (32 / t), tw = 4 * t;
-            const long a = (long)cdiv(d.Ho, th) * th * cdiv(d.Wo, tw) * tw;
-            if (best < 0 || a < best) best = a, txg = t;
-        }
-    }
-    q.tiles_x = cdiv(d.Wo, 4 * txg), q.tiles_y = cdiv(d.Ho, 2 * (32 / txg));
-    q.dy0 = dymin, q.dx0 = dxmin;
-    q.vec4 = 1, q.s2d_shift = d.out_s2d ? log2_exact(d.out_s2d) : 0, q.sparse = 0;
-    q.ksplit = 1, q.ws = nullptr, q.cnt = nullptr;
-    // XCD-pinned channel groups for weights that do not fit an L2 (conv_wino.hip)
-    const size_t wbytes = (size_t)q.nchunks * q.nblk * W6S_BLK_BYTES;
-    q.xg = wbytes > (12u << 20) ? 2 : wbytes > (3u << 20) ? 1 : 0;
-    while (q.xg > 0 && (q.nblk % (1 << q.xg)) != 0) --q.xg;
-    const int lanes = 8 >> q.xg;
-    q.inv_nbl = 1.0f / (float)(q.nblk >> q.xg), q.inv_tx = 1.0f / (float)q.tiles_x, q.inv_ty = 1.0f / (float)q.tiles_y;
-    dim3 grid(cdiv(q.tiles_x * q.tiles_y * d.B, lanes) * 8 * (q.nblk >> q.xg));
-    const size_t ex = (size_t)4 * 4 * 32 * (64 + 4) * sizeof(float);       // exchange buffer: both 32-channel halves
-    {
-        const unsigned long long px = (unsigned long long)d.Hin * d.Win * (d.in_mode == RAMNET_IN_S2D ? 4 : 1);
-        int ldmax = d.ld0 > d.ld1 ? d.ld0 : d.ld1;
-        ldmax = ldmax > d.ldm ? ldmax : d.ldm;
-        RAMNET_CHECK_ARG(px * ldmax * 4ull < (unsigned long long)WOOB);        // per-image 32-bit byte offsets
-        int lo = d.ldo > d.ldo1 ? d.ldo : d.ldo1;                              // ... of the epilogue's tensors too
-        lo = lo > d.lde0 ? lo : d.lde0;
-        lo = lo > d.lde1 ? lo : d.lde1;
-        RAMNET_CHECK_ARG((unsigned long long)d.HoF * d.WoF * lo * 4ull < (unsigned long long)WOOB);
-    }
-    note_kernel(d.active ? "conv_wino_r6s_kernel<%d,%d,masked>" : "conv_wino_r6s_kernel<%d,%d>", txg, d.in_mode);
-#define RAMNET_GO6S(TXv, MDv)                                                                                       \
-    case (TXv) * 100 + (MDv): {                                                                                     \
+    Wino6Plan pl;
+    if (int rc = wino6_plan(d, WKS, pl)) return rc;
+    RAMNET_CHECK_ARG(al16(d.w));                                    // 16-byte B-operand loads
+    note_kernel(d.active ? "conv_wino_r6s_kernel<%d,%d,masked>" : "conv_wino_r6s_kernel<%d,%d>", pl.txg, d.in_mode);
+#define RAMNET_GO6SK(KEYv, TXv, ...)                                                                                \
+    case (KEYv) + (TXv) * 100: {                                                                                    \
         const size_t pf = (size_t)(2 * R6SGeom<TXv>::PFLOATS + 256 * 4) * sizeof(float);                            \
-        RAMNET_FULL_LDS((conv_wino_r6s_kernel<TXv, MDv>));                                                          \
-        hipLaunchKernelGGL((conv_wino_r6s_kernel<TXv, MDv>), grid, dim3(256), (ex > pf ? ex : pf), st, d, q);       \
+        RAMNET_FULL_LDS((conv_wino_r6s_kernel<TXv, __VA_ARGS__>));                                                  \
+        hipLaunchKernelGGL((conv_wino_r6s_kernel<TXv, __VA_ARGS__>), dim3(pl.grid), dim3(256), (pl.exchange > pf ? pl.exchange : pf), st, d, pl.q); \
     } break;
-#define RAMNET_GO6SM(TXv, MDv)                                                                                      \
-    case 100000 + (TXv) * 100 + (MDv): {                                                                            \
-        const size_t pf = (size_t)(2 * R6SGeom<TXv>::PFLOATS + 256 * 4) * sizeof(float);                            \
-        RAMNET_FULL_LDS((conv_wino_r6s_kernel<TXv, MDv, true>));                                                    \
-        hipLaunchKernelGGL((conv_wino_r6s_kernel<TXv, MDv, true>), grid, dim3(256), (ex > pf ? ex : pf), st, d, q); \
-    } break;
+#define RAMNET_GO6S(TXv, MDv) RAMNET_GO6SK(MDv, TXv, MDv)
+#define RAMNET_GO6SM(TXv, MDv) RAMNET_GO6SK(100000 + (MDv), TXv, MDv, true)
 #if RAMNET_ABL6S
 #define RAMNET_GO6S_TX(TXv) RAMNET_GO6S(TXv, RAMNET_IN_CAT) RAMNET_GO6SM(TXv, RAMNET_IN_CAT)
 #else
@@ -705,7 +632,7 @@ int launch_wino6s(const ramnet_conv_desc &d, hipStream_t st) {
     RAMNET_GO6S(TXv, RAMNET_IN_PLAIN) RAMNET_GO6S(TXv, RAMNET_IN_CAT) RAMNET_GO6S(TXv, RAMNET_IN_CAT_MUL) RAMNET_GO6S(TXv, RAMNET_IN_RELUMASK) \
     RAMNET_GO6S(TXv, RAMNET_IN_S2D)
 #endif
-    switch (txg * 100 + d.in_mode + (d.active ? 100000 : 0)) {
+    switch (pl.txg * 100 + d.in_mode + (d.active ? 100000 : 0)) {
         RAMNET_GO6S_TX(4)
         RAMNET_GO6S_TX(2)
 #if !RAMNET_ABL6S
@@ -717,6 +644,7 @@ int launch_wino6s(const ramnet_conv_desc &d, hipStream_t st) {
 #undef RAMNET_GO6S_TX
 #undef RAMNET_GO6SM
 #undef RAMNET_GO6S
+#undef RAMNET_GO6SK
     RAMNET_LAUNCH_CHECK();
     return 0;
 }
@@ -744,10 +672,5 @@ extern "C" int ramnet_pack_weight_wino2x4_split(const float *w, float *wp, int C
     int R, N, nchunks, nblk;
     wino6s_geometry(Cout, Cin, transposed, R, N, nchunks, nblk);
     const size_t total = (size_t)nchunks * nblk * 4 * 6 * 2 * 64 * 8;          // weights (three planes each)
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 65535) blocks = 65535;
-    hipLaunchKernelGGL(pack_weight_wino_r6s_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, w, (unsigned short *)wp, Cout, Cin,
-                       transposed, R, N, nchunks, nblk, total);
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return launch_1d(pack_weight_wino_r6s_kernel, total, stream, w, (unsigned short *)wp, Cout, Cin, transposed, R, N, nchunks, nblk, total);
 }

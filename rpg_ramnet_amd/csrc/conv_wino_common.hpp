@@ -1,5 +1,6 @@
-// Shared by the Winograd kernels of the 3x3 layers (conv_wino.hip: F(2x2,3x3); conv_wino6.hip: F(2x4,3x3)): launch parameters and the
-// branch-free patch prefetcher.
+// Device side shared by the forward / backward-data Winograd kernels of the 3x3 layers (conv_wino.hip: F(2x2,3x3); conv_wino6.hip and
+// conv_wino6s.hip: F(2x4,3x3), exact fp32 and split bf16 operands): launch parameters and the branch-free patch prefetcher.  What the
+// launchers do with a descriptor on the host: conv_plan.hpp.
 #pragma once
 #include "common.hpp"
 
@@ -19,7 +20,7 @@ struct WinoParams {
     int ksplit;             // F(2x2) kernel, 32-channel workgroups: gridDim.y = splits of the channel reduction (1 = none)
     float *ws;              // ksplit > 1: partial output tiles [gridDim.x][ksplit][128 pixels][32 channels]
     int *cnt;               //             arrival counters [gridDim.x], zero between launches
-    float inv_nbl, inv_tx, inv_ty;      // conv_wino6s.hip: reciprocals of (nblk >> xg), tiles_x, tiles_y (workgroup index decomposition without integer division)
+    float inv_nbl, inv_tx, inv_ty;      // reciprocals of the channel blocks per XCD group (the launch's workgroups per spatial tile >> xg), tiles_x, tiles_y: the F(2x4) kernels decompose the workgroup index without integer division
 };
 
 // Patch prefetcher of the Winograd kernel, MODE = ramnet_in_mode of the launch as a compile-time constant (run-time, wave-uniform

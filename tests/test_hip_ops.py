@@ -288,6 +288,43 @@ def test_winograd2x4_conv3x3_raw(B, H, W, cin, cout):
     assert_close(outs["split"][0].cpu().numpy(), outs["force"][0].cpu().numpy(), 2e-5, "F(2x4) split operands vs exact fp32")
 
 
+@pytest.mark.parametrize("ch", [256, 512])
+def test_winograd_xcd_groups(ch):
+    """The plan branch the small layers never take: Winograd-domain weights beyond 3 MB (256 -> 256) and 12 MB (512 -> 512) are dealt to
+    2 / 4 XCD-pinned channel-block groups (csrc/conv_plan.hpp: xcd_groups) in all three forward kernels — forward with RES_RELU and
+    backward-data through the RELUMASK loader on a B = 1, 8 x 12 map, F(2x2,3x3), F(2x4,3x3) and F(2x4,3x3) with split operands, against
+    float64 F.conv2d / conv_transpose2d."""
+    import torch.nn.functional as F
+    from rpg_ramnet_amd import ops, _hip as Hh
+    B, H, W = 1, 8, 12
+    torch.manual_seed(12)
+    w = torch.randn(ch, ch, 3, 3) * 0.1
+    b = torch.randn(ch) * 0.1
+    cp = ops.ConvParam([torch.nn.Parameter(w.to(dev()))], [torch.nn.Parameter(b.to(dev()))])
+    x, res = torch.randn(B, ch, H, W), torch.randn(B, ch, H, W)
+    xg, resg = nhwc(x).to(dev()).contiguous(), nhwc(res).to(dev()).contiguous()
+    taps, tapsd = ops.Taps.get("conv", 3, 1), ops.Taps.get("dgrad1", 3, 1)
+    yref = torch.relu(F.conv2d(x.double(), w.double(), b.double(), 1, 1) + res.double())
+    dxref = F.conv_transpose2d(torch.where(res > 0, yref, torch.zeros_like(yref)), w.double(), None, 1, 1)
+    for mode in ("off", "force", "split"):
+        ops.set_winograd_2x4("force" if mode == "split" else mode)
+        ops.set_split_operands(mode == "split")
+        try:
+            kern = []
+            y = torch.full((B, H, W, ch), float("nan"), device=dev())
+            ops.conv_launch(xg, taps, cp.fwd(), y, ch, bias=cp.bias(), epi=Hh.EPI_RES_RELU, e0=resg)
+            kern.append(Hh.lib().ramnet_last_kernel().decode())
+            dx = torch.full((B, H, W, ch), float("nan"), device=dev())
+            ops.conv_launch(y, tapsd, cp.bwd(), dx, ch, xm=resg, in_mode=Hh.IN_RELUMASK)
+            kern.append(Hh.lib().ramnet_last_kernel().decode())
+        finally:
+            ops.set_winograd_2x4("auto")
+            ops.set_split_operands(False)
+        assert all(k.startswith({"force": "conv_wino_r6_kernel<", "split": "conv_wino_r6s_kernel<", "off": "conv_wino_r_kernel"}[mode]) for k in kern), kern
+        assert_close(nchw(y).cpu().numpy(), yref.numpy(), TOL, "forward 2x4=%s" % mode)
+        assert_close(nchw(dx).cpu().numpy(), dxref.numpy(), TOL, "dgrad 2x4=%s" % mode)
+
+
 @pytest.mark.parametrize("B,H,W", [(2, 16, 32), (1, 7, 13), (2, 9, 43), (1, 2, 2)])
 @pytest.mark.parametrize("cin,cout", [(64, 64), (32, 96), (40, 20), (128, 256), (36, 64), (68, 36)])
 def test_winograd_conv3x3_raw(B, H, W, cin, cout):

@@ -349,7 +349,8 @@ int ramnet_conv_launch_multi(const ramnet_conv_desc *descs, int n, void *stream)
 int ramnet_wgrad_launch(const ramnet_wgrad_desc *d, void *stream);  /* backward-weights (+bias)    */
 
 /* ---- HBM-bound point-wise / reduction kernels ------------------------------------------------- */
-/* pred = sigmoid(conv1x1(x) + b): statenet.py:116-117,313.  x NHWC [npix, C], y [npix].            */
+/* pred = sigmoid(conv1x1(x) + b): statenet.py:116-117,313.  x NHWC [npix, C], y [npix].  Here, in its backward, in
+ * ramnet_pred_sigmoid_si_fwd / _bwd and in ramnet_pred_linear_fwd / _bwd: C % 4 == 0, ldx % 4 == 0, ldx >= C and, where dx is given, lddx % 4 == 0, lddx >= C. */
 int ramnet_pred_sigmoid_fwd(const float *x, int ldx, int C, const float *w, const float *b, float *y,
                             size_t npix, void *stream);
 /* backward of the above: dx[npix,C] = dz*w, dw[C] += sum dz*x, db += sum dz, dz = dy*y*(1-y).      */
@@ -404,7 +405,8 @@ int ramnet_space_to_depth2(const float *x, float *out, int B, int H, int W, int 
 int ramnet_upsample2x_bwd(const float *dup, float *dx, int B, int H, int W, int C, void *stream);
 /* ConvGRU backward, point-wise parts (derivation in DESIGN.md):
  *  stage A: from dh' and saved u,o,h: dpo = dh'*u*(1-o^2) ; dpu = dh'*(o-h)*u*(1-u) ; dh = dh'*(1-u)
- *  stage B: from d(h*r) (dgrad of the candidate conv) : dpr = dhr*h*r*(1-r) ; dh += dhr*r            */
+ *  stage B: from d(h*r) (dgrad of the candidate conv) : dpr = dhr*h*r*(1-r) ; dh += dhr*r
+ *  (in place: dxhr = [dx | d(h*r)] leaves as [dx | dh + dhr*r], `dh` itself is only read).  C > 0, C % 4 == 0.   */
 int ramnet_gru_bwd_a(const float *dhn, const float *ur, const float *o, const float *h, float *dpo,
                      float *dpur, float *dh, size_t npix, int C, int ld_dhn /* floats per pixel of dhn (>= C: channel slices) */,
                      void *stream);

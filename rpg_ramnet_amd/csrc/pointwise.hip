@@ -1090,7 +1090,7 @@ extern "C" int ramnet_add(const float *a, const float *b, float *y, size_t n, vo
 }
 
 extern "C" int ramnet_pred_sigmoid_fwd(const float *x, int ldx, int C, const float *w, const float *b, float *y, size_t npix, void *stream) {
-    RAMNET_CHECK_ARG(x && w && y && C > 0 && C % 4 == 0 && ldx % 4 == 0);
+    RAMNET_CHECK_ARG(x && w && y && C > 0 && C % 4 == 0 && ldx % 4 == 0 && ldx >= C);
     hipLaunchKernelGGL(pred_sigmoid_fwd_kernel<true>, dim3(grid_for(npix * 8)), dim3(256), 0, (hipStream_t)stream, x, ldx, C, w, b, y, npix);
     RAMNET_LAUNCH_CHECK();
     return 0;
@@ -1098,7 +1098,8 @@ extern "C" int ramnet_pred_sigmoid_fwd(const float *x, int ldx, int C, const flo
 
 static int pred_bwd(const float *x, int ldx, int C, const float *w, const float *y, const float *dy, float *dx, int lddx, float *dw, float *db,
                     size_t npix, void *stream) {
-    if (dx) RAMNET_CHECK_ARG(lddx % 4 == 0);
+    RAMNET_CHECK_ARG(ldx >= C);
+    if (dx) RAMNET_CHECK_ARG(lddx % 4 == 0 && lddx >= C);
     int g = grid_for(npix * 8);      // every workgroup ends with 33 atomics on the SAME 33 addresses: few, fat workgroups
     if (g > 512) g = 512;
     hipLaunchKernelGGL(pred_sigmoid_bwd_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, x, ldx, C, w, y, dy, dx, lddx, dw, db, npix);
@@ -1138,7 +1139,7 @@ extern "C" size_t ramnet_pred_si_scratch_doubles(size_t seg_pix, int nseg) {
 extern "C" int ramnet_pred_sigmoid_si_fwd(const float *x, int ldx, int C, const float *w, const float *b, float *y, size_t seg_pix, int nseg,
                                           const float *const *targets, float weight, float lambda, double *scratch, double *stats, float *loss,
                                           void *stream) {
-    RAMNET_CHECK_ARG(x && w && y && C > 0 && C % 4 == 0 && ldx % 4 == 0 && seg_pix > 0);
+    RAMNET_CHECK_ARG(x && w && y && C > 0 && C % 4 == 0 && ldx % 4 == 0 && ldx >= C && seg_pix > 0);
     RAMNET_CHECK_ARG(nseg >= 1 && nseg <= RAMNET_PRED_SI_MAX_SEGMENTS && targets && scratch && stats && loss);
     PredSiTargets tg;
     for (int i = 0; i < RAMNET_PRED_SI_MAX_SEGMENTS; ++i) tg.t[i] = i < nseg ? targets[i] : nullptr;
@@ -1153,9 +1154,9 @@ extern "C" int ramnet_pred_sigmoid_si_fwd(const float *x, int ldx, int C, const 
 extern "C" int ramnet_pred_sigmoid_si_bwd(const float *x, int ldx, int C, const float *w, const float *y, const float *dy, size_t seg_pix, int nseg,
                                           const float *const *targets, const double *stats, const float *gscale, float weight, float lambda,
                                           float *dx, int lddx, float *dw, float *db, double *scratch, int mask_x, void *stream) {
-    RAMNET_CHECK_ARG(x && w && y && dw && db && C > 0 && C % 4 == 0 && C <= 128 && ldx % 4 == 0 && seg_pix > 0);
+    RAMNET_CHECK_ARG(x && w && y && dw && db && C > 0 && C % 4 == 0 && C <= 128 && ldx % 4 == 0 && ldx >= C && seg_pix > 0);
     RAMNET_CHECK_ARG(nseg >= 1 && nseg <= RAMNET_PRED_SI_MAX_SEGMENTS && targets && stats && gscale);
-    if (dx) RAMNET_CHECK_ARG(lddx % 4 == 0);
+    if (dx) RAMNET_CHECK_ARG(lddx % 4 == 0 && lddx >= C);
     PredSiTargets tg;
     for (int i = 0; i < RAMNET_PRED_SI_MAX_SEGMENTS; ++i) tg.t[i] = i < nseg ? targets[i] : nullptr;
     for (int i = 0; i < nseg; ++i) RAMNET_CHECK_ARG(tg.t[i] != nullptr);
@@ -1176,7 +1177,7 @@ extern "C" int ramnet_pred_sigmoid_si_bwd(const float *x, int ldx, int C, const 
 }
 
 extern "C" int ramnet_pred_linear_fwd(const float *x, int ldx, int C, const float *w, const float *b, float *z, size_t npix, void *stream) {
-    RAMNET_CHECK_ARG(x && w && z && C > 0 && C % 4 == 0 && ldx % 4 == 0);
+    RAMNET_CHECK_ARG(x && w && z && C > 0 && C % 4 == 0 && ldx % 4 == 0 && ldx >= C);
     hipLaunchKernelGGL(pred_sigmoid_fwd_kernel<false>, dim3(grid_for(npix * 8)), dim3(256), 0, (hipStream_t)stream, x, ldx, C, w, b, z, npix);
     RAMNET_LAUNCH_CHECK();
     return 0;
@@ -1252,7 +1253,7 @@ extern "C" int ramnet_space_to_depth2(const float *x, float *out, int B, int H, 
 
 extern "C" int ramnet_gru_bwd_a(const float *dhn, const float *ur, const float *o, const float *h, float *dpo, float *dpur,
                                 float *dh, size_t npix, int C, int ld_dhn, void *stream) {
-    RAMNET_CHECK_ARG(dhn && ur && o && dpo && dpur && dh && C % 4 == 0 && ld_dhn >= C && ld_dhn % 4 == 0);
+    RAMNET_CHECK_ARG(dhn && ur && o && dpo && dpur && dh && C > 0 && C % 4 == 0 && ld_dhn >= C && ld_dhn % 4 == 0);
     hipLaunchKernelGGL(gru_bwd_a_kernel, dim3(grid_for(npix * (C / 4))), dim3(256), 0, (hipStream_t)stream, dhn, ur, o, h, dpo, dpur, dh, npix, C,
                        ld_dhn, C);
     RAMNET_LAUNCH_CHECK();
@@ -1263,7 +1264,7 @@ extern "C" int ramnet_gru_bwd_a(const float *dhn, const float *ur, const float *
 // convolution's backward-data launch then completes in its epilogue (RAMNET_EPI_GRU_BWD) — stage B without a launch of its own
 extern "C" int ramnet_gru_bwd_a2(const float *dhn, const float *ur, const float *o, const float *h, float *dpo, float *dpur,
                                  float *dh, size_t npix, int C, int ld_dhn, int ld_dh, void *stream) {
-    RAMNET_CHECK_ARG(dhn && ur && o && dpo && dpur && dh && C % 4 == 0 && ld_dhn >= C && ld_dhn % 4 == 0 && ld_dh >= C && ld_dh % 4 == 0);
+    RAMNET_CHECK_ARG(dhn && ur && o && dpo && dpur && dh && C > 0 && C % 4 == 0 && ld_dhn >= C && ld_dhn % 4 == 0 && ld_dh >= C && ld_dh % 4 == 0);
     hipLaunchKernelGGL(gru_bwd_a_kernel, dim3(grid_for(npix * (C / 4))), dim3(256), 0, (hipStream_t)stream, dhn, ur, o, h, dpo, dpur, dh, npix, C,
                        ld_dhn, ld_dh);
     RAMNET_LAUNCH_CHECK();
@@ -1271,7 +1272,7 @@ extern "C" int ramnet_gru_bwd_a2(const float *dhn, const float *ur, const float 
 }
 
 extern "C" int ramnet_gru_bwd_b(const float *dxhr, const float *ur, const float *h, float *dpur, float *dh, size_t npix, int C, void *stream) {
-    RAMNET_CHECK_ARG(dxhr && ur && dpur && dh && C % 4 == 0);
+    RAMNET_CHECK_ARG(dxhr && ur && dpur && dh && C > 0 && C % 4 == 0);
     hipLaunchKernelGGL(gru_bwd_b_kernel, dim3(grid_for(npix * (C / 4))), dim3(256), 0, (hipStream_t)stream, const_cast<float *>(dxhr), ur, h, dpur, dh, npix, C);
     RAMNET_LAUNCH_CHECK();
     return 0;
@@ -1279,7 +1280,7 @@ extern "C" int ramnet_gru_bwd_b(const float *dxhr, const float *ur, const float 
 
 extern "C" int ramnet_lstm_bwd(const float *gates, const float *cprev, const float *cnew, const float *dhn, const float *dcn,
                                float *dpre, float *dcprev, size_t npix, int C, void *stream) {
-    RAMNET_CHECK_ARG(gates && cnew && dpre && dcprev && C % 4 == 0);
+    RAMNET_CHECK_ARG(gates && cnew && dpre && dcprev && C > 0 && C % 4 == 0);
     hipLaunchKernelGGL(lstm_bwd_kernel<false>, dim3(grid_for(npix * (C / 4))), dim3(256), 0, (hipStream_t)stream, gates, cprev, cnew, dhn, dcn, dpre, dcprev, npix, C,
                        nullptr, nullptr, 1);
     RAMNET_LAUNCH_CHECK();
@@ -1288,7 +1289,7 @@ extern "C" int ramnet_lstm_bwd(const float *gates, const float *cprev, const flo
 
 extern "C" int ramnet_lstm_bwd_masked(const float *gates, const float *cprev, const float *cnew, const float *dhn, const float *dcn,
                                       const int *active, float *dpre, float *dcprev, float *dxh, size_t npix, int hw, int C, void *stream) {
-    RAMNET_CHECK_ARG(gates && cnew && dpre && dcprev && active && dxh && hw > 0 && npix % (size_t)hw == 0 && C % 4 == 0);
+    RAMNET_CHECK_ARG(gates && cnew && dpre && dcprev && active && dxh && hw > 0 && npix % (size_t)hw == 0 && C > 0 && C % 4 == 0);
     hipLaunchKernelGGL(lstm_bwd_kernel<true>, dim3(grid_for(npix * (C / 4))), dim3(256), 0, (hipStream_t)stream, gates, cprev, cnew, dhn, dcn, dpre, dcprev, npix, C,
                        active, dxh, hw);
     RAMNET_LAUNCH_CHECK();

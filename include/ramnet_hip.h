@@ -570,6 +570,35 @@ size_t ramnet_batch_metrics_workspace(int G, int N, size_t npix);
 int ramnet_batch_metrics(const float *const *pred, const float *const *target, int G, int N, size_t npix, void *workspace,
                          double *out, void *stream);
 
+/* ---- depth evaluation table of G (prediction, target) pairs: evaluation.py:74-96, :201-241, :359-390 (csrc/metrics.hip) -----------
+ * The metric-depth conversion: out[i] = expf(reg_factor * (y[i] - 1.0f)) * clip_distance in fp32, with clamp != 0 clipped to
+ * [expf(-reg_factor) * clip_distance, clip_distance] (the prediction side of prepare_depth_data); NaN stays NaN.  The table kernels
+ * convert with the same device function.
+ * The table: pred / target are DEVICE tables of G device pointers to npix floats of normalised log depth each (NaN target = no ground
+ * truth); mask is NULL or a DEVICE table of G pointers to npix bytes (non-zero = inside the event mask; a NULL entry = all inside).
+ * cutoffs: HOST array of ncut ascending positive metric depths, 0 <= ncut <= 8, read during the call.
+ * out[G][V][16] doubles, V = (1 + ncut) * (mask ? 2 : 1); variants: all pixels, cut-off 0 .. ncut - 1, then the same under the mask.
+ * A pixel is inside a variant when (mask byte != 0 or the variant is unmasked) and (target NaN or metric target < cutoff) — the
+ * reference's np.nan_to_num(target) < cutoff; variant 0 of each half applies no cut-off test.  Columns of a row, t / p = metric target /
+ * clipped metric prediction, d = t - p, ld = log(t + 1e-5) - log(p + 1e-5), all in double over the float32 t and p exactly as the
+ * per-pair depth metrics above form them:
+ *   0 n_mask = pixels inside           1 n = pixels inside with a non-NaN target; over those n pixels:
+ *   2 sum |d| / (t + 1e-6)   3 sum d^2 / (t^2 + 1e-6)   4 sum d^2   5 sum ld^2   6 sum |ld|   7 sum |d|
+ *   8..10 count(max(t / (p + 1e-5), p / (t + 1e-5)) <= 1.25, 1.25^2, 1.25^3)   (the reference divides them by n_mask)
+ *   11 median of t, 12 median of p over the pixels inside: np.median of the float32 values (even count: (a + b) * 0.5f), exact, by a
+ *      three-pass radix selection on the bit patterns; NaN when n != n_mask or n_mask == 0, as np.median over such a mask is
+ *   13..15 zero
+ * Three launches whatever G and V are, partial sums and histograms joined in index order: the same input gives the same bits on every
+ * call; nothing is read back.  workspace: the size the workspace function returns (0 for sizes the call would reject), 256-byte
+ * aligned; its first RAMNET_EVAL_TABLE_TICKET_BYTES must be ZERO WHEN IT IS ALLOCATED, every call leaves them zero again and writes
+ * whatever else it reads: calls of any shape that fit the allocation follow each other with no memset in between (one call at a time
+ * per workspace: order them on one stream).  G * V may not exceed the tickets (RAMNET_EVAL_TABLE_TICKET_BYTES / 4).                 */
+#define RAMNET_EVAL_TABLE_TICKET_BYTES 262144
+int ramnet_metric_depth(const float *y, size_t n, float clip_distance, float reg_factor, int clamp, float *out, void *stream);
+size_t ramnet_eval_table_workspace(int G, size_t npix, int ncut, int has_mask);
+int ramnet_eval_table(const float *const *pred, const float *const *target, const unsigned char *const *mask, int G, size_t npix,
+                      float clip_distance, float reg_factor, const float *cutoffs, int ncut, void *workspace, double *out, void *stream);
+
 /* ---- multi-scale gradient loss of G pairs together (csrc/grad_loss.hip): the semantics of the per-pair entry points above (model/loss.py:22-70
  * as oracle/loss_ref.py restates it; kornia parity unpinned), batched, without a saved pyramid, a zero-fill or a floating-point atomic: the
  * same input gives the same bits on every call.  pred / target: DEVICE tables of G device pointers, pair g a contiguous [B][H][W] fp32

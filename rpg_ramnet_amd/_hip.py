@@ -177,6 +177,9 @@ _SIGS = {
     "ramnet_augment_batch": (C.c_int, [_fp] * 9 + [C.c_int] * 9 + [_fp]),
     "ramnet_batch_metrics_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_size_t]),
     "ramnet_batch_metrics": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_size_t, _fp, _fp, _fp]),
+    "ramnet_metric_depth": (C.c_int, [_fp, C.c_size_t, C.c_float, C.c_float, C.c_int, _fp, _fp]),
+    "ramnet_eval_table_workspace": (C.c_size_t, [C.c_int, C.c_size_t, C.c_int, C.c_int]),
+    "ramnet_eval_table": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_size_t, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_int, _fp, _fp, _fp]),
     "ramnet_fill_pointer_table": (C.c_int, [_fp, C.POINTER(C.c_void_p), C.c_int, _fp]),
     "ramnet_grad_loss_workspace": (C.c_size_t, [C.c_int] * 4),
     "ramnet_grad_loss_stats": (C.c_int, [_fp, _fp] + [C.c_int] * 5 + [_fp] * 6),

@@ -98,7 +98,8 @@ __device__ __forceinline__ void bm_sweep(bm_src_t p, bm_src_t t, unsigned lo, un
 
 // Adds the P slabs `h` of pair g into the LDS histogram (index order), all threads.  The loads of four slabs are in flight together: one
 // after the other, the P x NBINS / BM_T coherent loads of a thread were most of a launch (profiles/epoch_metrics_notes.md).
-template <int NBINS>
+// WGS / HS: words between the slabs of two workgroups / of two histograms of one workgroup (the evaluation table below packs four).
+template <int NBINS, int WGS = 2 * BM_BINS, int HS = BM_BINS>
 __device__ __forceinline__ void bm_join_slabs(const unsigned *slab, size_t g, int P, int h, unsigned *lds) {
     constexpr int PER = NBINS / BM_T;
     unsigned v[PER];
@@ -110,7 +111,7 @@ __device__ __forceinline__ void bm_join_slabs(const unsigned *slab, size_t g, in
         for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
             for (int j = 0; j < PER; ++j)
-                x[kk][j] = k0 + kk < P ? bm_ld(slab + (((size_t)g * P + k0 + kk) * 2 + h) * BM_BINS + threadIdx.x + j * BM_T) : 0u;
+                x[kk][j] = k0 + kk < P ? bm_ld(slab + ((size_t)g * P + k0 + kk) * WGS + (size_t)h * HS + threadIdx.x + j * BM_T) : 0u;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
@@ -154,11 +155,8 @@ __device__ __forceinline__ void bm_select(const unsigned *lds, int nbins, unsign
     __syncthreads();
 }
 
-// Stores the workgroup's histogram(s) to its slab(s), takes the pair's ticket; true in every thread of the last arrival of the pair.
-__device__ __forceinline__ bool bm_arrive(unsigned (*hist)[BM_BINS], int nh, int nbins, unsigned *slab, size_t g, int P, int wg, unsigned *tickets,
-                                          int *flag) {
-    for (int h = 0; h < nh; ++h)
-        for (int b = threadIdx.x; b < nbins; b += BM_T) slab[(((size_t)g * P + wg) * 2 + h) * BM_BINS + b] = hist[h][b];
+// Takes the pair's ticket after the workgroup's stores; true in every thread of the last arrival of the pair.
+__device__ __forceinline__ bool bm_ticket(size_t g, int P, unsigned *tickets, int *flag) {
     // Release ONCE per workgroup (a __threadfence() in each of the 6144 waves of a G = 48 launch writes the L2 back 6144 times): every wave
     // waits until its own stores have reached the L2 (the barrier alone does not), then thread 0 fences at device scope and takes the ticket.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -171,6 +169,14 @@ __device__ __forceinline__ bool bm_arrive(unsigned (*hist)[BM_BINS], int nh, int
     const bool last = *flag != 0;
     if (last) __threadfence();
     return last;
+}
+
+// Stores the workgroup's histogram(s) to its slab(s), takes the pair's ticket; true in every thread of the last arrival of the pair.
+__device__ __forceinline__ bool bm_arrive(unsigned (*hist)[BM_BINS], int nh, int nbins, unsigned *slab, size_t g, int P, int wg, unsigned *tickets,
+                                          int *flag) {
+    for (int h = 0; h < nh; ++h)
+        for (int b = threadIdx.x; b < nbins; b += BM_T) slab[(((size_t)g * P + wg) * 2 + h) * BM_BINS + b] = hist[h][b];
+    return bm_ticket(g, P, tickets, flag);
 }
 
 __global__ void __launch_bounds__(BM_T) bm_sums_kernel(const float *const *__restrict__ preds, const float *const *__restrict__ targets, int N,
@@ -339,5 +345,331 @@ extern "C" int ramnet_batch_metrics(const float *const *pred, const float *const
     hipLaunchKernelGGL(bm_select_kernel<0>, grid, dim3(BM_T), 0, st, pred, target, N, (unsigned)npix, pl.Ws, tickets, state, slab, out);
     RAMNET_LAUNCH_CHECK();
     note_kernel("bm_sums_kernel + bm_select_kernel<10> + bm_select_kernel<0>");
+    return 0;
+}
+
+// ================================================================================================ depth evaluation table
+namespace ramnet {
+
+// The table of evaluation.py:295-397 for G (prediction, target) pairs of normalised log depth, every variant of it together: all pixels and
+// each depth cut-off, and the same again under an event mask.  grid = (Ws, V, G): workgroup (w, v, g) reads its part of map g for variant v;
+// every variant re-reads the maps (they stay in L2: 8 B per pixel and pair), which keeps one histogram set per workgroup and the joins of
+// the training metrics above: partial rows and slabs in index order, tickets that reset themselves, the same bits on every call.
+//
+// pass 1  the sums of depth_metrics_kernel (loss_voxel.hip: same expressions, epsilons and types) + histograms of bits 30..20 of the metric
+//         target and of the metric prediction (positive floats: the pattern orders like the value)
+// pass 2  bits 19..10 under the prefixes of the wanted ranks (two per stream for an even count), pass 3  bits 9..0 -> both medians
+// A variant whose mask holds a NaN target, or nothing, has NaN medians (np.median over such a mask is NaN): passes 2 and 3 skip it.
+//
+// Workspace: [64 Ki tickets][G V states][G V x P partial rows][G V x P slabs of 4096 words: 2 x 2048 bins in pass 1, 4 x 1024 after it].
+constexpr int ET_ROW = 12;                 // doubles of a partial row: n_mask, n, six sums, three threshold counts, (unused)
+constexpr int ET_COLS = 11;
+constexpr int ET_OUT = 16;                 // doubles of an output row
+constexpr int ET_STATE = 12;               // uint32 per (pair, variant): target prefix0, rank0, prefix1, rank1; the same of the prediction; n; medians wanted
+constexpr int ET_MAX_PER_MAP = 32;         // workgroups per (pair, variant) at most
+constexpr unsigned ET_SPAN = 16384;        // pixels a workgroup should at least have (its slab is 16 KB: an eighth of what it reads)
+constexpr int ET_SLAB = 2 * BM_BINS;       // words of a workgroup's slab
+constexpr int ET_MAXCUT = 8;
+
+typedef const unsigned char __attribute__((address_space(1))) *et_msk_t;
+typedef unsigned char et_b4 __attribute__((ext_vector_type(4), aligned(1)));
+
+struct et_args_t {
+    float clip, reg, cut[ET_MAXCUT];
+    int ncut, V, Ws;
+    unsigned npix;
+};
+
+struct et_plan_t {
+    int V, Ws;
+    size_t off_state, off_part, off_slab, total;
+};
+
+static et_plan_t et_plan(int G, size_t npix, int ncut, int has_mask) {
+    et_plan_t p;
+    size_t ws = (npix + ET_SPAN - 1) / ET_SPAN;
+    if (ws > ET_MAX_PER_MAP) ws = ET_MAX_PER_MAP;
+    p.Ws = (int)ws;
+    p.V = (1 + ncut) * (has_mask ? 2 : 1);
+    const size_t cells = (size_t)G * p.V;
+    p.off_state = RAMNET_EVAL_TABLE_TICKET_BYTES;
+    p.off_part = p.off_state + ((cells * ET_STATE * sizeof(unsigned) + 255) & ~(size_t)255);
+    p.off_slab = p.off_part + ((cells * p.Ws * ET_ROW * sizeof(double) + 255) & ~(size_t)255);
+    p.total = p.off_slab + cells * p.Ws * ET_SLAB * sizeof(unsigned);
+    return p;
+}
+
+static bool et_sizes_ok(int G, size_t npix, int ncut, int has_mask) {
+    if (G < 1 || G > 65535 || npix == 0 || npix >= ((size_t)1 << 32) || ncut < 0 || ncut > ET_MAXCUT) return false;
+    return (size_t)G * (1 + ncut) * (has_mask ? 2 : 1) <= RAMNET_EVAL_TABLE_TICKET_BYTES / sizeof(unsigned);
+}
+
+// Normalised log depth -> metric depth (evaluation.py:76-85), the ONE conversion of ramnet_metric_depth and of the table kernels.
+// lo = expf(-reg) * clip.  The clamp keeps a NaN (both comparisons are false); on numbers it is fminf(fmaxf(d, lo), clip).
+__device__ __forceinline__ float et_metric_depth(float y, float reg, float clip, float lo, bool clamp) {
+    float d = expf(reg * (y - 1.0f)) * clip;
+    if (clamp) d = d < lo ? lo : (d > clip ? clip : d);
+    return d;
+}
+
+// bm_range for a map of up to 2^32 - 1 pixels
+__device__ __forceinline__ void et_range(unsigned npix, int Ws, int w, unsigned &lo, unsigned &hi) {
+    const unsigned chunk = (unsigned)((((unsigned long long)npix + Ws - 1) / Ws + 3u) & ~3ull);
+    const unsigned long long a = (unsigned long long)w * chunk;
+    lo = a < npix ? (unsigned)a : npix;
+    hi = npix - lo < chunk ? npix : lo + chunk;
+}
+
+// f(p, t, inside mask) over the pixels [lo, hi) of one map: 16 bytes per lane and map (and 4 of the mask), then the tail.  m == NULL: all inside.
+template <class F>
+__device__ __forceinline__ void et_sweep(bm_src_t p, bm_src_t t, et_msk_t m, unsigned lo, unsigned hi, F f) {
+    typedef const bm_f4u __attribute__((address_space(1))) *v4_t;
+    typedef const et_b4 __attribute__((address_space(1))) *b4_t;
+    const unsigned nv = (hi - lo) >> 2;
+    unsigned i = threadIdx.x;
+    for (; i + BM_T < nv; i += 2 * BM_T) {                        // four (six) loads in flight per lane
+        bm_f4u a[2], b[2];
+        et_b4 c[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const size_t o = lo + 4 * (size_t)(i + j * BM_T);
+            a[j] = *(v4_t)(p + o), b[j] = *(v4_t)(t + o);
+            c[j] = m ? *(b4_t)(m + o) : (et_b4)(unsigned char)1;
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) f(a[j].x, b[j].x, c[j].x), f(a[j].y, b[j].y, c[j].y), f(a[j].z, b[j].z, c[j].z), f(a[j].w, b[j].w, c[j].w);
+    }
+    for (; i < nv; i += BM_T) {
+        const size_t o = lo + 4 * (size_t)i;
+        const bm_f4u a = *(v4_t)(p + o), b = *(v4_t)(t + o);
+        const et_b4 c = m ? *(b4_t)(m + o) : (et_b4)(unsigned char)1;
+        f(a.x, b.x, c.x), f(a.y, b.y, c.y), f(a.z, b.z, c.z), f(a.w, b.w, c.w);
+    }
+    for (size_t k = (size_t)lo + 4 * (size_t)nv + threadIdx.x; k < hi; k += BM_T) f(p[k], t[k], m ? m[k] : (unsigned char)1);
+}
+
+// What a workgroup of variant v of pair g sweeps, and which pixels are inside: (mask byte != 0 or unmasked variant) and
+// (target NaN or metric target < cutoff) — np.nan_to_num(target) < cutoff, strict; variant 0 of each half applies no cut-off test.
+struct et_view_t {
+    bm_src_t p, t;
+    et_msk_t m;
+    unsigned lo, hi;
+    float reg, clip, lo_d, cutoff;
+    bool cut;
+    __device__ __forceinline__ et_view_t(const float *const *preds, const float *const *targets, const unsigned char *const *masks, const et_args_t &a,
+                                         int w, int v, size_t g) {
+        const int c = v % (a.ncut + 1);
+        p = (bm_src_t)preds[g], t = (bm_src_t)targets[g];
+        m = v > a.ncut && masks ? (et_msk_t)masks[g] : (et_msk_t) nullptr;
+        et_range(a.npix, a.Ws, w, lo, hi);
+        reg = a.reg, clip = a.clip, lo_d = expf(-a.reg) * a.clip;
+        cut = c != 0, cutoff = c ? a.cut[c - 1] : 0.f;
+    }
+    // metric target of a pixel that is inside -> tm; nan: it has no ground truth
+    __device__ __forceinline__ bool inside(float tn, unsigned char mv, float &tm, bool &nan) const {
+        nan = !(tn == tn);
+        tm = et_metric_depth(tn, reg, clip, lo_d, false);
+        return mv != 0 && (!cut || nan || tm < cutoff);
+    }
+    __device__ __forceinline__ float pred(float pn) const { return et_metric_depth(pn, reg, clip, lo_d, true); }
+};
+
+__device__ __forceinline__ unsigned et_key(float x) { return __float_as_uint(x) & 0x7fffffffu; }     // (a sign bit cannot leave the histogram)
+
+// Stores the marked histograms of the workgroup to its slab (histogram h at h * nbins) and takes the ticket of (pair, variant).
+__device__ __forceinline__ bool et_arrive(unsigned (*hist)[BM_BINS / 2], unsigned hmask, unsigned *slab, size_t cell, int P, int wg,
+                                          unsigned *tickets, int *flag) {
+    constexpr int NB = BM_BINS / 2;
+    for (int h = 0; h < 4; ++h)
+        if ((hmask >> h) & 1u)
+            for (int b = threadIdx.x; b < NB; b += BM_T) slab[(cell * P + wg) * ET_SLAB + h * NB + b] = hist[h][b];
+    return bm_ticket(cell, P, tickets, flag);
+}
+
+__global__ void __launch_bounds__(BM_T) et_sums_kernel(const float *const *__restrict__ preds, const float *const *__restrict__ targets,
+                                                       const unsigned char *const *__restrict__ masks, et_args_t a, unsigned *tickets, unsigned *state,
+                                                       double *part, unsigned *slab, double *__restrict__ out) {
+    __shared__ unsigned hist[2][BM_BINS];
+    __shared__ double red[ET_COLS][BM_T / 64], stage[ET_MAX_PER_MAP * ET_ROW];
+    __shared__ unsigned scan[BM_T / 64], res[2];
+    __shared__ int flag;
+    const int w = blockIdx.x, v = blockIdx.y, P = a.Ws;
+    const size_t g = blockIdx.z, cell = g * a.V + v;
+    unsigned *const both = &hist[0][0];
+    for (int b = threadIdx.x; b < 2 * BM_BINS; b += BM_T) both[b] = 0;
+    __syncthreads();
+    const et_view_t vw(preds, targets, masks, a, w, v, g);
+    double acc[ET_COLS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    unsigned nmask = 0, n = 0;
+    const double eps = 1e-5;
+    et_sweep(vw.p, vw.t, vw.m, vw.lo, vw.hi, [&](float pn, float tn, unsigned char mv) {
+        float t;
+        bool nan;
+        if (!vw.inside(tn, mv, t, nan)) return;
+        ++nmask;
+        if (nan) return;
+        const float p = vw.pred(pn);
+        const double d = (double)t - (double)p, ld = log((double)t + eps) - log((double)p + eps);
+        ++n;
+        acc[2] += fabs(d) / ((double)t + 1e-6), acc[3] += d * d / ((double)t * t + 1e-6), acc[4] += d * d;
+        acc[5] += ld * ld, acc[6] += fabs(ld), acc[7] += fabs(d);
+        const double r = fmax((double)t / ((double)p + eps), (double)p / ((double)t + eps));
+        acc[8] += r <= 1.25, acc[9] += r <= 1.5625, acc[10] += r <= 1.953125;
+        atomicAdd(&hist[0][et_key(t) >> 20], 1u);
+        atomicAdd(&hist[1][et_key(p) >> 20], 1u);
+    });
+    acc[0] = (double)nmask, acc[1] = (double)n;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < ET_COLS; ++k) {
+        const double s = bm_wave_sum(acc[k]);
+        if (lane == 0) red[k][wave] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < ET_COLS) {
+        double s = 0.0;
+        for (int i = 0; i < BM_T / 64; ++i) s += red[threadIdx.x][i];
+        part[(cell * P + w) * ET_ROW + threadIdx.x] = s;
+    }
+    for (int b = threadIdx.x; b < 2 * BM_BINS; b += BM_T) slab[(cell * P + w) * ET_SLAB + b] = both[b];
+    if (!bm_ticket(cell, P, tickets, &flag)) return;
+
+    // last arrival of (pair, variant): the P <= 32 rows through LDS, one thread per column adds them in index order
+    const double *rows = part + cell * P * ET_ROW;
+    for (int i = threadIdx.x; i < P * ET_ROW; i += BM_T) stage[i] = bm_ld(rows + i);
+    __syncthreads();
+    if (threadIdx.x < ET_COLS) {
+        double s = 0.0;
+        for (int r = 0; r < P; ++r) s += stage[r * ET_ROW + threadIdx.x];
+        red[threadIdx.x][0] = s;
+        out[cell * ET_OUT + threadIdx.x] = s;
+    } else if (threadIdx.x < ET_OUT) {
+        out[cell * ET_OUT + threadIdx.x] = threadIdx.x < 13 ? (double)__uint_as_float(0x7fc00000u) : 0.0;      // (pass 3 writes the medians it finds)
+    }
+    __syncthreads();
+    const unsigned total = (unsigned)red[1][0];
+    const bool wanted = total != 0 && red[0][0] == red[1][0];
+    unsigned *st = state + cell * ET_STATE;
+    if (wanted) {
+        const unsigned r0 = (total - 1) / 2, r1 = total / 2;
+        for (int s = 0; s < 2; ++s) {
+            bm_join_slabs<BM_BINS, ET_SLAB, BM_BINS>(slab, cell, P, s, hist[0]);
+            bm_select(hist[0], BM_BINS, r0, scan, res);
+            if (threadIdx.x == 0) st[4 * s] = res[0], st[4 * s + 1] = res[1];
+            bm_select(hist[0], BM_BINS, r1, scan, res);
+            if (threadIdx.x == 0) st[4 * s + 2] = res[0], st[4 * s + 3] = res[1];
+        }
+    }
+    if (threadIdx.x == 0) {
+        st[8] = total, st[9] = wanted ? 1u : 0u;
+        atomicExch(tickets + cell, 0u);                           // ready for the next pass
+    }
+}
+
+template <int SHIFT>
+__global__ void __launch_bounds__(BM_T) et_select_kernel(const float *const *__restrict__ preds, const float *const *__restrict__ targets,
+                                                         const unsigned char *const *__restrict__ masks, et_args_t a, unsigned *tickets, unsigned *state,
+                                                         unsigned *slab, double *__restrict__ out) {
+    constexpr int NB = BM_BINS / 2;
+    __shared__ unsigned hist[4][NB];
+    __shared__ unsigned scan[BM_T / 64], res[2];
+    __shared__ int flag;
+    const int w = blockIdx.x, v = blockIdx.y, P = a.Ws;
+    const size_t g = blockIdx.z, cell = g * a.V + v;
+    unsigned *st = state + cell * ET_STATE;
+    if (st[9] == 0) return;                                       // NaN medians: written by pass 1, no ticket is taken
+    unsigned pre[4], rank[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pre[k] = st[2 * k], rank[k] = st[2 * k + 1];
+    const unsigned total = st[8];
+    const bool two_t = pre[0] != pre[1], two_p = pre[2] != pre[3];
+    for (int h = 0; h < 4; ++h)
+        for (int b = threadIdx.x; b < NB; b += BM_T) hist[h][b] = 0;
+    __syncthreads();
+    const et_view_t vw(preds, targets, masks, a, w, v, g);
+    et_sweep(vw.p, vw.t, vw.m, vw.lo, vw.hi, [&](float pn, float tn, unsigned char mv) {
+        float t;
+        bool nan;
+        if (!vw.inside(tn, mv, t, nan) || nan) return;
+        const unsigned kt = et_key(t), kp = et_key(vw.pred(pn));
+        const unsigned tt = kt >> (SHIFT + 10), tp = kp >> (SHIFT + 10);
+        if (tt == pre[0]) atomicAdd(&hist[0][(kt >> SHIFT) & (NB - 1)], 1u);
+        else if (tt == pre[1]) atomicAdd(&hist[1][(kt >> SHIFT) & (NB - 1)], 1u);
+        if (tp == pre[2]) atomicAdd(&hist[2][(kp >> SHIFT) & (NB - 1)], 1u);
+        else if (tp == pre[3]) atomicAdd(&hist[3][(kp >> SHIFT) & (NB - 1)], 1u);
+    });
+    __syncthreads();
+    if (!et_arrive(hist, 1u | (two_t ? 2u : 0u) | 4u | (two_p ? 8u : 0u), slab, cell, P, w, tickets, &flag)) return;
+
+    unsigned found[4], inside[4];
+    for (int s = 0; s < 2; ++s) {
+        const bool two = s ? two_p : two_t;
+        bm_join_slabs<NB, ET_SLAB, NB>(slab, cell, P, 2 * s, hist[0]);
+        bm_select(hist[0], NB, rank[2 * s], scan, res);
+        found[2 * s] = (pre[2 * s] << 10) | res[0], inside[2 * s] = res[1];
+        __syncthreads();
+        if (two) bm_join_slabs<NB, ET_SLAB, NB>(slab, cell, P, 2 * s + 1, hist[0]);
+        bm_select(hist[0], NB, rank[2 * s + 1], scan, res);
+        found[2 * s + 1] = (pre[2 * s + 1] << 10) | res[0], inside[2 * s + 1] = res[1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        if (SHIFT) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) st[2 * k] = found[k], st[2 * k + 1] = inside[k];
+        } else {
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const float fa = __uint_as_float(found[2 * s]), fb = __uint_as_float(found[2 * s + 1]);
+                out[cell * ET_OUT + 11 + s] = (double)((total & 1u) ? fa : (fa + fb) * 0.5f);
+            }
+        }
+        atomicExch(tickets + cell, 0u);
+    }
+}
+
+__global__ void __launch_bounds__(256) metric_depth_kernel(const float *__restrict__ y, size_t n, float clip, float reg, int clamp, float *__restrict__ out) {
+    const float lo = expf(-reg) * clip;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        out[i] = et_metric_depth(y[i], reg, clip, lo, clamp != 0);
+}
+
+}  // namespace ramnet
+
+extern "C" int ramnet_metric_depth(const float *y, size_t n, float clip_distance, float reg_factor, int clamp, float *out, void *stream) {
+    RAMNET_CHECK_ARG(y && out && n > 0 && clip_distance > 0.f);
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(metric_depth_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, (hipStream_t)stream, y, n, clip_distance,
+                       reg_factor, clamp, out);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t ramnet_eval_table_workspace(int G, size_t npix, int ncut, int has_mask) {
+    return et_sizes_ok(G, npix, ncut, has_mask) ? et_plan(G, npix, ncut, has_mask).total : 0;
+}
+
+extern "C" int ramnet_eval_table(const float *const *pred, const float *const *target, const unsigned char *const *mask, int G, size_t npix,
+                                 float clip_distance, float reg_factor, const float *cutoffs, int ncut, void *workspace, double *out, void *stream) {
+    RAMNET_CHECK_ARG(pred && target && workspace && out && clip_distance > 0.f);
+    RAMNET_CHECK_ARG(et_sizes_ok(G, npix, ncut, mask != nullptr));
+    RAMNET_CHECK_ARG(ncut == 0 || cutoffs);
+    for (int i = 0; i < ncut; ++i) RAMNET_CHECK_ARG(cutoffs[i] > (i ? cutoffs[i - 1] : 0.f));
+    RAMNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0);
+    const et_plan_t pl = et_plan(G, npix, ncut, mask != nullptr);
+    et_args_t a;
+    a.clip = clip_distance, a.reg = reg_factor, a.ncut = ncut, a.V = pl.V, a.Ws = pl.Ws, a.npix = (unsigned)npix;
+    for (int i = 0; i < ET_MAXCUT; ++i) a.cut[i] = i < ncut ? cutoffs[i] : 0.f;
+    char *ws = static_cast<char *>(workspace);
+    unsigned *tickets = reinterpret_cast<unsigned *>(ws), *state = reinterpret_cast<unsigned *>(ws + pl.off_state);
+    double *part = reinterpret_cast<double *>(ws + pl.off_part);
+    unsigned *slab = reinterpret_cast<unsigned *>(ws + pl.off_slab);
+    const dim3 grid(pl.Ws, pl.V, G);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(et_sums_kernel, grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, part, slab, out);
+    hipLaunchKernelGGL(et_select_kernel<10>, grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, slab, out);
+    hipLaunchKernelGGL(et_select_kernel<0>, grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, slab, out);
+    RAMNET_LAUNCH_CHECK();
+    note_kernel("et_sums_kernel + et_select_kernel<10> + et_select_kernel<0>");
     return 0;
 }

@@ -16,7 +16,7 @@ from os.path import join
 import numpy as np
 import torch
 
-from .metrics import depth_metrics
+from .metrics import EVAL_CUTOFFS, EvalTable, depth_metrics
 
 
 def empty_states(every_x_rgb_frame):
@@ -35,13 +35,18 @@ def _time_batched_ok(model):
 
 
 def stream_dataset(model, dataset, every_x_rgb_frame, output_folder=None, settle=2, calculate_scale=False,
-                   reg_factor=5.70378, clip_distance=1000.0, max_items=None, time_batched="auto"):
+                   reg_factor=5.70378, clip_distance=1000.0, max_items=None, time_batched="auto", table=None):
     """Run ``model`` over ``dataset`` (items ``(sequence, dataset_idx)``, sequence_length 1) the way test.py does and
     optionally write predictions / targets as .npy.  Returns {'items', 'saved', 'scale': (mean, min, max) or None}.
 
     time_batched ("auto" = whenever the model allows it): a data package IS one group of ``graph.TimeBatchedStream`` — its K event
     grids encode at batch K, its K + 1 decodes run as one chain, only the state updates are sequential — with the same outputs
-    bit for bit; False calls ``model(package, ...)`` as test.py:230-232 does."""
+    bit for bit; False calls ``model(package, ...)`` as test.py:230-232 does.
+
+    table: a dict prediction key -> ``metrics.EvalTable``, or True to create one per prediction key from ``clip_distance`` /
+    ``reg_factor``: every package past ``settle`` adds each prediction with its ``depth_<key>`` target to that key's table while it is
+    still on the device — no ``output_folder`` and no read-back inside the loop; the tables come back under ``info["tables"]``."""
+    tables = {} if table is True else table
     was_training = model.training
     model.eval()
     use_tb = _time_batched_ok(model) if time_batched == "auto" else bool(time_batched)
@@ -84,6 +89,13 @@ def stream_dataset(model, dataset, every_x_rgb_frame, output_folder=None, settle
                         os.makedirs(d, exist_ok=True)
                         np.save(join(d, 'frame_{:010d}.npy'.format(idx)), value[0].cpu().numpy())
                 saved += 1
+            if tables is not None and sequence_idx >= settle:
+                for key, img in preds.items():
+                    if key not in tables:
+                        if table is not True:
+                            continue
+                        tables[key] = EvalTable(clip_distance, reg_factor)
+                    tables[key].add([img[0]], [package['depth_' + key][0]])      # (launched now: img is a view of a static buffer)
             if calculate_scale:      # least-squares scale between metric prediction and target (test.py:365-378; last key wins there, too)
                 for key, img in preds.items():
                     p = np.exp(reg_factor * (img[0][0].cpu().numpy() - np.float32(1.0))) * clip_distance
@@ -93,8 +105,11 @@ def stream_dataset(model, dataset, every_x_rgb_frame, output_folder=None, settle
             sequence_idx += 1
             prev_dataset_idx = dataset_idx
     model.train(was_training)
-    return {"items": n, "saved": saved,
+    info = {"items": n, "saved": saved,
             "scale": (float(np.mean(scale)), float(np.min(scale)), float(np.max(scale))) if calculate_scale else None}
+    if tables is not None:
+        info["tables"] = tables
+    return info
 
 
 def evaluate_folders(predictions_dir, targets_dir, clip_distance, reg_factor, crop_ymax=None, prediction_offset=0,
@@ -122,5 +137,48 @@ def evaluate_folders(predictions_dir, targets_dir, clip_distance, reg_factor, cr
                     sums[pre + k] = sums.get(pre + k, 0.0) + v
             counts[pre] = counts.get(pre, 0) + 1
     out = {k: v / counts[k.split("_")[0] + "_" if k.split("_")[0].isdigit() else ""] for k, v in sums.items()}
+    out["files"] = len(p_files)
+    return out
+
+
+def evaluate_table(predictions_dir, targets_dir, clip_distance, reg_factor, crop_ymax=None, prediction_offset=0, target_offset=0,
+                   cutoffs=EVAL_CUTOFFS, event_masks_dir=None, batch_files=64, skip_empty=True, device="cuda:0"):
+    """evaluation.py:295-397 with the whole table on the device: the file pairing of ``evaluate_folders``, ``batch_files`` files at a time
+    into one ``metrics.EvalTable`` (three launches per batch, one read-back at the end), all ten metrics for all pixels and every cut-off.
+    event_masks_dir: the sorted ``*png`` event frames of that folder, from ``prediction_offset`` on, give the ``event_masked_*`` half of the
+    table (mask = ``sum(frame.astype(float32), -1) > 0``, cropped like the maps; evaluation.py:371-390).
+    skip_empty: ``evaluate_folders``' rule (True) or the reference's sum / number of files (False), see ``metrics.finish_eval_rows``."""
+    p_files = sorted(glob.glob(join(predictions_dir, '*.npy')))[prediction_offset:]
+    t_files = sorted(glob.glob(join(targets_dir, '*.npy')))[target_offset:]
+    assert len(p_files) > 0 and len(t_files) > 0
+    pairs = list(zip(p_files, t_files))
+    e_files = None
+    if event_masks_dir is not None:
+        from .data import _imread
+        e_files = sorted(glob.glob(join(event_masks_dir, '*png')))[prediction_offset:]
+        assert len(e_files) >= len(pairs), "%d event frames for %d file pairs" % (len(e_files), len(pairs))
+    tab = EvalTable(clip_distance, reg_factor, cutoffs)
+    for i0 in range(0, len(pairs), batch_files):
+        ps, ts, ms = [], [], []
+        for i in range(i0, min(i0 + batch_files, len(pairs))):
+            t, p = np.load(pairs[i][1])[0], np.load(pairs[i][0])[0]
+            if crop_ymax is not None:
+                t, p = t[:crop_ymax], p[:crop_ymax]
+            assert p.shape == t.shape
+            ps.append(p), ts.append(t)
+            if e_files is not None:
+                frame = _imread(e_files[i])
+                frame = frame[:crop_ymax] if crop_ymax is not None else frame
+                m = np.sum(frame.astype("float32").reshape(frame.shape[:2] + (-1,)), axis=-1) > 0
+                assert m.shape == t.shape
+                ms.append(m)
+        if len(set(p.shape for p in ps)) == 1:                      # one upload per batch
+            tab.add(torch.from_numpy(np.stack(ps)).to(device), torch.from_numpy(np.stack(ts)).to(device),
+                    torch.from_numpy(np.stack(ms)).to(device) if e_files is not None else None)
+        else:                                                       # (recordings of different resolution in one folder: one call per file)
+            for j in range(len(ps)):
+                tab.add(torch.from_numpy(ps[j][None]).to(device), torch.from_numpy(ts[j][None]).to(device),
+                        torch.from_numpy(ms[j][None]).to(device) if e_files is not None else None)
+    out = tab.result(skip_empty=skip_empty)
     out["files"] = len(p_files)
     return out

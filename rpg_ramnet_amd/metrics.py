@@ -7,10 +7,14 @@ reference's table, NaN behaviour included: `RMS_log` and `median_diff` are plain
 
 The TRAINING metrics (model/metric.py:8-54 through LSTMTrainer._eval_metrics, lstm_trainer.py:100-106) are different functions, on the
 normalised log-depth maps themselves: `batch_metrics` computes all of them for a whole list of (prediction, target) pairs in one HIP
-reduction (exact median included) and leaves the table on the device; `eval_metrics` is the one-pair drop-in for `_eval_metrics`."""
+reduction (exact median included) and leaves the table on the device; `eval_metrics` is the one-pair drop-in for `_eval_metrics`.
+
+`EvalTable` is the batched form of the evaluation table: all ten rows for any number of files, every depth cut-off and the event-masked
+half (evaluation.py:359-390) in three launches per batch, rows kept on the device, one read-back (`finish_eval_rows` is its host part)."""
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import _hip as H
@@ -157,3 +161,172 @@ def eval_metrics(pred, target, names=TRAIN_METRICS):
     if row[0] != row[1]:
         raise ValueError("eval_metrics: %d valid targets but %d valid |target - prediction|: the prediction is not finite" % (row[1], row[0]))
     return row[cols]
+
+
+# ------------------------------------------------------------------------------------------------ evaluation table (evaluation.py:295-397)
+EVAL_KEYS = ("abs_rel_diff", "squ_rel_diff", "RMS_linear", "RMS_log", "SILog", "mean_depth_error", "median_diff", "threshold_delta_1.25",
+             "threshold_delta_1.25^2", "threshold_delta_1.25^3")
+EVAL_CUTOFFS = (10, 20, 30, 80, 250, 500)       # depth_values of evaluation.py
+EVAL_ROW = 16           # doubles of a row of ramnet_eval_table (include/ramnet_hip.h lists the columns)
+EVAL_TICKET_BYTES = 262144   # RAMNET_EVAL_TABLE_TICKET_BYTES
+
+_eval_workspaces = {}   # (device index, raw stream) -> uint8 workspace of ramnet_eval_table (tickets zeroed once, at allocation)
+
+
+def metric_depth(y, clip_distance, reg_factor, clamp=False):
+    """Normalised log depth -> metric depth on the device, float32: exp(reg * (y - 1)) * clip, with clamp=True clipped to
+    [exp(-reg) * clip, clip] (the prediction side of prepare_depth_data, evaluation.py:74-96).  NaN stays NaN.  The evaluation table
+    converts with the same device function."""
+    if y.device.type != "cuda":
+        raise ValueError("metric_depth: the map must live on the GPU (no CPU fallback)")
+    x = y.detach().to(torch.float32).contiguous()
+    out = torch.empty_like(x)
+    if x.numel():
+        with torch.cuda.device(x.device):
+            H.check(H.lib().ramnet_metric_depth(_p(x), x.numel(), float(clip_distance), float(reg_factor), int(bool(clamp)), _p(out), _st()),
+                    "ramnet_metric_depth")
+    return out
+
+
+def eval_variant_prefixes(cutoffs, has_mask):
+    """Key prefixes of the variants in the order of a table row: "", "10_", ..., then "event_masked_", "event_masked_10_", ..."""
+    pre = [""] + ["%d_" % c for c in cutoffs]
+    return pre + ["event_masked_" + p for p in pre] if has_mask else pre
+
+
+def _eval_entries(rows):
+    """[F, V, 16] rows -> ([F, V, 10] table entries in the order of EVAL_KEYS, as depth_metrics forms them, [F, V] n)."""
+    r = np.asarray(rows, dtype=np.float64)
+    nmask, n = r[..., 0], r[..., 1]
+    with np.errstate(all="ignore"):
+        clean = n == nmask
+        msq = r[..., 5] / n
+        med = np.abs(r[..., 11].astype(np.float32) - r[..., 12].astype(np.float32)).astype(np.float64)
+        cols = [r[..., 2] / n, r[..., 3] / n, np.sqrt(r[..., 4] / n), np.where(clean, np.sqrt(msq), np.nan), msq - (r[..., 6] / n) ** 2,
+                r[..., 7] / n, np.where(clean, med, np.nan), r[..., 8] / nmask, r[..., 9] / nmask, r[..., 10] / nmask]
+    return np.stack(cols, axis=-1), n
+
+
+def eval_file_counts(rows, skip_empty=True):
+    """Files that count for each variant: [V].  skip_empty=True: those with a valid pixel inside the variant; False: all."""
+    r = np.asarray(rows)
+    return (r[..., 1] > 0).sum(axis=0) if skip_empty else np.full(r.shape[1], r.shape[0])
+
+
+def finish_eval_rows(rows, cutoffs, has_mask, skip_empty=True):
+    """Host part of the evaluation table, pure numpy: [F, V, 16] rows of ramnet_eval_table -> {"<variant prefix><metric>": mean over
+    files, "files": F}.  Per file and variant the ten entries are formed as depth_metrics forms them; median_diff is
+    abs(float32(median_t) - float32(median_p)); a variant without a pixel gives ten NaN, one with NaN targets only gives thresholds 0.0
+    and the rest NaN (what the reference's add_to_metrics returns on such masks).
+    skip_empty=True is evaluate_folders' rule: a file without a valid pixel in a variant does not count for that variant (a variant no
+    file counts for has no keys).  skip_empty=False is the reference's sum / number of files, NaN propagating (evaluation.py:393)."""
+    r = np.asarray(rows, dtype=np.float64)
+    prefixes = eval_variant_prefixes(cutoffs, has_mask)
+    if r.ndim != 3 or r.shape[1] != len(prefixes) or r.shape[2] != EVAL_ROW:
+        raise ValueError("finish_eval_rows: rows are [F, %d, %d], got %s" % (len(prefixes), EVAL_ROW, r.shape))
+    vals, n = _eval_entries(r)
+    out = {}
+    for v, pre in enumerate(prefixes):
+        keep = n[:, v] > 0 if skip_empty else np.ones(r.shape[0], bool)
+        if skip_empty and not keep.any():
+            continue
+        for k, name in enumerate(EVAL_KEYS):
+            out[pre + name] = float(sum(vals[keep, v, k].tolist()) / int(keep.sum())) if keep.any() else float("nan")
+    out["files"] = int(r.shape[0])
+    return out
+
+
+def _eval_maps(x, device, dtype, what):
+    """list of maps or a [G, 1, H, W] / [G, H, W] tensor -> (list of contiguous tensors that own what the kernel reads, shape of a map)"""
+    if torch.is_tensor(x):
+        if x.dim() == 4 and x.shape[1] == 1:
+            x = x[:, 0]
+        if x.dim() != 3:
+            raise ValueError("EvalTable.add: %s is a list of maps or a [G, 1, H, W] / [G, H, W] tensor, got %s" % (what, tuple(x.shape)))
+        x = list(x.detach().to(device=device, dtype=dtype, non_blocking=True).contiguous())
+        return x
+    return [None if m is None else m.detach().to(device=device, dtype=dtype, non_blocking=True).contiguous() for m in x]
+
+
+class EvalTable:
+    """The reference's evaluation table (evaluation.py:295-397) for any number of (prediction, target) pairs of normalised log depth, on
+    the device: all pixels, every depth cut-off, and the same under event masks when masks are given.  `add` launches
+    ramnet_eval_table for its maps at once and appends their rows to a device-side table without a synchronisation; `result` reads the
+    table back once and averages over the files on the host."""
+
+    def __init__(self, clip_distance, reg_factor, cutoffs=EVAL_CUTOFFS):
+        self.clip_distance, self.reg_factor = float(clip_distance), float(reg_factor)
+        self.cutoffs = tuple(cutoffs)
+        if len(self.cutoffs) > 8 or any(not b > a for a, b in zip((0,) + self.cutoffs, self.cutoffs)):
+            raise ValueError("EvalTable: at most 8 ascending positive cut-offs, got %r" % (self.cutoffs,))
+        self._cut = (C.c_float * max(len(self.cutoffs), 1))(*[float(c) for c in self.cutoffs])
+        self._chunks, self.has_mask = [], None
+
+    def __len__(self):
+        return sum(c.shape[0] for c in self._chunks)
+
+    def add(self, preds, targets, masks=None):
+        """preds / targets: lists of same-shape maps (targets may live on the host: moved once) or [G, 1, H, W] / [G, H, W] tensors;
+        masks: the same of uint8 / bool (non-zero = inside the event mask; a list entry may be None: all inside).  Enqueued on the
+        current stream for exactly these maps; no reference to them is kept (what had to be copied belongs to the stream-ordered allocator).
+        Returns the [G, V, 16] rows (device)."""
+        has_mask = masks is not None
+        if self.has_mask is None:
+            self.has_mask = has_mask
+        elif self.has_mask != has_mask:
+            raise ValueError("EvalTable.add: every call of one table comes with masks, or none does")
+        first = preds[0]
+        device = first.device
+        if device.type != "cuda":
+            raise ValueError("EvalTable.add: predictions must live on the GPU (no CPU fallback)")
+        with torch.cuda.device(device):
+            ps, ts = _eval_maps(preds, device, torch.float32, "preds"), _eval_maps(targets, device, torch.float32, "targets")
+            if has_mask:
+                ms = [m if m is None or m.dtype == torch.uint8 else (m if m.dtype == torch.bool else m != 0).view(torch.uint8)
+                      for m in _eval_maps(masks, device, None, "masks")]
+            else:
+                ms = []
+            G = len(ps)
+            if G == 0 or len(ts) != G or (has_mask and len(ms) != G):
+                raise ValueError("EvalTable.add: %d predictions, %d targets, %s masks" % (G, len(ts), len(ms) if has_mask else "no"))
+            npix = ps[0].numel()
+            for p, t in zip(ps, ts):
+                if p is None or t is None or p.numel() != npix or t.numel() != npix:
+                    raise ValueError("EvalTable.add: every prediction and target holds %d pixels" % npix)
+            for m in ms:
+                if m is not None and (m.numel() != npix or m.dtype != torch.uint8):
+                    raise ValueError("EvalTable.add: every mask holds %d uint8 / bool pixels" % npix)
+            L = H.lib()
+            nbytes = L.ramnet_eval_table_workspace(G, npix, len(self.cutoffs), int(has_mask))
+            if nbytes == 0:
+                raise ValueError("EvalTable.add: unsupported sizes G=%d npix=%d cut-offs=%d" % (G, npix, len(self.cutoffs)))
+            key = (device.index, _st().value or 0)
+            ws = _eval_workspaces.get(key)
+            if ws is None or ws.numel() < nbytes:
+                ws = torch.empty(nbytes, device=device, dtype=torch.uint8)
+                ws[:EVAL_TICKET_BYTES].zero_()
+                _eval_workspaces[key] = ws
+            ptrs = [p.data_ptr() for p in ps] + [t.data_ptr() for t in ts] + [0 if m is None else m.data_ptr() for m in ms]
+            tab = torch.empty((3, G), device=device, dtype=torch.int64)
+            host = (C.c_void_p * len(ptrs))(*ptrs)
+            H.check(L.ramnet_fill_pointer_table(C.c_void_p(tab.data_ptr()), host, len(ptrs), _st()), "ramnet_fill_pointer_table")
+            V = (1 + len(self.cutoffs)) * (2 if has_mask else 1)
+            out = torch.empty((G, V, EVAL_ROW), device=device, dtype=torch.float64)
+            H.check(L.ramnet_eval_table(C.c_void_p(tab[0].data_ptr()), C.c_void_p(tab[1].data_ptr()),
+                                        C.c_void_p(tab[2].data_ptr()) if has_mask else None, G, npix, self.clip_distance, self.reg_factor,
+                                        self._cut, len(self.cutoffs), C.c_void_p(ws.data_ptr()), C.c_void_p(out.data_ptr()), _st()),
+                    "ramnet_eval_table")
+        self._chunks.append(out)
+        return out
+
+    def rows(self):
+        """[F, V, 16] float64 on the device: one row per added pair and variant, in the order they were added."""
+        if not self._chunks:
+            raise ValueError("EvalTable: nothing was added")
+        if len(self._chunks) > 1:
+            self._chunks = [torch.cat(self._chunks, dim=0)]
+        return self._chunks[0]
+
+    def result(self, skip_empty=True):
+        """ONE read-back of the table, then finish_eval_rows."""
+        return finish_eval_rows(self.rows().cpu().numpy(), self.cutoffs, bool(self.has_mask), skip_empty=skip_empty)

@@ -379,6 +379,15 @@ int ramnet_pred_sigmoid_si_bwd(const float *x, int ldx, int C, const float *w, c
 int ramnet_pred_linear_fwd(const float *x, int ldx, int C, const float *w, const float *b, float *z, size_t npix, void *stream);
 int ramnet_pred_linear_bwd(const float *x, int ldx, int C, const float *w, const float *dz, float *dx, int lddx, float *dw, float *db,
                            size_t npix, void *stream);
+/* Data-gradient-only backward of the three forms above, for a prediction layer whose weight and bias are frozen (requires_grad == False): dx
+ * alone — no weight / bias partial sums, no tickets, no join, x read only for mask_x.  dx is bit for bit the dx of ramnet_pred_sigmoid_bwd /
+ * ramnet_pred_linear_bwd / ramnet_pred_sigmoid_si_bwd on the same operands (the same expressions).  C % 4 == 0, C <= 128, lddx % 4 == 0,
+ * lddx >= C; dy of the _si_ form may be NULL, its x only when mask_x == 0. */
+int ramnet_pred_sigmoid_dgrad(int C, const float *w, const float *y, const float *dy, float *dx, int lddx, size_t npix, void *stream);
+int ramnet_pred_linear_dgrad(int C, const float *w, const float *dz, float *dx, int lddx, size_t npix, void *stream);
+int ramnet_pred_sigmoid_si_dgrad(const float *x, int ldx, int C, const float *w, const float *y, const float *dy, size_t seg_pix, int nseg,
+                                 const float *const *targets, const double *stats, const float *gscale, float weight, float lambda,
+                                 float *dx, int lddx, int mask_x, void *stream);
 /* dx = dy * (y > 0) */
 int ramnet_relu_bwd(const float *dy, const float *y, float *dx, size_t n, void *stream);
 /* Folded upsample-conv (UpsampleConvLayer forward as four 4x4 parity convolutions of the LOW-resolution input):

@@ -594,6 +594,74 @@ __global__ void pred_sigmoid_si_bwd_kernel(const float *__restrict__ x, int ldx,
     }
 }
 
+// ------------------------------------------------------------------------------------------ prediction head, data gradient only
+// The layer's weight and bias are frozen (requires_grad == False) and only dx is wanted: dx = dz w with the dz of pred_sigmoid_bwd_kernel
+// (MODE 1; MODE 0: the linear layer, dz = dy) or of pred_sigmoid_si_bwd_kernel (MODE 2) — the SAME expressions, so the same bits — and nothing
+// else: no x (unless its ReLU mask is asked for), no partial rows, no tickets, no join.  A plain HBM-bound write stream: a workgroup owns a
+// contiguous run of `chunk` pixels of one segment and addresses its dx (and x) rows through buffer resources over exactly that run, so an offset
+// past the run is dropped by the range check; 8 lanes per pixel row, a wavefront store covers 8 neighbouring rows (1 KiB at 32 channels).
+template <int MODE>
+__global__ void __launch_bounds__(256) pred_dgrad_kernel(const float *__restrict__ w, int C, const float *__restrict__ y, const float *__restrict__ dy,
+                                                         PredSiTargets tg, const double *__restrict__ stats, const float *__restrict__ gscale,
+                                                         float weight, float lambda, const float *__restrict__ x, int ldx, int mask_x,
+                                                         float *__restrict__ dx, int lddx, size_t seg_pix, size_t chunk) {
+    const int sub = threadIdx.x & 7, slot = threadIdx.x >> 3, seg = blockIdx.y;
+    const size_t start = blockIdx.x * chunk;
+    if (start >= seg_pix) return;
+    const size_t n = seg_pix - start < chunk ? seg_pix - start : chunk, base = (size_t)seg * seg_pix + start;
+    const auto drs = wino_rsrc(dx + base * lddx, (unsigned)(((n - 1) * lddx + C) * 4));
+    const bool masked = MODE == 2 && mask_x != 0;
+    const auto xrs = wino_rsrc(masked ? x + base * ldx : nullptr, masked ? (unsigned)(((n - 1) * ldx + C) * 4) : 0u);
+    const float *__restrict__ tgt = MODE == 2 ? tg.t[seg] + start : nullptr;
+    double s2 = 0.0, lm = 0.0;
+    if (MODE == 2) {
+        const double cnt = stats[seg * 4 + 2], mean = stats[seg * 4] / cnt;
+        s2 = 2.0 * (double)(gscale[seg] * weight) / cnt, lm = (double)lambda * mean;
+    }
+    float4 ww[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ww[k] = sub * 4 + 32 * k < C ? ld4(w + sub * 4 + 32 * k) : f4zero();      // C <= 128
+    // four pixels per trip and lane group: their scalar loads are issued back to back, then 4 x C / 32 row stores
+    for (size_t p0 = slot; p0 < n; p0 += 4 * 32) {
+        float dz[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const size_t p = p0 + u * 32, pix = base + p;
+            const bool ok = p < n;
+            if (MODE == 0) {
+                dz[u] = ok ? dy[pix] : 0.f;
+            } else if (MODE == 1) {
+                const float yy = ok ? y[pix] : 0.f;
+                dz[u] = ok ? dy[pix] * yy * (1.0f - yy) : 0.f;
+            } else {
+                const float yy = ok ? y[pix] : 0.f;
+                const float d = ok ? yy - tgt[p] : 0.f;
+                float g = (ok && dy) ? dy[pix] : 0.f;
+                if (ok && d == d) g += (float)(s2 * ((double)d - lm));
+                dz[u] = g * yy * (1.0f - yy);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const size_t p = p0 + u * 32;
+            if (p >= n) break;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int c = sub * 4 + 32 * k;
+                if (c < C) {
+                    float4 g = f4scale(ww[k], dz[u]);
+                    if (masked) {
+                        const float4 xv = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(xrs, (int)((p * ldx + c) * 4), 0, 0));
+                        g.x = xv.x > 0.f ? g.x : 0.f, g.y = xv.y > 0.f ? g.y : 0.f, g.z = xv.z > 0.f ? g.z : 0.f, g.w = xv.w > 0.f ? g.w : 0.f;
+                    }
+                    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, g), drs, (int)((p * lddx + c) * 4), 0, 0);
+                }
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------ upsample adjoint
 __device__ __forceinline__ float up2x_weight(int dst, int src, int n_src) {
     int i0, i1;
@@ -1186,6 +1254,48 @@ extern "C" int ramnet_pred_linear_bwd(const float *x, int ldx, int C, const floa
                                       size_t npix, void *stream) {
     RAMNET_CHECK_ARG(x && w && dz && dw && C > 0 && C % 4 == 0 && C <= 128 && ldx % 4 == 0);
     return pred_bwd(x, ldx, C, w, nullptr, dz, dx, lddx, dw, db, npix, stream);
+}
+
+// data-gradient-only forms (pred_dgrad_kernel): a workgroup owns `chunk` consecutive pixels of a segment, a multiple of the 128 pixels of a
+// trip, at most what a buffer resource's 32-bit byte offset reaches over rows of max(ldx, lddx) floats
+template <int MODE>
+static int pred_dgrad(const float *x, int ldx, int C, const float *w, const float *y, const float *dy, size_t seg_pix, int nseg,
+                      const float *const *targets, const double *stats, const float *gscale, float weight, float lambda, float *dx, int lddx,
+                      int mask_x, void *stream) {
+    RAMNET_CHECK_ARG(w && dx && C > 0 && C % 4 == 0 && C <= 128 && lddx % 4 == 0 && lddx >= C && seg_pix > 0);
+    RAMNET_CHECK_ARG(nseg >= 1 && nseg <= RAMNET_PRED_SI_MAX_SEGMENTS);
+    if (mask_x) RAMNET_CHECK_ARG(x && ldx % 4 == 0 && ldx >= C);
+    PredSiTargets tg;
+    for (int i = 0; i < RAMNET_PRED_SI_MAX_SEGMENTS; ++i) tg.t[i] = (targets && i < nseg) ? targets[i] : nullptr;
+    if (MODE == 2)
+        for (int i = 0; i < nseg; ++i) RAMNET_CHECK_ARG(tg.t[i] != nullptr);
+    size_t g = (size_t)grid_for(seg_pix * 8);
+    if (g > (size_t)(2048 / nseg)) g = (size_t)(2048 / nseg);
+    const size_t ldmax = (size_t)(mask_x && ldx > lddx ? ldx : lddx);
+    const size_t reach = ((size_t)0x7fffffff / (4 * ldmax)) / 128 * 128;
+    RAMNET_CHECK_ARG(reach >= 128);
+    size_t chunk = ((seg_pix + g - 1) / g + 127) / 128 * 128;
+    if (chunk > reach) chunk = reach;
+    g = (seg_pix + chunk - 1) / chunk;
+    RAMNET_CHECK_ARG(g <= 0x7fffffff);
+    hipLaunchKernelGGL(pred_dgrad_kernel<MODE>, dim3((unsigned)g, nseg), dim3(256), 0, (hipStream_t)stream, w, C, y, dy, tg, stats, gscale, weight,
+                       lambda, x, ldx, mask_x, dx, lddx, seg_pix, chunk);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int ramnet_pred_sigmoid_dgrad(int C, const float *w, const float *y, const float *dy, float *dx, int lddx, size_t npix, void *stream) {
+    RAMNET_CHECK_ARG(y && dy);
+    return pred_dgrad<1>(nullptr, 0, C, w, y, dy, npix, 1, nullptr, nullptr, nullptr, 0.f, 0.f, dx, lddx, 0, stream);
+}
+extern "C" int ramnet_pred_linear_dgrad(int C, const float *w, const float *dz, float *dx, int lddx, size_t npix, void *stream) {
+    RAMNET_CHECK_ARG(dz);
+    return pred_dgrad<0>(nullptr, 0, C, w, nullptr, dz, npix, 1, nullptr, nullptr, nullptr, 0.f, 0.f, dx, lddx, 0, stream);
+}
+extern "C" int ramnet_pred_sigmoid_si_dgrad(const float *x, int ldx, int C, const float *w, const float *y, const float *dy, size_t seg_pix, int nseg,
+                                            const float *const *targets, const double *stats, const float *gscale, float weight, float lambda,
+                                            float *dx, int lddx, int mask_x, void *stream) {
+    RAMNET_CHECK_ARG(y && targets && stats && gscale);
+    return pred_dgrad<2>(x, ldx, C, w, y, dy, seg_pix, nseg, targets, stats, gscale, weight, lambda, dx, lddx, mask_x, stream);
 }
 
 extern "C" int ramnet_upsample2x_bwd(const float *dup, float *dx, int B, int H, int W, int C, void *stream) {

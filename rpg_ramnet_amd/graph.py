@@ -531,6 +531,8 @@ class GraphedTrainStep:
                 reducer.zero(arm=False)          # (the collectives stay outside the graph: all_reduce() after the replay)
             else:
                 for p in model.parameters():
+                    if not p.requires_grad:      # frozen: no gradient tensor of ours (ops: its launches and folds are skipped)
+                        continue
                     if p.grad is None:
                         p.grad = torch.zeros_like(p)
                     else:
@@ -542,6 +544,8 @@ class GraphedTrainStep:
             total.backward()
             return total.detach(), reported
 
+        # which launches and folds the capture holds follows the parameters' requires_grad flags (partial training): baked in here
+        self.flags = tuple(p.requires_grad for p in model.parameters())
         _warm(run, warmup)
         torch.cuda.empty_cache()
         ops.invalidate_packs()            # every weight pack is re-run — and therefore recorded — inside the capture
@@ -568,6 +572,11 @@ class GraphedTrainStep:
 
     def __call__(self):
         """Replay; returns (differentiated loss, reported loss) as device scalars (static buffers)."""
+        flags = tuple(p.requires_grad for p in self.model.parameters())
+        if flags != self.flags:
+            changed = [n for (n, p), f in zip(self.model.named_parameters(), self.flags) if p.requires_grad != f]
+            raise RuntimeError("GraphedTrainStep: requires_grad of %s changed since the capture; the graph holds the launches of the "
+                               "captured flags — build a new GraphedTrainStep" % ", ".join(changed[:4] + (["..."] if len(changed) > 4 else [])))
         self._attach()
         self.graph.replay()
         return self.total, self.reported

@@ -762,6 +762,9 @@ def get_finalize_hook():
 
 
 def ensure_grad(p):
+    """p.grad, created as zeros when missing.  Only for tensors that train: a frozen one (requires_grad == False) never gets a gradient
+    from this package — its launches and folds are skipped —, so a path that asks for one has been missed and fails here."""
+    assert p.requires_grad, "ensure_grad: a gradient was asked for a tensor with requires_grad == False (frozen)"
     if p.grad is None:
         p.grad = torch.zeros_like(p)
     return p.grad
@@ -1025,6 +1028,12 @@ class ConvParam:
     def bwd(self):
         return PackRef(self, 1)
 
+    def state_half(self):
+        """The state half of this recurrent-cell convolution over [x | h] (StateHalfConvParam), created once."""
+        if getattr(self, "_state_half", None) is None:
+            self._state_half = StateHalfConvParam(self)
+        return self._state_half
+
     def s2d(self):
         """3x3 view over the space-to-depth input of this 5x5 stride-2 convolution (S2DConvParam), created once."""
         if getattr(self, "_s2d", None) is None:
@@ -1114,10 +1123,15 @@ class ConvParam:
         launches' workspace + G^T dU G of the Winograd-domain launches: one launch (ramnet_fold_unpack_wgrad), which also zeroes the
         workspaces for the next pass."""
         w4, wr, wc = self._ws_fold
-        g = ensure_grad(self.weights[0])
         dU = self._ws_fold24 if getattr(self, "_fold24_used", False) else None
-        H.check(H.lib().ramnet_fold_unpack_wgrad(_p(w4), _p(dU), _p(wr), _p(wc), _p(g), self.Cout, self.Cin, self.CinWs, _st()),
-                "ramnet_fold_unpack_wgrad")
+        if self.weights[0].requires_grad:
+            g = ensure_grad(self.weights[0])
+            H.check(H.lib().ramnet_fold_unpack_wgrad(_p(w4), _p(dU), _p(wr), _p(wc), _p(g), self.Cout, self.Cin, self.CinWs, _st()),
+                    "ramnet_fold_unpack_wgrad")
+        else:       # frozen weight beside a trainable bias (they share the launches): nothing to fold, the workspaces start the next pass at zero
+            for t in (w4, dU, wr, wc):
+                if t is not None:
+                    _zero_later(t)
         self._fold24_used = False
         self._fold_used = False
 
@@ -1161,7 +1175,7 @@ class ConvParam:
         if self._ws_used:
             self._join_slabs()
         if not self._ws_used:
-            if self.biases[0] is not None and self.biases[0].shape[0] == self.Cout:
+            if self.biases[0] is not None and self.biases[0].shape[0] == self.Cout and self.biases[0].requires_grad:
                 ensure_grad(self.biases[0]).add_(self._bws[:self.Cout])
             _zero_later(self._bws)
             self._dirty = False
@@ -1169,8 +1183,12 @@ class ConvParam:
         off = 0
         for w, b in zip(self.weights, self.biases):
             n = w.shape[0]
-            g = ensure_grad(w)
-            if getattr(self._ws, "wino6", False):
+            # tensors that share the launch (a weight and its bias, the update and reset gates of a ConvGRU) may be frozen one by one
+            # (requires_grad == False, read live): the fold writes the trainable ones only
+            g = ensure_grad(w) if w.requires_grad else None
+            if g is None:
+                pass
+            elif getattr(self._ws, "wino6", False):
                 H.check(H.lib().ramnet_unpack_wgrad_wino2x4(_p(self._ws), _p(g), n, self.Cin, self.CinWs, self.Cout, off, _st()),
                         "ramnet_unpack_wgrad_wino2x4")
             elif getattr(self._ws, "wg_dsplit", False):
@@ -1182,7 +1200,7 @@ class ConvParam:
             else:
                 H.check(H.lib().ramnet_unpack_wgrad(_p(self._ws), _p(g), n, self.Cin, self.CinWs, self.Cout, off,
                                                     self.k, self.k, _st()), "ramnet_unpack_wgrad")
-            if b is not None and b.shape[0] == n:      # (transposed conv: bias has Cout_t entries, handled by its op)
+            if b is not None and b.shape[0] == n and b.requires_grad:      # (transposed conv: bias has Cout_t entries, handled by its op)
                 ensure_grad(b).add_(self._bws[off:off + n])
             off += n
         self._zero_ws()
@@ -1213,10 +1231,12 @@ class S2DConvParam(ConvParam):
 
     def finalize(self):
         w, b = self.parent.weights[0], self.parent.biases[0]
-        g3 = torch.zeros(self.Cout, self.Cin, 3, 3, device=w.device)
+        g3 = torch.zeros(self.Cout, self.Cin, 3, 3, device=w.device) if w.requires_grad else None
         L = H.lib()
         self._join_slabs()
-        if getattr(self._ws, "wino6", False):
+        if g3 is None:          # frozen weight beside a trainable bias: the bias sum below is all there is to fold
+            pass
+        elif getattr(self._ws, "wino6", False):
             H.check(L.ramnet_unpack_wgrad_wino2x4(_p(self._ws), _p(g3), self.Cout, self.Cin, self.CinWs, self.Cout, 0, _st()), "ramnet_unpack_wgrad_wino2x4")
         elif getattr(self._ws, "wg_dsplit", False):
             H.check(L.ramnet_unpack_wgrad_dsplit(_p(self._ws), _p(g3), self.Cout, self.Cin, self.CinWs, self.Cout, 0, _st()), "ramnet_unpack_wgrad_dsplit")
@@ -1224,11 +1244,59 @@ class S2DConvParam(ConvParam):
             H.check(L.ramnet_unpack_wgrad_wino(_p(self._ws), _p(g3), self.Cout, self.Cin, self.CinWs, self.Cout, 0, _st()), "ramnet_unpack_wgrad_wino")
         else:
             H.check(L.ramnet_unpack_wgrad(_p(self._ws), _p(g3), self.Cout, self.Cin, self.CinWs, self.Cout, 0, 3, 3, _st()), "ramnet_unpack_wgrad")
-        ensure_grad(w).add_(s2d_weights_adjoint(g3, self.parent.Cin))
-        if b is not None:
+        if g3 is not None:
+            ensure_grad(w).add_(s2d_weights_adjoint(g3, self.parent.Cin))
+        if b is not None and b.requires_grad:
             ensure_grad(b).add_(self._bws[:self.Cout])
         self._zero_ws()
         self._dirty = self._ws_used = False
+
+
+class StateHalfConvParam(ConvParam):
+    """Input channels C.. of a recurrent cell's 3x3 convolution over the concatenation [x | h] (Cin = 2C): the operand of a backward-data
+    launch that forms dh alone — `bwd()` packs the transposed weights with Cout = C — for a cell whose x needs no gradient (frozen encoder
+    in front of it).  Packs follow the parent's parameter versions; there is no gradient workspace: the weight gradient is the parent's."""
+
+    def __init__(self, parent):
+        assert parent.k == 3 and parent.Cin % 2 == 0
+        self.parent = parent
+        self.weights, self.biases, self.gates = parent.weights, parent.biases, parent.gates
+        self.Cout, self.Cin, self.k = parent.Cout, parent.Cin // 2, 3
+        self.CinWs = self.Cin
+        self._packs = {}
+        self._dirty = False
+        self._defer = []
+
+    def _cat_w(self):
+        return self.parent._cat_w()[:, self.Cin:].contiguous()
+
+    def grad_ws(self, wino_ok=False):
+        raise RuntimeError("StateHalfConvParam: backward-data operand only; the weight gradient belongs to the parent layer")
+
+    def finalize(self):
+        pass
+
+
+# Backward-data of a recurrent cell whose x needs no gradient: the launches form dh alone from the state half of the transposed weights
+# (half the output channels, written into dxh[..., C:] at ld 2C).  The ConvGRU then runs stage B as its own launch (RAMNET_EPI_GRU_BWD
+# tells the halves apart by Cout = 2C).  "auto": where it pays (launches of at least _STATE_HALF_MIN_PIX pixels; profiles/
+# partial_training_notes.md has the table), "off": full-width launches everywhere, "force": every cell (tests).
+_STATE_HALF = "auto"
+_STATE_HALF_MIN_PIX = 0
+
+
+def set_cell_state_half(mode, min_pix=None):
+    global _STATE_HALF, _STATE_HALF_MIN_PIX
+    assert mode in ("auto", "off", "force")
+    _STATE_HALF = mode
+    if min_pix is not None:
+        _STATE_HALF_MIN_PIX = int(min_pix)
+
+
+def _state_half_ok(want_x, npix, Cc):
+    if want_x or _STATE_HALF == "off" or Cc % 4:
+        return False
+    return _STATE_HALF == "force" or npix >= _STATE_HALF_MIN_PIX
 
 
 # ------------------------------------------------------------------------------------------------ operators
@@ -1496,6 +1564,21 @@ def _folded_upsample_dgrad(x, dy, y, cp):
     return dx
 
 
+class _ShapeOf:
+    """Stands in a backward pass for an input tensor of which the forward kept only shape and device: the weight gradient, its one
+    reader, is not formed (frozen layer)."""
+    __slots__ = ("shape", "device")
+
+    def __init__(self, t):
+        self.shape, self.device = t.shape, t.device
+
+
+def _wants(ctx, *idx):
+    """Does any of the Function's inputs `idx` (its weight / bias arguments) need a gradient?  Read per pass from ctx.needs_input_grad:
+    requires_grad of the parameters when the forward ran — nothing is cached on the layer."""
+    return any(ctx.needs_input_grad[i] for i in idx)
+
+
 class ConvAct(Function):
     """ConvLayer / UpsampleConvLayer (submodules.py:8-35, 69-97): [bilinear x2 of (x [+ skip])] -> KxK conv -> bias -> [ReLU]."""
 
@@ -1531,7 +1614,13 @@ class ConvAct(Function):
         # premask_ok: a caller that routes EVERY gradient of y through one fan-in (ops.TimeSplit / TimeFan) may have that fan-in apply the ReLU
         # mask and set premasked (premask_relu_feature): backward then reads dy as a plain operand
         ctx.premask_ok, ctx.premasked = bool(relu), False
-        ctx.save_for_backward(x, skip, y, xpad if _SAVE_XPAD else None)
+        # x and skip are read by the backward-weights launches alone: with weight and bias frozen the backward keeps their shape
+        # (and y only as the ReLU mask of the backward-data launch)
+        ctx.xmeta, ctx.has_skip = _ShapeOf(x), skip is not None
+        if _wants(ctx, 2, 3):
+            ctx.save_for_backward(x, skip, y, xpad if _SAVE_XPAD else None)
+        else:
+            ctx.save_for_backward(None, None, y if relu else None, None)
         return y
 
     @staticmethod
@@ -1540,46 +1629,51 @@ class ConvAct(Function):
         cp, stride, relu, up, mode = ctx.cp, ctx.stride, ctx.relu, ctx.up, ctx.mode
         relu = relu and not ctx.premasked           # (dy == dy * (y > 0) already)
         dy = dense(dy)
+        want_w = _wants(ctx, 2, 3)                  # weight and bias share the backward-weights launch: skipped when both are frozen
+        xs, has_skip = ctx.xmeta, ctx.has_skip      # (shape and device of x; x itself only with want_w)
         if ctx.s2d_fused:   # x is the full-resolution input; the kernels address its space-to-depth view
             sp = cp.s2d()
-            ws, bws = sp.grad_ws(wino_ok=True)
-            Hl, Wl = x.shape[1] // 2, x.shape[2] // 2
-            wgrad_side([x, dy, y], x, Taps.get("conv_s2d", 3, 1), dy, ws, cp.Cout, in_mode=H.IN_S2D, Hin=Hl, Win=Wl,
-                       gmask=y if relu else None, dbias=bws)
+            Hl, Wl = xs.shape[1] // 2, xs.shape[2] // 2
+            if want_w:
+                ws, bws = sp.grad_ws(wino_ok=True)
+                wgrad_side([x, dy, y], x, Taps.get("conv_s2d", 3, 1), dy, ws, cp.Cout, in_mode=H.IN_S2D, Hin=Hl, Win=Wl,
+                           gmask=y if relu else None, dbias=bws)
             dx = None
             if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
+                dx = torch.empty(xs.shape, device=xs.device)
                 conv_launch(dy, Taps.get("dgrad1_s2d", 3, 1), sp.bwd(), dx, sp.Cin, xm=y if relu else None,
-                            in_mode=H.IN_RELUMASK if relu else H.IN_PLAIN, Ho=Hl, Wo=Wl, out_s2d=x.shape[3])
+                            in_mode=H.IN_RELUMASK if relu else H.IN_PLAIN, Ho=Hl, Wo=Wl, out_s2d=xs.shape[3])
             return dx, None, None, None, None, None, None, None
         if ctx.s2d:         # x is the space-to-depth input saved by forward
             sp = cp.s2d()
-            ws, bws = sp.grad_ws(wino_ok=True)
-            wgrad_side([x, dy, y], x, Taps.get("conv_s2d", 3, 1), dy, ws, cp.Cout, gmask=y if relu else None, dbias=bws)
+            if want_w:
+                ws, bws = sp.grad_ws(wino_ok=True)
+                wgrad_side([x, dy, y], x, Taps.get("conv_s2d", 3, 1), dy, ws, cp.Cout, gmask=y if relu else None, dbias=bws)
             dx = None
             if ctx.needs_input_grad[0]:
-                gs = torch.empty_like(x)
+                gs = torch.empty(xs.shape, device=xs.device)
                 conv_launch(dy, Taps.get("dgrad1_s2d", 3, 1), sp.bwd(), gs, sp.Cin, xm=y if relu else None,
                             in_mode=H.IN_RELUMASK if relu else H.IN_PLAIN)
                 dx = _space_to_depth(gs, inverse=True)
             return dx, None, None, None, None, None, None, None
-        B, Hh, W, _ = x.shape
+        B, Hh, W, _ = xs.shape
         k, pad = cp.k, cp.k // 2
         Hin, Win = (2 * Hh, 2 * W) if up else (Hh, W)
-        if _fold_eligible(x, cp, k, stride, up):
+        if _fold_eligible(xs, cp, k, stride, up):
             dy = dy.contiguous()        # (no-op on the path: the folded kernels' point-wise helpers index dy densely)
-            _folded_upsample_wgrad(x, skip, dy, y if relu else None, cp, xpad)
-        else:
+            if want_w:
+                _folded_upsample_wgrad(x, skip, dy, y if relu else None, cp, xpad)
+        elif want_w:
             ws, bws = cp.grad_ws(wino_ok=(stride == 1 and k == 3 and pad == 1 and mode == H.IN_PLAIN))
             wgrad_side([x, skip, dy, y], x, Taps.get("conv", k, pad), dy, ws, cp.Cout, stride=stride, x1=skip, in_mode=mode,
                        Hin=Hin, Win=Win, gmask=y if relu else None, dbias=bws)
         dx = dskip = None
-        if (ctx.needs_input_grad[0] or (skip is not None and ctx.needs_input_grad[1])) and _fold_eligible(x, cp, k, stride, up) \
+        if (ctx.needs_input_grad[0] or (has_skip and ctx.needs_input_grad[1])) and _fold_eligible(xs, cp, k, stride, up) \
                 and _fold_dgrad_ok(B, Hin, Win, cp):
-            dx = _folded_upsample_dgrad(x, dy, y if relu else None, cp)
-            return dx, (dx if skip is not None else None), None, None, None, None, None, None
-        if ctx.needs_input_grad[0] or (skip is not None and ctx.needs_input_grad[1]):
-            gin = torch.empty(B, Hin, Win, cp.Cin, device=x.device)
+            dx = _folded_upsample_dgrad(xs, dy, y if relu else None, cp)
+            return dx, (dx if has_skip else None), None, None, None, None, None, None
+        if ctx.needs_input_grad[0] or (has_skip and ctx.needs_input_grad[1]):
+            gin = torch.empty(B, Hin, Win, cp.Cin, device=xs.device)
             gmode = H.IN_RELUMASK if relu else H.IN_PLAIN
             if stride == 1:
                 conv_launch(dy, Taps.get("dgrad1", k, pad), cp.bwd(), gin, cp.Cin, xm=y if relu else None, in_mode=gmode)
@@ -1588,11 +1682,11 @@ class ConvAct(Function):
                                   [(Taps.get("dgrad2", k, pad, py, px), (Hin - py + 1) // 2, (Win - px + 1) // 2, (2, 2, py, px))
                                    for py in range(2) for px in range(2)], xm=y if relu else None, in_mode=gmode)
             if up:
-                dx = torch.empty(B, Hh, W, cp.Cin, device=x.device)
+                dx = torch.empty(B, Hh, W, cp.Cin, device=xs.device)
                 H.check(H.lib().ramnet_upsample2x_bwd(_p(gin), _p(dx), B, Hh, W, cp.Cin, _st()), "ramnet_upsample2x_bwd")
             else:
                 dx = gin
-            dskip = dx if skip is not None else None
+            dskip = dx if has_skip else None
         return dx, dskip, None, None, None, None, None, None
 
 
@@ -1611,7 +1705,8 @@ class TConvAct(Function):
                                                for py in range(2) for px in range(2)], bias=cp.bias(),
                           epi=H.EPI_RELU if relu else H.EPI_LINEAR)
         ctx.cp, ctx.relu = cp, relu
-        ctx.save_for_backward(x, y)
+        ctx.xmeta = _ShapeOf(x)
+        ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, y)       # (x: read by the weight-gradient launch alone)
         return y
 
     @staticmethod
@@ -1619,18 +1714,20 @@ class TConvAct(Function):
         x, y = ctx.saved_tensors
         cp = ctx.cp
         dy = dense(dy)
-        B, Hh, W, Cx = x.shape
+        B, Hh, W, Cx = ctx.xmeta.shape
         taps = Taps.get("conv", 5, 2)
-        ws, _ = cp.grad_ws()
         mask, mode = (y, H.IN_RELUMASK) if ctx.relu else (None, H.IN_PLAIN)
-        # weight gradient of the stride-2 conv (input = masked dy, output gradient = x); bias gradient = sum of masked dy
-        wgrad_launch(dy, taps, x, ws, Cx, stride=2, xm=mask, in_mode=mode)
-        if cp.biases[0] is not None:
+        # weight gradient of the stride-2 conv (input = masked dy, output gradient = x); bias gradient = sum of masked dy: two launches
+        # of their own, each skipped when its tensor is frozen
+        if ctx.needs_input_grad[1]:
+            ws, _ = cp.grad_ws()
+            wgrad_launch(dy, taps, x, ws, Cx, stride=2, xm=mask, in_mode=mode)
+        if cp.biases[0] is not None and ctx.needs_input_grad[2]:
             dyc = dy.contiguous()
             H.check(H.lib().ramnet_bias_grad(_p(dyc), _p(mask), _p(ensure_grad(cp.biases[0])), B * 4 * Hh * W, cp.Cin, _st()), "bias_grad")
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty(B, Hh, W, Cx, device=x.device)
+            dx = torch.empty(B, Hh, W, Cx, device=ctx.xmeta.device)
             conv_launch(dy, taps, cp.fwd(), dx, Cx, stride=2, xm=mask, in_mode=mode)
         return dx, None, None, None, None
 
@@ -1645,7 +1742,7 @@ class ResConv(Function):
         y = torch.empty_like(res, memory_format=torch.contiguous_format)
         conv_launch(t, Taps.get("conv", 3, 1), cp.fwd(), y, cp.Cout, bias=cp.bias(), epi=H.EPI_RES_RELU, e0=res)
         ctx.cp = cp
-        ctx.save_for_backward(t, y)
+        ctx.save_for_backward(t if _wants(ctx, 2, 3) else None, y)      # (t: read by the backward-weights launch alone)
         return y
 
     @staticmethod
@@ -1655,12 +1752,16 @@ class ResConv(Function):
         dy = dense(dy).contiguous()
         dpre = torch.empty_like(y)
         H.check(H.lib().ramnet_relu_bwd(_p(dy), _p(y), _p(dpre), y.numel(), _st()), "ramnet_relu_bwd")
-        ws, bws = cp.grad_ws(wino_ok=True)
-        wgrad_side([t, dpre], t, Taps.get("conv", 3, 1), dpre, ws, cp.Cout, dbias=bws)
-        dt = torch.empty_like(t, memory_format=torch.contiguous_format)
-        conv_launch(dpre, Taps.get("dgrad1", 3, 1), cp.bwd(), dt, cp.Cin)
+        want_w = _wants(ctx, 2, 3)
+        if want_w:
+            ws, bws = cp.grad_ws(wino_ok=True)
+            wgrad_side([t, dpre], t, Taps.get("conv", 3, 1), dpre, ws, cp.Cout, dbias=bws)
+        dt = None
+        if ctx.needs_input_grad[0]:
+            dt = torch.empty_like(y, memory_format=torch.contiguous_format)       # (t has y's shape)
+            conv_launch(dpre, Taps.get("dgrad1", 3, 1), cp.bwd(), dt, cp.Cin)
         dres = dpre
-        if _USE_SIDE:       # autograd may accumulate IN PLACE into the tensor returned for the residual input while the side
+        if _USE_SIDE and want_w:       # autograd may accumulate IN PLACE into the tensor returned for the residual input while the side
             dres = torch.empty_like(y)      # stream still reads dpre: hand it a buffer of its own
             H.check(H.lib().ramnet_relu_bwd(_p(dy), _p(y), _p(dres), y.numel(), _st()), "ramnet_relu_bwd")
         return dt, dres, None, None, None
@@ -1719,7 +1820,9 @@ class NormAct(Function):
         dres = torch.empty_like(x) if ctx.has_res else None
         H.check(L.ramnet_norm_bwd(_p(dy), Cc, _p(y) if act else None, Cc, act, _p(x), Cc, _p(c[0]), _p(c[1]), _p(c[2]), _p(dx), Cc, _p(dres), Cc,
                                   groups, npix, Cc, _st()), "ramnet_norm_bwd")
-        return dx, (dgb[0] if dgb is not None else None), (dgb[1] if dgb is not None else None), dres, None, None, None, None, None, None
+        # (gamma / beta travel through autograd: a frozen one gets nothing; the running statistics of the forward move regardless, as torch's do)
+        return (dx, (dgb[0] if dgb is not None and ctx.needs_input_grad[1] else None),
+                (dgb[1] if dgb is not None and ctx.needs_input_grad[2] else None), dres, None, None, None, None, None, None)
 
 
 _ACT_CODE = {None: 0, "relu": 1, "sigmoid": 2}
@@ -1818,7 +1921,10 @@ class GRUCell(Function):
         ctx.cps = (cp_ur, cp_o)
         ctx.has_hr = hr is not None
         if need:
-            ctx.save_for_backward(*((x, h, ur, o, hr) if hr is not None else (x, h, ur, o)))
+            # x and h.r are read by the backward-weights launches alone (x: both layers', h.r: the candidate's): not kept for frozen gates
+            w_ur, w_o = _wants(ctx, 2, 3, 4, 5), _wants(ctx, 6, 7)
+            xs = x if (w_ur or w_o) else None
+            ctx.save_for_backward(*((xs, h, ur, o, hr if w_o else None) if hr is not None else (xs, h, ur, o)))
         return hn
 
     @staticmethod
@@ -1828,36 +1934,51 @@ class GRUCell(Function):
         else:
             (x, h, ur, o), hr = ctx.saved_tensors, None
         cp_ur, cp_o = ctx.cps
-        B, Hh, W, Cc = x.shape
+        B, Hh, W, Cc = h.shape
         npix = B * Hh * W
         dhn = dense(dhn)                  # the [.., C:] half of the next update's [dx | dh] is read in place (ld = 2C)
         L = H.lib()
+        # what this pass needs (ctx.needs_input_grad, per tensor): update and reset gate share cp_ur's launches; the gradient of the gates'
+        # pre-activation needs d(h.r), i.e. the candidate's backward-data launch, whether or not x or h want a gradient themselves
+        want_x, want_h = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_ur, want_o = _wants(ctx, 2, 3, 4, 5), _wants(ctx, 6, 7)
+        data = want_x or want_h
         dpo = torch.empty_like(o)
         dpur = torch.empty_like(ur)
-        dxh = torch.empty(B, Hh, W, 2 * Cc, device=x.device)       # [dx | dh]
+        dxh = torch.empty(B, Hh, W, 2 * Cc, device=h.device)       # [dx | dh]
         taps, tapsd = Taps.get("conv", 3, 1), Taps.get("dgrad1", 3, 1)
         # stage B (dpr = d(h.r) h r (1-r), dh = dh'(1-u) + d(h.r) r) in the epilogue of the launch that produces d(h.r): stage A leaves
         # dh'(1-u) in the [.., C:] half of dxh (RAMNET_EPI_GRU_BWD; a 64-channel output block must lie in one half)
-        fused = _GRU_BWD_FUSED and Cc % 64 == 0
+        half = (data or want_ur) and _state_half_ok(want_x, npix, Cc)      # x frozen out: dh alone, from the state half of the weights
+        fused = _GRU_BWD_FUSED and Cc % 64 == 0 and not half
         if fused:
             H.check(L.ramnet_gru_bwd_a2(_p(dhn), _p(ur), _p(o), _p(h), _p(dpo), _p(dpur), _p(dxh, Cc), npix, Cc, ld(dhn), 2 * Cc, _st()), "gru_bwd_a2")
         else:
             dhd = torch.empty_like(o)
             H.check(L.ramnet_gru_bwd_a(_p(dhn), _p(ur), _p(o), _p(h), _p(dpo), _p(dpur), _p(dhd), npix, Cc, ld(dhn), _st()), "gru_bwd_a")
-        ws, bws = cp_o.grad_ws(wino_ok=Cc % 32 == 0)
-        if hr is not None:
-            _wgrad_cell(cp_o, ws, [x, hr, dpo], x, taps, dpo, Cc, x1=hr, in_mode=H.IN_CAT, C1=Cc, dbias=bws)
-        else:
-            _wgrad_cell(cp_o, ws, [x, h, ur, dpo], x, taps, dpo, Cc, x1=h, xm=ur, xm_off=Cc, in_mode=H.IN_CAT_MUL, C1=Cc, dbias=bws)
-        if fused:
-            conv_launch(dpo, tapsd, cp_o.bwd(), dxh, 2 * Cc, epi=H.EPI_GRU_BWD, e0=ur, e1=h, o1=dpur)
-        else:
-            conv_launch(dpo, tapsd, cp_o.bwd(), dxh, 2 * Cc)
-            H.check(L.ramnet_gru_bwd_b(_p(dxh), _p(ur), _p(h), _p(dpur), _p(dhd), npix, Cc, _st()), "gru_bwd_b")
-        ws, bws = cp_ur.grad_ws(wino_ok=Cc % 32 == 0)
-        _wgrad_cell(cp_ur, ws, [x, h, dpur], x, taps, dpur, 2 * Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, dbias=bws)
-        conv_launch(dpur, tapsd, cp_ur.bwd(), dxh, 2 * Cc, beta=1.0)
-        return dxh[..., :Cc], dxh[..., Cc:], None, None, None, None, None, None, None, None, None, None
+        if want_o:
+            ws, bws = cp_o.grad_ws(wino_ok=Cc % 32 == 0)
+            if hr is not None:
+                _wgrad_cell(cp_o, ws, [x, hr, dpo], x, taps, dpo, Cc, x1=hr, in_mode=H.IN_CAT, C1=Cc, dbias=bws)
+            else:
+                _wgrad_cell(cp_o, ws, [x, h, ur, dpo], x, taps, dpo, Cc, x1=h, xm=ur, xm_off=Cc, in_mode=H.IN_CAT_MUL, C1=Cc, dbias=bws)
+        if data or want_ur:
+            if half:
+                conv_launch(dpo, tapsd, cp_o.state_half().bwd(), dxh, Cc, out_off=Cc)
+                H.check(L.ramnet_gru_bwd_b(_p(dxh), _p(ur), _p(h), _p(dpur), _p(dhd), npix, Cc, _st()), "gru_bwd_b")
+            elif fused:
+                conv_launch(dpo, tapsd, cp_o.bwd(), dxh, 2 * Cc, epi=H.EPI_GRU_BWD, e0=ur, e1=h, o1=dpur)
+            else:
+                conv_launch(dpo, tapsd, cp_o.bwd(), dxh, 2 * Cc)
+                H.check(L.ramnet_gru_bwd_b(_p(dxh), _p(ur), _p(h), _p(dpur), _p(dhd), npix, Cc, _st()), "gru_bwd_b")
+        if want_ur:
+            ws, bws = cp_ur.grad_ws(wino_ok=Cc % 32 == 0)
+            _wgrad_cell(cp_ur, ws, [x, h, dpur], x, taps, dpur, 2 * Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, dbias=bws)
+        if data and half:
+            conv_launch(dpur, tapsd, cp_ur.state_half().bwd(), dxh, Cc, out_off=Cc, beta=1.0)
+        elif data:
+            conv_launch(dpur, tapsd, cp_ur.bwd(), dxh, 2 * Cc, beta=1.0)
+        return (dxh[..., :Cc] if want_x else None), (dxh[..., Cc:] if want_h else None), None, None, None, None, None, None, None, None, None, None
 
 
 _TIME_BATCH = True
@@ -2055,29 +2176,42 @@ class LSTMCell(Function):
         ctx.cp = cp
         ctx.active = act
         if need:
-            ctx.save_for_backward(x, h, c, cn, gates)
+            ctx.save_for_backward(x if _wants(ctx, 3, 4) else None, h, c, cn, gates)       # (x: read by the backward-weights launch alone)
         return hn, cn
 
     @staticmethod
     def backward(ctx, dhn, dcn):
         x, h, c, cn, gates = ctx.saved_tensors
         cp = ctx.cp
-        B, Hh, W, Cc = x.shape
+        B, Hh, W, Cc = h.shape
         npix = B * Hh * W
         dhn = None if dhn is None else dense(dhn).contiguous()
         dcn = None if dcn is None else dense(dcn).contiguous()
         dpre = torch.empty_like(gates)
         dc = torch.empty_like(cn)
-        dxh = torch.empty(B, Hh, W, 2 * Cc, device=x.device)
+        dxh = torch.empty(B, Hh, W, 2 * Cc, device=h.device)
         if ctx.active is None:
             H.check(H.lib().ramnet_lstm_bwd(_p(gates), _p(c), _p(cn), _p(dhn), _p(dcn), _p(dpre), _p(dc), npix, Cc, _st()), "lstm_bwd")
         else:               # inactive samples: dh = dh' (left in dxh for the beta = 1 launch below), dc = dc', dpre = 0
             H.check(H.lib().ramnet_lstm_bwd_masked(_p(gates), _p(c), _p(cn), _p(dhn), _p(dcn), _p(ctx.active), _p(dpre), _p(dc), _p(dxh),
                                                    npix, Hh * W, Cc, _st()), "lstm_bwd_masked")
-        ws, bws = cp.grad_ws(wino_ok=x.shape[3] % 32 == 0)
-        wgrad_side([x, h, dpre], x, Taps.get("conv", 3, 1), dpre, ws, 4 * Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, dbias=bws)
-        conv_launch(dpre, Taps.get("dgrad1", 3, 1), cp.bwd(), dxh, 2 * Cc, beta=0.0 if ctx.active is None else 1.0)
-        return dxh[..., :Cc], dxh[..., Cc:], dc, None, None, None, None, None, None
+        want_x, want_h = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if _wants(ctx, 3, 4):       # weight and bias of the gates share the backward-weights launch
+            ws, bws = cp.grad_ws(wino_ok=Cc % 32 == 0)
+            wgrad_side([x, h, dpre], x, Taps.get("conv", 3, 1), dpre, ws, 4 * Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, dbias=bws)
+        if want_h and _state_half_ok(want_x, npix, Cc):      # x frozen out: dh alone, from the state half of the weights
+            conv_launch(dpre, Taps.get("dgrad1", 3, 1), cp.state_half().bwd(), dxh, Cc, out_off=Cc, beta=0.0 if ctx.active is None else 1.0)
+        elif want_x or want_h:
+            conv_launch(dpre, Taps.get("dgrad1", 3, 1), cp.bwd(), dxh, 2 * Cc, beta=0.0 if ctx.active is None else 1.0)
+        return (dxh[..., :Cc] if want_x else None), (dxh[..., Cc:] if want_h else None), dc, None, None, None, None, None, None
+
+
+def _pred_grads(ctx, w, b):
+    """(dw, db) operands of a prediction-layer backward launch that forms weight and bias sums together: the .grad of a trainable tensor,
+    a throw-away buffer for a frozen one beside it (b may be None: the layer has no bias)."""
+    dw = ensure_grad(w) if ctx.needs_input_grad[1] else torch.zeros_like(w)
+    db = None if b is None else (ensure_grad(b) if ctx.needs_input_grad[2] else torch.zeros_like(b))
+    return dw, db
 
 
 class PredSigmoid(Function):
@@ -2089,17 +2223,23 @@ class PredSigmoid(Function):
         B, Hh, W, Cc = x.shape
         y = torch.empty(B, 1, Hh, W, device=x.device)
         H.check(H.lib().ramnet_pred_sigmoid_fwd(_p(x), ld(x), Cc, _p(w.detach()), _p(b.detach()), _p(y), B * Hh * W, _st()), "pred_fwd")
-        ctx.save_for_backward(x, w, b, y)
+        ctx.xmeta = _ShapeOf(x)
+        ctx.save_for_backward(x if _wants(ctx, 1, 2) else None, w, b, y)       # (x: read for the weight gradient alone)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, w, b, y = ctx.saved_tensors
-        B, Hh, W, Cc = x.shape
+        B, Hh, W, Cc = ctx.xmeta.shape
         dy = dy.contiguous()
-        dx = torch.empty(B, Hh, W, Cc, device=x.device) if ctx.needs_input_grad[0] else None
+        dx = torch.empty(B, Hh, W, Cc, device=ctx.xmeta.device) if ctx.needs_input_grad[0] else None
+        if not _wants(ctx, 1, 2):      # the layer is frozen: the data gradient alone (no partial sums, no join)
+            if dx is not None:
+                H.check(H.lib().ramnet_pred_sigmoid_dgrad(Cc, _p(w.detach()), _p(y), _p(dy), _p(dx), Cc, B * Hh * W, _st()), "pred_dgrad")
+            return dx, None, None
+        dw, db = _pred_grads(ctx, w, b)
         H.check(H.lib().ramnet_pred_sigmoid_bwd(_p(x), ld(x), Cc, _p(w.detach()), _p(y), _p(dy), _p(dx), Cc,
-                                                _p(ensure_grad(w)), _p(ensure_grad(b)), B * Hh * W, _st()), "pred_bwd")
+                                                _p(dw), _p(db), B * Hh * W, _st()), "pred_bwd")
         return dx, None, None
 
 
@@ -2141,7 +2281,9 @@ class PredSigmoidSI(Function):
         arr = (C.c_void_p * n)(*[t.data_ptr() for t in tg])
         H.check(L.ramnet_pred_sigmoid_si_fwd(_p(x), ld(x), Cc, _p(w.detach()), _p(b.detach()), _p(y), seg_pix, n, arr, weight, n_lambda,
                                              _p(scratch), _p(stats), _p(loss), _st()), "pred_si_fwd")
-        ctx.save_for_backward(x, w, b, y, stats, scratch, *tg)      # (scratch: the backward launch joins its partial sums through it)
+        # (scratch: the backward launch joins its partial sums through it; x: read for the weight gradient and as the ReLU mask of dx)
+        ctx.xmeta = _ShapeOf(x)
+        ctx.save_for_backward(x if (_wants(ctx, 1, 2) or mask_x) else None, w, b, y, stats, scratch, *tg)
         ctx.meta = (weight, n_lambda, n, seg_pix, bool(mask_x))
         ctx.set_materialize_grads(False)
         return (y,) + tuple(loss[i] for i in range(n))
@@ -2151,19 +2293,26 @@ class PredSigmoidSI(Function):
         x, w, b, y, stats, scratch = ctx.saved_tensors[:6]
         tg = ctx.saved_tensors[6:]
         weight, n_lambda, n, seg_pix, mask_x = ctx.meta
-        B, Hh, W, Cc = x.shape
+        B, Hh, W, Cc = ctx.xmeta.shape
+        dev = ctx.xmeta.device
         dy = dy.contiguous() if dy is not None else None
         if all(g is None for g in dloss):
-            gs = torch.zeros(n, device=x.device)
+            gs = torch.zeros(n, device=dev)
         else:
-            gs = torch.stack([g.float().reshape(()) if g is not None else torch.zeros((), device=x.device) for g in dloss])
-        dx = torch.empty(B, Hh, W, Cc, device=x.device) if ctx.needs_input_grad[0] else None
+            gs = torch.stack([g.float().reshape(()) if g is not None else torch.zeros((), device=dev) for g in dloss])
+        dx = torch.empty(B, Hh, W, Cc, device=dev) if ctx.needs_input_grad[0] else None
         arr = (C.c_void_p * n)(*[t.data_ptr() for t in tg])
+        if not _wants(ctx, 1, 2):      # the layer is frozen: the data gradient alone (no partial sums, no tickets, no join)
+            if dx is not None:
+                H.check(H.lib().ramnet_pred_sigmoid_si_dgrad(_p(x), ld(x) if x is not None else 0, Cc, _p(w.detach()), _p(y), _p(dy), seg_pix, n, arr,
+                                                             _p(stats), _p(gs), weight, n_lambda, _p(dx), Cc, int(mask_x), _st()), "pred_si_dgrad")
+            return (dx, None, None, None, None, None) + (None,) * n
+        dw, db = _pred_grads(ctx, w, b)
         # the fixed-order join of the weight / bias partial sums runs through the forward's scratch; its layout follows the library options
         # ("pred_si_cap" / "pred_si_bwd_cap"): had they changed since the forward pass, fall back to the atomic form instead of a wrong layout
         join = scratch.numel() == H.lib().ramnet_pred_si_scratch_doubles(seg_pix, n)
         H.check(H.lib().ramnet_pred_sigmoid_si_bwd(_p(x), ld(x), Cc, _p(w.detach()), _p(y), _p(dy), seg_pix, n, arr, _p(stats), _p(gs), weight,
-                                                   n_lambda, _p(dx), Cc, _p(ensure_grad(w)), _p(ensure_grad(b)), _p(scratch) if join else None, int(mask_x), _st()), "pred_si_bwd")
+                                                   n_lambda, _p(dx), Cc, _p(dw), _p(db), _p(scratch) if join else None, int(mask_x), _st()), "pred_si_bwd")
         return (dx, None, None, None, None, None) + (None,) * n
 
 
@@ -2178,17 +2327,23 @@ class PredLinear(Function):
         z = torch.empty(B, Hh, W, 1, device=x.device)
         H.check(H.lib().ramnet_pred_linear_fwd(_p(x), ld(x), Cc, _p(w.detach()), _p(b.detach()) if b is not None else None, _p(z),
                                                B * Hh * W, _st()), "pred_linear_fwd")
-        ctx.save_for_backward(x, w, b)
+        ctx.xmeta = _ShapeOf(x)
+        ctx.save_for_backward(x if _wants(ctx, 1, 2) else None, w, b)       # (x: read for the weight gradient alone)
         return z
 
     @staticmethod
     def backward(ctx, dz):
         x, w, b = ctx.saved_tensors
-        B, Hh, W, Cc = x.shape
+        B, Hh, W, Cc = ctx.xmeta.shape
         dz = dz.contiguous()
-        dx = torch.empty(B, Hh, W, Cc, device=x.device) if ctx.needs_input_grad[0] else None
-        H.check(H.lib().ramnet_pred_linear_bwd(_p(x), ld(x), Cc, _p(w.detach()), _p(dz), _p(dx), Cc, _p(ensure_grad(w)),
-                                               _p(ensure_grad(b)) if b is not None else None, B * Hh * W, _st()), "pred_linear_bwd")
+        dx = torch.empty(B, Hh, W, Cc, device=ctx.xmeta.device) if ctx.needs_input_grad[0] else None
+        if not _wants(ctx, 1, 2):      # the layer is frozen: the data gradient alone
+            if dx is not None:
+                H.check(H.lib().ramnet_pred_linear_dgrad(Cc, _p(w.detach()), _p(dz), _p(dx), Cc, B * Hh * W, _st()), "pred_linear_dgrad")
+            return dx, None, None
+        dw, db = _pred_grads(ctx, w, b)
+        H.check(H.lib().ramnet_pred_linear_bwd(_p(x), ld(x), Cc, _p(w.detach()), _p(dz), _p(dx), Cc, _p(dw),
+                                               _p(db), B * Hh * W, _st()), "pred_linear_bwd")
         return dx, None, None
 
 

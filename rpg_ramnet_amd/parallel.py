@@ -25,6 +25,10 @@ class FlatGradReducer:
         fold (see the module text); False = everything in all_reduce()."""
         self.always_collective = bool(always_collective)
         self.params = [p for p in model.parameters() if p.requires_grad]
+        # the flat buffer, its views and the buckets cover the tensors trainable NOW; frozen ones (requires_grad == False) stay outside
+        # and get no .grad (ops skips their launches and folds).  Every rank's collectives are sized by this layout: zero() refuses a
+        # flag that changed since
+        self._flags = [(n, p, p.requires_grad) for n, p in model.named_parameters()]
         self.group = process_group
         dev = self.params[0].device
         total = sum(p.numel() for p in self.params)
@@ -96,6 +100,11 @@ class FlatGradReducer:
         the rank AVERAGE of pass 1 on every rank, so averaging (that + the local gradients of pass 2) gives avg 1 + avg 2.  For
         accumulation loops prefer zero(arm=False) and arm() right before the last backward: the overlap then goes to the pass that
         completes the gradients.  arm=False: the pass that follows is NOT a collective one: nothing may leave early."""
+        for n, p, f in self._flags:
+            if p.requires_grad != f:
+                raise RuntimeError("FlatGradReducer: requires_grad of %s changed from %s to %s since the reducer was built; its flat "
+                                   "buffer and buckets (what every rank's collectives are sized by) cover the tensors trainable at "
+                                   "construction — close() it and build a new one" % (n, f, p.requires_grad))
         if self._issued:                  # buckets of a pass whose all_reduce() never came: let them finish before the buffer is reused
             torch.cuda.current_stream().wait_stream(self.side)
             self._issued, self._pending = 0, None

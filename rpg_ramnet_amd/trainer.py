@@ -19,6 +19,44 @@ def empty_states_lstm(K):
     return d
 
 
+def freeze(model, patterns, train_only=False):
+    """Partial training by the ordinary idiom: sets requires_grad = False on parameters of `model` picked by `patterns`, fnmatch
+    patterns (a string or a list of them) over the names of model.named_parameters(), and returns the names it froze, in
+    registration order.  train_only=False: the matching tensors are frozen.  train_only=True: the patterns name what stays trainable
+    and EVERY OTHER tensor is frozen.  A pattern that matches no name raises KeyError (a typo must not train, or freeze, the whole
+    network silently).  Nothing is ever un-frozen here (`p.requires_grad_(True)` does that), so calls compose.  The operators read the
+    flags at every pass: a frozen tensor gets no .grad, its backward-weights launches and folds are skipped, and gradients still flow
+    through its layer ("Partial training")."""
+    import fnmatch
+    patterns = [patterns] if isinstance(patterns, str) else list(patterns)
+    named = list(model.named_parameters())
+    hit = set()
+    for pat in patterns:
+        m = [n for n, _ in named if fnmatch.fnmatchcase(n, pat)]
+        if not m:
+            raise KeyError("freeze: pattern %r matches no parameter name (e.g. %s)" % (pat, ", ".join(n for n, _ in named[:3])))
+        hit.update(m)
+    frozen = []
+    for n, p in named:
+        if (n in hit) != bool(train_only):
+            p.requires_grad_(False)
+            frozen.append(n)
+    return frozen
+
+
+def apply_freeze_config(model, config):
+    """The optional keys config['trainer']['freeze'] / config['trainer']['train_only'] (lists of patterns for `freeze`; absent = every
+    tensor trains): applied by the trainers BEFORE they build an optimizer — and to be called before a parallel.FlatGradReducer or a
+    graph.GraphedTrainStep is built, whose layouts follow the flags.  Idempotent.  Returns the frozen names."""
+    tr = config.get('trainer', {})
+    frozen = []
+    if tr.get('freeze'):
+        frozen += freeze(model, tr['freeze'])
+    if tr.get('train_only'):
+        frozen += freeze(model, tr['train_only'], train_only=True)
+    return frozen
+
+
 LOSS_SEMANTICS = {
     False: "per-rank mean over the rank's batch, gradients averaged over ranks (standard DDP)",
     True: "exact global batch: SI statistics (sum d, sum d^2, n per supervised map) all-reduced before the backward; the N-rank "
@@ -230,6 +268,9 @@ class EpochTrainer:
         self.model, self.config, self.train_epoch, self.reducer = model, config, train_epoch, reducer
         self.epochs = config['trainer']['epochs']
         self.save_freq = config['trainer']['save_freq']
+        # optional partial training (config['trainer']['freeze' | 'train_only']) BEFORE the optimizer exists; the optimizer still gets
+        # model.parameters() as the reference's does — it skips tensors without .grad, and checkpoints keep the reference layout
+        self.frozen = apply_freeze_config(model, config)
         self.optimizer = getattr(torch.optim, config['optimizer_type'])(model.parameters(), **config['optimizer'])
         sched = getattr(torch.optim.lr_scheduler, config.get('lr_scheduler_type', ''), None)
         self.lr_scheduler = sched(self.optimizer, **config['lr_scheduler']) if sched else None
@@ -293,7 +334,8 @@ class SequenceTrainer:
 
     config keys, read as the reference reads them: config['trainer']['num_previews' | 'num_val_previews' | 'loss_composition' |
     'loss_weights'], config['loss'] ('type', 'config'), optional config['grad_loss'] / config['mse_loss'], config['metrics'],
-    config['data_loader']['train']['every_x_rgb_frame'].
+    config['data_loader']['train']['every_x_rgb_frame'].  Not in the reference, optional: config['trainer']['freeze'] /
+    config['trainer']['train_only'] — lists of patterns for `freeze` (partial training), applied to the model here.
 
     Mirrored semantics.  Every entry of 'losses' carries the aliasing factor (`loss_parts`); an epoch value is the sum over the
     batches / len(loader).  'metrics' = sum over the preview sequences and over ALL prediction keys of the metrics of (prediction of
@@ -314,6 +356,7 @@ class SequenceTrainer:
         self.config, self.model, self.optimizer, self.reducer, self.group = config, model, optimizer, reducer, process_group
         self.data_loader, self.valid_data_loader = data_loader, valid_data_loader
         tr = config['trainer']
+        self.frozen = apply_freeze_config(model, config)       # optional tr['freeze'] / tr['train_only'] (before epoch_trainer() builds the optimizer)
         self.num_previews, self.num_val_previews = tr['num_previews'], tr['num_val_previews']
         self.loss_composition, self.loss_weights = tr['loss_composition'], tr['loss_weights']
         self.loss_type = config['loss']['type']

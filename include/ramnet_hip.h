@@ -444,7 +444,8 @@ int ramnet_bias_grad(const float *dy, const float *mask, float *db, size_t npix,
  * ramnet_norm_finalize: mean, rstd [groups][C] (fp64), scale = gamma * rstd, shift = beta - mean * scale (fp32; gamma / beta may be
  *   NULL = 1 / 0) from the partial sums — or, use_running != 0 (eval mode, groups = 1), from the running buffers.  update_running:
  *   running = (1 - momentum) * running + momentum * mean over the groups of (mean, UNBIASED variance), as torch's BatchNorm2d /
- *   InstanceNorm2d(track_running_stats=True) in training mode; num_batches_tracked (int64, may be NULL) += 1.
+ *   InstanceNorm2d(track_running_stats=True) in training mode; num_batches_tracked (int64, may be NULL) += 1.  With use_running
+ *   nothing is updated or counted, whatever update_running says (eval mode).
  * ramnet_norm_finalize_bwd: from the backward's partial sums: c1, c2, c3 [groups][C] of ramnet_norm_bwd (batch_stats = the forward
  *   normalised with the statistics of x itself; 0 = running statistics: c2 = c3 = 0), dgamma / dbeta [C] (=, may be NULL).
  * ramnet_norm_apply:   out = act(x * scale[g][c] + shift[g][c] [+ res]).
@@ -479,7 +480,8 @@ int ramnet_split2(const float *y, int ldy, int Ca, int Cb, float *a, float *b, s
 
 /* ---- scale-invariant loss: model/loss.py:6-9 -------------------------------------------------- */
 /* stats[0..2] = (sum d, sum d^2, count) over non-NaN d = pred - target; loss = w*(S2/n - lambda*(S1/n)^2).  `stats` holds FOUR
- * doubles ([3] is scratch of the reduction; the backward reads [0..2]).  One launch: every workgroup stores its partial sums to a
+ * doubles ([3] is scratch of the reduction: 0.0 after the one-launch form, an integer arrival count after the form used inside a capture,
+ * so only [0..2] are defined; the backward reads [0..2]).  One launch: every workgroup stores its partial sums to a
  * scratch the library owns per (device, stream), the last one to arrive adds them in a fixed order (bit-reproducible loss); inside a
  * stream capture that finds no scratch yet: zero-fill + atomics on `stats`.                                              */
 int ramnet_si_loss_fwd(const float *pred, const float *target, size_t n, float weight, float lambda,
@@ -493,14 +495,15 @@ int ramnet_si_loss_bwd(const float *pred, const float *target, size_t n, float w
                        const double *stats, const float *gscale, float *dpred, void *stream);
 
 /* scale_invariant_log_loss (model/loss.py:12-15): the same statistic on d = log(pred) - log(target) (no weight argument in the reference).
- * stats: 4 doubles as above (zeroed here).                                                                             */
+ * stats: 4 doubles as above; the same two forms of the reduction (one launch and bit-reproducible, zero-fill + atomics inside a capture). */
 int ramnet_si_log_loss_fwd(const float *pred, const float *target, size_t n, float lambda, double *stats, float *loss, void *stream);
 int ramnet_si_log_loss_bwd(const float *pred, const float *target, size_t n, float lambda, const double *stats, const float *gscale,
                            float *dpred, void *stream);
 /* mse_loss (model/loss.py:18-19) as the trainer's extra term uses it (lstm_trainer.py:169-185): mean squared error over the non-NaN
  * TARGET entries of [B][H][W] maps; half = 1: both maps first go through F.interpolate(scale_factor=0.5, 'bilinear', align_corners=False)
  * (2 x 2 block means; a NaN in a target block masks the cell; odd trailing rows / columns are dropped).  stats: 4 doubles
- * ([0] = sum d^2, [1] = count, zeroed here); dpred [B][H][W] = gscale * d loss / d pred (every element written).            */
+ * ([0] = sum d^2, [1] = count, zeroed here; [2] unused, [3] scratch of the reduction); dpred [B][H][W] = gscale * d loss / d pred
+ * (every element written).  half != 0 needs H >= 2 and W >= 2, in the forward and in the backward.                          */
 int ramnet_mse_loss_fwd(const float *pred, const float *target, int B, int H, int W, int half, double *stats, float *loss, void *stream);
 int ramnet_mse_loss_bwd(const float *pred, const float *target, int B, int H, int W, int half, const double *stats, const float *gscale,
                         float *dpred, void *stream);
@@ -531,8 +534,8 @@ int ramnet_voxel_indices(const double *events, size_t n_events, int bins, int W,
 int ramnet_normalize_nonzero(float *grid, size_t n, double *scratch, void *stream);
 /* Batched forms (one launch for the B x K grids of a batch of packages): event lists concatenated in `events`, list g =
  * rows offsets[g] .. offsets[g+1] (device int64 [n_grids+1]; each list sorted by t, normalised by ITS first / last stamp),
- * max_events = longest list; grids [n_grids][bins][H][W] (zeroed here).  normalize: n = bins*H*W (multiple of 4) per grid,
- * scratch = 3*n_grids doubles.  Same arithmetic per grid as the single-grid entry points.  Launches of >= 16 grids resolve the
+ * max_events = longest list; grids [n_grids][bins][H][W] (zeroed here).  normalize: n = bins*H*W (multiple of 4) per grid, `grids`
+ * 16-byte aligned (also for ramnet_nonzero_stats_batch), scratch = 3*n_grids doubles.  Same arithmetic per grid as the single-grid entry points.  Launches of >= 16 grids resolve the
  * votes in LDS row bands (no global atomics, no zero-fill pass); smaller ones scatter with global fp32 atomics.             */
 int ramnet_voxelize_batch(const double *events, const long long *offsets, int n_grids, size_t max_events, int bins, int W, int H,
                           float *grids, void *stream);

@@ -857,6 +857,13 @@ extern "C" int ramnet_si_log_loss_fwd(const float *pred, const float *target, si
     hipStream_t st = (hipStream_t)stream;
     int g = grid_for(n / 4 + 1, 1024);
     if (g > 256) g = 256;
+    if (double *part = si_scratch(st)) {             // as ramnet_si_loss_fwd: one launch, fixed-order join, bit-reproducible
+        if (g > 64) g = 64;
+        hipLaunchKernelGGL(si_stats_fold_kernel<true>, dim3(g), dim3(1024), 0, st, pred, target, n, 1.0f, lambda, stats, loss, part,
+                           reinterpret_cast<unsigned long long *>(part + 3 * 256));
+        RAMNET_LAUNCH_CHECK();
+        return 0;
+    }
     RAMNET_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(double), st));
     hipLaunchKernelGGL(si_stats_kernel<true>, dim3(g), dim3(1024), 0, st, pred, target, n, 1.0f, lambda, stats, loss);
     RAMNET_LAUNCH_CHECK();
@@ -886,7 +893,7 @@ extern "C" int ramnet_mse_loss_fwd(const float *pred, const float *target, int B
 
 extern "C" int ramnet_mse_loss_bwd(const float *pred, const float *target, int B, int H, int W, int half, const double *stats,
                                    const float *gscale, float *dpred, void *stream) {
-    RAMNET_CHECK_ARG(pred && target && stats && dpred && B > 0 && H > 0 && W > 0);
+    RAMNET_CHECK_ARG(pred && target && stats && dpred && B > 0 && H > 0 && W > 0 && (!half || (H >= 2 && W >= 2)));      // (as the forward)
     const size_t n = (size_t)B * H * W;
     if (half) hipLaunchKernelGGL(mse_bwd_kernel<true>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, pred, target, B, H, W, stats, gscale, dpred);
     else hipLaunchKernelGGL(mse_bwd_kernel<false>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, pred, target, B, H, W, stats, gscale, dpred);
@@ -1098,6 +1105,7 @@ extern "C" int ramnet_voxelize_batch(const double *events, const long long *offs
 
 extern "C" int ramnet_normalize_nonzero_batch(float *grids, int n_grids, size_t n, double *scratch, void *stream) {
     RAMNET_CHECK_ARG(grids && scratch && n > 0 && n % 4 == 0 && n_grids > 0 && n_grids <= 65535);
+    RAMNET_CHECK_ARG(((uintptr_t)grids & 15) == 0);      // 16-byte loads and stores: with n % 4 == 0 every grid then starts aligned
     hipStream_t st = (hipStream_t)stream;
     RAMNET_HIP(hipMemsetAsync(scratch, 0, (size_t)3 * n_grids * sizeof(double), st));
     int gx = (int)((n / 4 + 255) / 256);
@@ -1113,6 +1121,7 @@ extern "C" int ramnet_normalize_nonzero_batch(float *grids, int n_grids, size_t 
 // the values it reads.
 extern "C" int ramnet_nonzero_stats_batch(const float *grids, int n_grids, size_t n, double *stats, void *stream) {
     RAMNET_CHECK_ARG(grids && stats && n > 0 && n % 4 == 0 && n_grids > 0 && n_grids <= 65535);
+    RAMNET_CHECK_ARG(((uintptr_t)grids & 15) == 0);      // (16-byte loads)
     hipStream_t st = (hipStream_t)stream;
     RAMNET_HIP(hipMemsetAsync(stats, 0, (size_t)3 * n_grids * sizeof(double), st));
     int gx = (int)((n / 4 + 255) / 256);

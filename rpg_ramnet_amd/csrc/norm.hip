@@ -141,7 +141,7 @@ __global__ void norm_finalize_kernel(const double *__restrict__ part, int groups
     __shared__ double red[16][16][2];
     const int c = blockIdx.x * 16 + (threadIdx.x & 15), lane = threadIdx.x >> 4;
     const bool own = lane == 0 && c < C;
-    if (c == 0 && lane == 0 && tracked != nullptr && update) tracked[0] += 1;
+    if (c == 0 && lane == 0 && tracked != nullptr && update && !use_running) tracked[0] += 1;      // (eval mode does not count)
     const double ga = own && gamma ? (double)gamma[c] : 1.0, be = own && beta ? (double)beta[c] : 0.0;
     double am = 0.0, av = 0.0;
     for (int g = 0; g < groups; ++g) {

@@ -1,5 +1,5 @@
 """GPU: the launches that partial training adds (a frozen prediction layer, a cell behind a frozen encoder), each alone through the C ABI
-/ ops.conv_launch, in the manner of tests/test_hip_pointwise.py (its guarded buffers and its `call`).
+/ ops.conv_launch, in the manner of tests/test_hip_pointwise.py (the guarded buffers and the `call` of tests/guarded.py).
 
   ramnet_pred_sigmoid_dgrad / ramnet_pred_linear_dgrad / ramnet_pred_sigmoid_si_dgrad: dx EQUAL, bit for bit, to the dx of the launch
   that also forms the weight and bias gradients, on the same operands — it is the same expression per element.
@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from rpg_ramnet_amd import _hip
-from test_hip_pointwise import GUARD, SENT, In, Out, _bits, _dev, call, rn
+from guarded import GUARD, SENT, In, Out, _bits, _dev, call, rn
 
 pytestmark = pytest.mark.gpu
 

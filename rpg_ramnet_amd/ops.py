@@ -454,6 +454,31 @@ def _conv_desc_build(x0, taps, w, out, Cout, meta, *, stride=1, x1=None, xm=None
 
 _WDESC_CACHE = {}
 
+# Weight-gradient layouts of a backward pass: kind -> (one slab: a library query of (CinWs, Cout), or positions x CinWs x Cout with
+# 0 = the layer's k x k taps; slab-count query; unpack launch; launch algorithm).  direct: [tap][CinWs][Cout]; wino: F(2x2,3x3) domain
+# [16][CinWs][Cout] (csrc/conv_wgrad_wino.hip); wino6: F(2x4,3x3) blocked [24][Cin][Cout] (conv_wgrad_wino6.hip); dsplit: direct 3x3
+# on split bf16 operands [9][Cin][Cout] (conv_wgrad_dsplit.hip).
+_LAYOUTS = {
+    "direct": (0, None, "ramnet_unpack_wgrad", H.ALGO_DIRECT),
+    "wino": (16, "ramnet_wgrad_wino_slabs", "ramnet_unpack_wgrad_wino", H.ALGO_WINOGRAD),
+    "wino6": ("ramnet_wgrad_wino2x4_ws_floats", "ramnet_wgrad_wino2x4_slabs", "ramnet_unpack_wgrad_wino2x4", H.ALGO_WINOGRAD_2X4),
+    "dsplit": ("ramnet_wgrad_dsplit_ws_floats", "ramnet_wgrad_dsplit_slabs", "ramnet_unpack_wgrad_dsplit", H.ALGO_DIRECT_SPLIT),
+}
+
+
+def _stamp_layout(dw, kind, slabs, head_cin=0):
+    """Write the layout of a pass onto its workspace tensor (the protocol stated at wgrad_launch); ConvParam.grad_ws is the one caller."""
+    dw.wino, dw.wino6, dw.wg_dsplit = kind == "wino", kind == "wino6", kind == "dsplit"
+    dw.slabs, dw.head_cin = slabs, head_cin
+    return dw
+
+
+def _layout_of(dw):
+    """(kind, slabs) back from the attributes of a workspace tensor, stamped by grad_ws or by hand."""
+    kind = ("dsplit" if getattr(dw, "wg_dsplit", False) else "wino6" if getattr(dw, "wino6", False) else
+            "wino" if getattr(dw, "wino", False) else "direct")
+    return kind, getattr(dw, "slabs", 0)
+
 
 def _wgrad_desc_build(x0, taps, dout, dw, Cout, stride, x1, xm, xm_off, in_mode, C0, C1, Hin, Win, gmask, dbias, Ho, Wo, gview, dw_off, wino24):
     d = H.WgradDesc()
@@ -469,12 +494,9 @@ def _wgrad_desc_build(x0, taps, dout, dw, Cout, stride, x1, xm, xm_off, in_mode,
     d.dw, d.dbias = _p(dw, dw_off), _p(dbias)
     if gview is not None:      # dout / gmask addressed as (oy*gsy + goy, ox*gsx + gox) of [B, HoG, WoG]
         d.gsy, d.gsx, d.goy, d.gox, d.HoG, d.WoG = gview
-    d.algo = H.ALGO_WINOGRAD if getattr(dw, "wino", False) else H.ALGO_DIRECT      # set by ConvParam.grad_ws()
-    if getattr(dw, "wino6", False):          # F(2x4,3x3): dw = [slabs][24][Cin][Cout] (csrc/conv_wgrad_wino6.hip)
-        d.algo = H.ALGO_WINOGRAD_2X4
-    if getattr(dw, "wg_dsplit", False):         # direct 3x3, split bf16 operands: dw = [slabs][9][Cin][Cout] (csrc/conv_wgrad_dsplit.hip)
-        d.algo = H.ALGO_DIRECT_SPLIT
-    d.dw_slabs = getattr(dw, "slabs", 0) if (d.algo in (H.ALGO_WINOGRAD, H.ALGO_WINOGRAD_2X4, H.ALGO_DIRECT_SPLIT) and _WGRAD_SLABS) else 0     # per-split slabs (read-modify-write joins)
+    kind, slabs = _layout_of(dw)
+    d.algo = _LAYOUTS[kind][3]
+    d.dw_slabs = slabs if (kind != "direct" and _WGRAD_SLABS) else 0     # per-split slabs (read-modify-write joins)
     if wino24:          # folded upsample-conv in the Winograd F(2x2,4x4) domain: dw = [4][25][C0][Cout]
         d.algo = H.ALGO_WINOGRAD24
     hc = getattr(dw, "head_cin", 0)
@@ -489,8 +511,12 @@ def wgrad_launch(x0, taps, dout, dw, Cout, *, stride=1, x1=None, xm=None, xm_off
                  C1=0, Hin=None, Win=None, gmask=None, dbias=None, Ho=None, Wo=None, gview=None, dw_off=0, wino24=False, segs=None, stream=None):
     """segs: a ctypes array of H.WgradSeg (ramnet_wgrad_desc.segs) — the tensors of several launches of the SAME layer and shape reduced
     in one launch (deferred ConvGRU cell updates, _wgrad_cell); x0 ... gmask then describe the first segment."""
+    # The layout of `dw` travels as plain attributes of the tensor: wino / wino6 / wg_dsplit (bool, absent = False; wg_dsplit wins over
+    # wino6 over wino, none = direct), slabs (int, absent = 0: no per-split slabs) and head_cin (int, absent = 0: not a head layer).
+    # ConvParam.grad_ws is the one writer in the package (_stamp_layout) and _layout_of the one reader of the first four; bench.py reads
+    # them for its FLOP / byte accounting, tests and tools stamp them on plain tensors to pick an algorithm: the names and defaults stay.
     # (descriptor cache as for _conv_desc: the template holds everything but the six pointers)
-    key = (id(taps), id(dw), getattr(dw, "wino", False), getattr(dw, "wino6", False), getattr(dw, "wg_dsplit", False), getattr(dw, "slabs", 0), getattr(dw, "head_cin", 0), Cout, stride,
+    key = (id(taps), id(dw), _layout_of(dw), getattr(dw, "head_cin", 0), Cout, stride,
            in_mode, C0, C1, Hin, Win, Ho, Wo, gview, dw_off, wino24, xm_off, tuple(x0.shape), x0.stride(2), _sd(x1), _sd(xm), dout.shape[1],
            dout.shape[2], dout.stride(2), _sd(gmask), _WGRAD_SLABS, _HEAD, x0.device.index)
     tmpl = _WDESC_CACHE.get(key) if _DESC_CACHE_ON else None
@@ -649,7 +675,7 @@ def wgrad_defer():
 
 def _wgrad_cell(cp, dw, tensors, x0, taps, dout, Cout, **kw):
     """Backward-weights of one recurrent-cell convolution: launched now (wgrad_side) or queued on the layer for a multi-segment launch."""
-    if _WGRAD_DEFER <= 1 or not getattr(dw, "wino6", False) or not _WGRAD_SLABS:
+    if _WGRAD_DEFER <= 1 or _layout_of(dw)[0] != "wino6" or not _WGRAD_SLABS:
         return wgrad_side(tensors, x0, taps, dout, dw, Cout, **kw)
     x1, xm = kw.get("x1"), kw.get("xm")
     key = (id(dw), tuple(x0.shape), ld(x0), ld(x1) if x1 is not None else 0, ld(xm) if xm is not None else 0, ld(dout), Cout,
@@ -838,6 +864,32 @@ def invalidate_packs():
     _PACK_EPOCH += 1
 
 
+# Packs of a layer: kind -> (size query, pack launch, the integer arguments of the launch from (Cout, Cin, k, transposed, gates), how
+# many of them the size query does not take).  False / True: direct and F(2x2,3x3) layouts; "head": the 5x5 head kernel; "2x4" / "2x4g" /
+# "2x4s": F(2x4,3x3), its gate-interleaved form for the ConvLSTM cell launch (8 hidden channels x (i, f, o, g) per 32-column workgroup,
+# forward only) and its three bf16 planes (csrc/conv_wino6s.hip; the size is in 4-byte units); "fold": the 8 x 8 = (py, px, ty, tx) tap
+# slices of fold_weights() in the direct layout; "fold24[d]" / "fold23[d]": the folded upsample-conv in the F(2x2,4x4) / F(2x3,4x4)
+# domain, forward and backward-data; "border": the four border matrices of one launch (no size query: ConvParam._build_pack).
+def _oc(Cout, Cin, k, transposed, gates):
+    return Cout, Cin
+
+
+_PACKS = {
+    False: ("ramnet_packed_weight_elems", "ramnet_pack_weight", lambda Co, Ci, k, t, g: (Co, Ci, k, k, t, g), 0),
+    True: ("ramnet_packed_weight_elems_wino", "ramnet_pack_weight_wino", lambda Co, Ci, k, t, g: (Co, Ci, t, g), 0),
+    "head": ("ramnet_packed_weight_elems_head", "ramnet_pack_weight_head", _oc, 1),
+    "2x4": ("ramnet_packed_weight_elems_wino2x4", "ramnet_pack_weight_wino2x4", lambda Co, Ci, k, t, g: (Co, Ci, t), 0),
+    "2x4g": ("ramnet_packed_weight_elems_wino2x4_gates", "ramnet_pack_weight_wino2x4_gates", lambda Co, Ci, k, t, g: (Co, Ci, t, g), 0),
+    "2x4s": ("ramnet_packed_weight_elems_wino2x4_split", "ramnet_pack_weight_wino2x4_split", lambda Co, Ci, k, t, g: (Co, Ci, t), 0),
+    "fold": ("ramnet_packed_weight_elems", "ramnet_pack_weight", lambda Co, Ci, k, t, g: (Co, Ci, 8, 8, 0, 1), 0),
+    "fold24": ("ramnet_packed_weight_elems_fold_wino", "ramnet_pack_weight_fold_wino", _oc, 0),
+    "fold24d": ("ramnet_packed_weight_elems_fold_wino", "ramnet_pack_weight_fold_wino_dgrad", _oc, 0),
+    "fold23": ("ramnet_packed_weight_elems_fold_wino2x3", "ramnet_pack_weight_fold_wino2x3", _oc, 0),
+    "fold23d": ("ramnet_packed_weight_elems_fold_wino2x3", "ramnet_pack_weight_fold_wino2x3_dgrad", _oc, 0),
+    "border": (None, "ramnet_pack_border_weights", _oc, 0),
+}
+
+
 class PackRef:
     """Handle on the packed weights of a ConvParam; the launch picks the layout (direct / Winograd) that fits it."""
     __slots__ = ("cp", "transposed")
@@ -857,11 +909,18 @@ class ConvParam:
         self.Cout = sum(w.shape[0] for w in self.weights)
         self.Cin, self.k = w0.shape[1], w0.shape[2]
         self.CinWs = (self.Cin + 3) // 4 * 4
-        self._bias = self._ws = self._bws = None
+        self._init_state()
+
+    def _init_state(self):
+        """Everything but the shape fields, for this class and the derived parameter views."""
+        self._bias = self._vbias = None
+        self._packs = {}                 # pack key -> (_versions at pack time, packed tensor(s))
+        self._splitk = {}                # floats -> split-reduction workspace (splitk_ws)
+        self._state_half = self._s2d = None
+        self._ws = self._bws = self._slabs = None
         self._ws_fold = None             # (dW4 [64][CinWs][Cout], dWrows, dWcols) of the folded upsample-conv backward-weights
-        self._fold_used = self._ws_used = False
-        self._vbias = None
-        self._packs = {}
+        self._ws_fold24 = None
+        self._fold_used = self._fold24_used = self._ws_used = False
         self._dirty = False
         self._defer = []                 # queued backward-weights launches of a recurrent cell (_wgrad_cell)
 
@@ -886,7 +945,7 @@ class ConvParam:
         counters at zero —, one buffer per size; the launches of ONE layer are ordered on one stream everywhere in this package
         (per-scale update chains, decoder stream and backward-weights stream run different layers).  First use inside a graph capture
         would record the zero-fill into the graph: the streaming runtimes warm up eagerly before they capture."""
-        pool = self.__dict__.setdefault("_splitk", {})       # (derived parameter views — S2DConvParam — build themselves)
+        pool = self._splitk
         ws = pool.get(n)
         if ws is None or ws.device != device:
             if torch.cuda.is_current_stream_capturing():
@@ -904,44 +963,33 @@ class ConvParam:
         w = self.weights[0] if len(self.weights) == 1 else torch.cat([w.detach() for w in self.weights], 0)
         return w.detach().contiguous()
 
-    def _pack(self, transposed, wino):
-        L, g = H.lib(), (self.gates if not transposed else 1)
-        w = self._cat_w()
-        if wino == "head":
-            out = torch.empty(L.ramnet_packed_weight_elems_head(self.Cin), device=w.device, dtype=torch.float32)
-            H.check(L.ramnet_pack_weight_head(_p(w), _p(out), self.Cout, self.Cin, _st()), "ramnet_pack_weight_head")
-            return out
-        if wino == "2x4":
-            out = torch.empty(L.ramnet_packed_weight_elems_wino2x4(self.Cout, self.Cin, transposed), device=w.device, dtype=torch.float32)
-            H.check(L.ramnet_pack_weight_wino2x4(_p(w), _p(out), self.Cout, self.Cin, transposed, _st()), "ramnet_pack_weight_wino2x4")
-            return out
-        if wino == "2x4g":      # ConvLSTM cell launch: 8 hidden channels x (i, f, o, g) per 32-column workgroup (forward only)
-            out = torch.empty(L.ramnet_packed_weight_elems_wino2x4_gates(self.Cout, self.Cin, transposed, g), device=w.device, dtype=torch.float32)
-            H.check(L.ramnet_pack_weight_wino2x4_gates(_p(w), _p(out), self.Cout, self.Cin, transposed, g, _st()), "ramnet_pack_weight_wino2x4_gates")
-            return out
-        if wino == "2x4s":      # three bf16 planes of the same Winograd-domain weights (csrc/conv_wino6s.hip); the size is in 4-byte units
-            out = torch.empty(L.ramnet_packed_weight_elems_wino2x4_split(self.Cout, self.Cin, transposed), device=w.device, dtype=torch.float32)
-            H.check(L.ramnet_pack_weight_wino2x4_split(_p(w), _p(out), self.Cout, self.Cin, transposed, _st()), "ramnet_pack_weight_wino2x4_split")
-            return out
-        if wino:
-            n = L.ramnet_packed_weight_elems_wino(self.Cout, self.Cin, transposed, g)
-            out = torch.empty(n, device=w.device, dtype=torch.float32)
-            H.check(L.ramnet_pack_weight_wino(_p(w), _p(out), self.Cout, self.Cin, transposed, g, _st()), "ramnet_pack_weight_wino")
-            return out
-        n = L.ramnet_packed_weight_elems(self.Cout, self.Cin, self.k, self.k, transposed, g)
-        out = torch.empty(n, device=w.device, dtype=torch.float32)
-        H.check(L.ramnet_pack_weight(_p(w), _p(out), self.Cout, self.Cin, self.k, self.k, transposed, g, _st()), "ramnet_pack_weight")
+    def _cached(self, key, kind, transposed=0):
+        """The pack `kind` of the current weights: re-run when a parameter's version or address, or the pack epoch, has changed."""
+        v = self._versions(self.weights)
+        hit = self._packs.get(key)
+        if hit is None or hit[0] != v:
+            hit = self._packs[key] = (v, self._build_pack(kind, transposed))
+        return hit[1]
+
+    def _build_pack(self, kind, transposed):
+        L, w = H.lib(), self._cat_w()
+        elems, pack, args, skip = _PACKS[kind]
+        a = args(self.Cout, self.Cin, self.k, transposed, 1 if transposed else self.gates)
+        if kind == "border":
+            rows, cols = (torch.empty(2, 5 * self.Cin, 2 * self.Cout, device=w.device) for _ in range(2))
+            rows_t, cols_t = (torch.empty(2, 2 * self.Cout, 5 * self.Cin, device=w.device) for _ in range(2))
+            H.check(getattr(L, pack)(_p(w), _p(rows), _p(cols), _p(rows_t), _p(cols_t), *a, _st()), pack)
+            return rows, cols, rows_t, cols_t
+        if kind == "fold":
+            w = fold_weights(w).reshape(self.Cout, self.Cin, 8, 8).float().contiguous()
+        out = torch.empty(getattr(L, elems)(*a[skip:]), device=w.device, dtype=torch.float32)
+        H.check(getattr(L, pack)(_p(w), _p(out), *a, _st()), pack)
         return out
 
     def pack(self, transposed, wino=False):
         """Packed weights for the forward (transposed=0) / backward-data (1) launch, re-packed when a parameter changes."""
-        v = self._versions(self.weights)
         wino = wino if wino in ("head", "2x4", "2x4g", "2x4s") else bool(wino)
-        key = (transposed, wino)
-        hit = self._packs.get(key)
-        if hit is None or hit[0] != v:
-            hit = self._packs[key] = (v, self._pack(transposed, wino))
-        return hit[1]
+        return self._cached((transposed, wino), wino, transposed)
 
     def fwd(self):
         return PackRef(self, 0)
@@ -951,92 +999,43 @@ class ConvParam:
 
     def pack_fold(self):
         """[64 = (py, px, ty, tx)] tap slices of fold_weights() in the direct kernel's layout."""
-        v = (self._versions(self.weights), "fold")
-        hit = self._packs.get("fold")
-        if hit is None or hit[0] != v:
-            w4 = fold_weights(self._cat_w()).reshape(self.Cout, self.Cin, 8, 8).float().contiguous()
-            L = H.lib()
-            out = torch.empty(L.ramnet_packed_weight_elems(self.Cout, self.Cin, 8, 8, 0, 1), device=w4.device)
-            H.check(L.ramnet_pack_weight(_p(w4), _p(out), self.Cout, self.Cin, 8, 8, 0, 1, _st()), "ramnet_pack_weight")
-            hit = self._packs["fold"] = (v, out)
-        return hit[1]
+        return self._cached("fold", "fold")
 
     def pack_fold_wino(self):
         """Winograd-domain weights of the folded upsample-conv (conv_wino24_kernel), cached per parameter version."""
-        v = (self._versions(self.weights), "fold24")
-        hit = self._packs.get("fold24")
-        if hit is None or hit[0] != v:
-            L, w = H.lib(), self._cat_w()
-            out = torch.empty(L.ramnet_packed_weight_elems_fold_wino(self.Cout, self.Cin), device=w.device, dtype=torch.float32)
-            H.check(L.ramnet_pack_weight_fold_wino(_p(w), _p(out), self.Cout, self.Cin, _st()), "ramnet_pack_weight_fold_wino")
-            hit = self._packs["fold24"] = (v, out)
-        return hit[1]
+        return self._cached("fold24", "fold24")
 
     def pack_fold_wino_dgrad(self):
-        v = (self._versions(self.weights), "fold24d")
-        hit = self._packs.get("fold24d")
-        if hit is None or hit[0] != v:
-            L, w = H.lib(), self._cat_w()
-            out = torch.empty(L.ramnet_packed_weight_elems_fold_wino(self.Cout, self.Cin), device=w.device, dtype=torch.float32)
-            H.check(L.ramnet_pack_weight_fold_wino_dgrad(_p(w), _p(out), self.Cout, self.Cin, _st()), "ramnet_pack_weight_fold_wino_dgrad")
-            hit = self._packs["fold24d"] = (v, out)
-        return hit[1]
+        return self._cached("fold24d", "fold24d")
 
     def pack_fold_wino2x3(self):
         """Winograd-domain weights of the folded upsample-conv for F(2x3,4x4) launches (conv_wino24_kernel<.., 3>), cached per parameter version."""
-        v = (self._versions(self.weights), "fold23")
-        hit = self._packs.get("fold23")
-        if hit is None or hit[0] != v:
-            L, w = H.lib(), self._cat_w()
-            out = torch.empty(L.ramnet_packed_weight_elems_fold_wino2x3(self.Cout, self.Cin), device=w.device, dtype=torch.float32)
-            H.check(L.ramnet_pack_weight_fold_wino2x3(_p(w), _p(out), self.Cout, self.Cin, _st()), "ramnet_pack_weight_fold_wino2x3")
-            hit = self._packs["fold23"] = (v, out)
-        return hit[1]
+        return self._cached("fold23", "fold23")
 
     def pack_fold_wino2x3_dgrad(self):
-        v = (self._versions(self.weights), "fold23d")
-        hit = self._packs.get("fold23d")
-        if hit is None or hit[0] != v:
-            L, w = H.lib(), self._cat_w()
-            out = torch.empty(L.ramnet_packed_weight_elems_fold_wino2x3(self.Cout, self.Cin), device=w.device, dtype=torch.float32)
-            H.check(L.ramnet_pack_weight_fold_wino2x3_dgrad(_p(w), _p(out), self.Cout, self.Cin, _st()), "ramnet_pack_weight_fold_wino2x3_dgrad")
-            hit = self._packs["fold23d"] = (v, out)
-        return hit[1]
-
-    def _border_pack(self):
-        """(rows, cols, rows^T, cols^T) of the border matrices (tests/torch_restatements.border_matrices is the plain-torch statement; one launch of
-        ramnet_pack_border_weights), cached per parameter version."""
-        v = (self._versions(self.weights), "border")
-        hit = self._packs.get("border")
-        if hit is None or hit[0] != v:
-            w = self._cat_w()
-            rows, cols = (torch.empty(2, 5 * self.Cin, 2 * self.Cout, device=w.device) for _ in range(2))
-            rows_t, cols_t = (torch.empty(2, 2 * self.Cout, 5 * self.Cin, device=w.device) for _ in range(2))
-            H.check(H.lib().ramnet_pack_border_weights(_p(w), _p(rows), _p(cols), _p(rows_t), _p(cols_t), self.Cout, self.Cin, _st()),
-                    "ramnet_pack_border_weights")
-            hit = self._packs["border"] = (v, (rows, cols, rows_t, cols_t))
-        return hit[1]
+        return self._cached("fold23d", "fold23d")
 
     def border_weights(self):
-        """[2 sides][5*Cin][2*Cout] row / column border matrices of the current weights."""
-        return self._border_pack()[:2]
+        """[2 sides][5*Cin][2*Cout] row / column border matrices of the current weights (tests/torch_restatements.border_matrices is the
+        plain-torch statement; one launch of ramnet_pack_border_weights for these and their transposes)."""
+        return self._cached("border", "border")[:2]
 
     def border_weights_t(self):
         """border_weights() transposed to [2 sides][2*Cout][5*Cin] (the backward-data operand)."""
-        return self._border_pack()[2:]
+        return self._cached("border", "border")[2:]
 
     def bwd(self):
         return PackRef(self, 1)
 
     def state_half(self):
         """The state half of this recurrent-cell convolution over [x | h] (StateHalfConvParam), created once."""
-        if getattr(self, "_state_half", None) is None:
+        if self._state_half is None:
             self._state_half = StateHalfConvParam(self)
         return self._state_half
 
     def s2d(self):
         """3x3 view over the space-to-depth input of this 5x5 stride-2 convolution (S2DConvParam), created once."""
-        if getattr(self, "_s2d", None) is None:
+        if self._s2d is None:
             self._s2d = S2DConvParam(self)
         return self._s2d
 
@@ -1050,6 +1049,23 @@ class ConvParam:
             self._bias, self._vbias = torch.cat([b.detach() for b in self.biases]).contiguous(), v
         return self._bias
 
+    def _slab_floats(self, kind):
+        f = _LAYOUTS[kind][0]
+        return getattr(H.lib(), f)(self.CinWs, self.Cout) if isinstance(f, str) else (f or self.k * self.k) * self.CinWs * self.Cout
+
+    def _choose_layout(self, wino_ok):
+        """(kind, slabs) of the weight-gradient workspace for the pass that starts: one algorithm per layer and pass."""
+        wino = bool(wino_ok and _WINOGRAD and self.k == 3 and self.CinWs >= _WINO_MIN_CIN)
+        # F(2x4,3x3) for the plain 3x3 layers (not the space-to-depth views): slabs of [24][Cin][Cout], half as many as F(2x2)'s
+        wino6 = bool(wino and (_WGRAD_2X4 == "force" or (_WGRAD_2X4 == "auto" and _USE_SIDE))
+                     and (type(self) is ConvParam or (_S2D_2X4 and self.Cin >= 128)) and self.CinWs >= 64)
+        # ... and with split operands on, those layers' backward-weights in direct form on the bf16 matrix pipe: slabs of [9][Cin][Cout]
+        kind = "dsplit" if (wino6 and _SPLIT_OPERANDS and _SPLIT_WGRAD) else "wino6" if wino6 else "wino" if wino else "direct"
+        if kind in ("direct", "wino"):
+            return kind, self._slabs
+        ns = getattr(H.lib(), _LAYOUTS[kind][1])(self.CinWs, self.Cout)
+        return kind, (min(self._slabs, ns) if kind == "wino6" else ns)
+
     def grad_ws(self, wino_ok=False):
         """([tap][CinWs][Cout] weight-gradient workspace, [Cout] bias-gradient workspace), zero at pass start.
         wino_ok: the caller's launch is a plain 3x3 stride-1 convolution (no upsampling loader), i.e. eligible for the
@@ -1059,39 +1075,23 @@ class ConvParam:
             slots = 24 if self.k == 3 else self.k * self.k       # 3x3: room for the Winograd-domain gradient dU (F(2x4): 24, F(2x2): 16 positions)
             # 3x3 layers: one slab per tile split of the Winograd backward-weights launch (joined by plain read-modify-write: no atomics,
             # bit-reproducible sums; ramnet_wgrad_desc.dw_slabs) — folded into slab 0 by finalize(); other layers: one slab
-            self._slabs = H.lib().ramnet_wgrad_wino_slabs(self.CinWs, self.Cout) if self.k == 3 else 1
+            self._slabs = getattr(H.lib(), _LAYOUTS["wino"][1])(self.CinWs, self.Cout) if self.k == 3 else 1
             # (F(2x4): blocked layout padded to 32 x 32-channel blocks, half as many slabs as F(2x2): never larger than the dense 24-slot slabs
             # of F(2x2)'s count unless the channel counts are ragged — take the maximum)
-            n6 = H.lib().ramnet_wgrad_wino2x4_ws_floats(self.CinWs, self.Cout) * H.lib().ramnet_wgrad_wino2x4_slabs(self.CinWs, self.Cout) if self.k == 3 else 0
+            n6 = self._slab_floats("wino6") * getattr(H.lib(), _LAYOUTS["wino6"][1])(self.CinWs, self.Cout) if self.k == 3 else 0
             self._ws = torch.zeros(max(self._slabs * slots * self.CinWs * self.Cout, n6), device=dev)
             self._bws = torch.zeros(self._slabs * self.Cout, device=dev)
-            self._ws.slabs = self._slabs
         _Engine.enter()         # (a new pass after an aborted one resets _dirty first)
-        if not self._dirty:     # one algorithm per backward pass: every launch of the pass accumulates into the same layout
-            self._ws.wino = bool(wino_ok and _WINOGRAD and self.k == 3
-                                 and self.CinWs >= _WINO_MIN_CIN)
-            # F(2x4,3x3) for the plain 3x3 layers (not the space-to-depth views): slabs of [24][Cin][Cout], half as many as F(2x2)'s
-            self._ws.wino6 = bool(self._ws.wino and (_WGRAD_2X4 == "force" or (_WGRAD_2X4 == "auto" and _USE_SIDE))
-                                  and (type(self) is ConvParam or (_S2D_2X4 and self.Cin >= 128)) and self.CinWs >= 64)
-            # ... and with split operands on, those layers' backward-weights in direct form on the bf16 matrix pipe: slabs of [9][Cin][Cout]
-            self._ws.wg_dsplit = bool(self._ws.wino6 and _SPLIT_OPERANDS and _SPLIT_WGRAD)
-            if self._ws.wg_dsplit:
-                ns, nf = H.lib().ramnet_wgrad_dsplit_slabs(self.CinWs, self.Cout), H.lib().ramnet_wgrad_dsplit_ws_floats(self.CinWs, self.Cout)
-                if self._ws.numel() < ns * nf or self._bws.numel() < ns * self.Cout:       # (between passes the workspaces hold zeros: grow them)
-                    old = self._ws
-                    self._ws = torch.zeros(max(ns * nf, old.numel()), device=old.device)
-                    self._ws.wg_dsplit = True
-                    self._bws = torch.zeros(max(ns, self._slabs) * self.Cout, device=old.device)
-                self._ws.wino = self._ws.wino6 = False
-                self._ws.slabs = ns
-            elif self._ws.wino6:
-                self._ws.wino = False
-                self._ws.slabs = min(self._slabs, H.lib().ramnet_wgrad_wino2x4_slabs(self.CinWs, self.Cout))
-            else:
-                self._ws.slabs = self._slabs
+        if not self._dirty:     # every launch of the pass accumulates into the same layout
+            kind, ns = self._choose_layout(wino_ok)
+            n = ns * self._slab_floats(kind) if kind == "dsplit" else 0
+            if self._ws.numel() < n or (n and self._bws.numel() < ns * self.Cout):
+                dev = self._ws.device                       # (between passes the workspaces hold zeros: grow them)
+                self._ws = torch.zeros(max(n, self._ws.numel()), device=dev)
+                self._bws = torch.zeros(max(ns, self._slabs) * self.Cout, device=dev)
             # head layers: the launch may run the head kernel (same [tap][CinWs][Cout] layout as the direct kernel)
-            self._ws.head_cin = self.Cin if (self.k == 5 and self.gates == 1 and len(self.weights) == 1
-                                             and H.lib().ramnet_head_supported(self.Cin, self.Cout)) else 0
+            _stamp_layout(self._ws, kind, ns, self.Cin if (self.k == 5 and self.gates == 1 and len(self.weights) == 1
+                                                          and H.lib().ramnet_head_supported(self.Cin, self.Cout)) else 0)
         _Engine.mark(self)
         self._ws_used = True
         return self._ws, self._bws
@@ -1113,7 +1113,7 @@ class ConvParam:
 
     def grad_ws_fold24(self):
         """dU [4 parity classes][25 positions][Cin][Cout]: Winograd-domain gradient of the four 4x4 parity filters."""
-        if getattr(self, "_ws_fold24", None) is None:
+        if self._ws_fold24 is None:
             self._ws_fold24 = torch.zeros(4 * 25 * self.CinWs * self.Cout, device=self.weights[0].device)
         self._fold24_used = True
         return self._ws_fold24
@@ -1123,7 +1123,7 @@ class ConvParam:
         launches' workspace + G^T dU G of the Winograd-domain launches: one launch (ramnet_fold_unpack_wgrad), which also zeroes the
         workspaces for the next pass."""
         w4, wr, wc = self._ws_fold
-        dU = self._ws_fold24 if getattr(self, "_fold24_used", False) else None
+        dU = self._ws_fold24 if self._fold24_used else None
         if self.weights[0].requires_grad:
             g = ensure_grad(self.weights[0])
             H.check(H.lib().ramnet_fold_unpack_wgrad(_p(w4), _p(dU), _p(wr), _p(wc), _p(g), self.Cout, self.Cin, self.CinWs, _st()),
@@ -1137,37 +1137,32 @@ class ConvParam:
 
     def discard(self):
         """Zero every gradient workspace without folding it (aborted backward pass)."""
-        for t in (self._ws, self._bws, getattr(self, "_ws_fold24", None)) + tuple(self._ws_fold or ()):
+        for t in (self._ws, self._bws, self._ws_fold24) + tuple(self._ws_fold or ()):
             if t is not None:
                 t.zero_()
         self._dirty = self._ws_used = self._fold_used = self._fold24_used = False
 
     def _join_slabs(self):
         """Winograd backward-weights slabs -> slab 0 (fixed order), weights and bias."""
-        w6, ds = getattr(self._ws, "wino6", False), getattr(self._ws, "wg_dsplit", False)
-        ns = getattr(self._ws, "slabs", 1)
-        if ns > 1 and (w6 or ds or getattr(self._ws, "wino", False)):
-            n = (H.lib().ramnet_wgrad_wino2x4_ws_floats(self.CinWs, self.Cout) if w6 else
-                 H.lib().ramnet_wgrad_dsplit_ws_floats(self.CinWs, self.Cout) if ds else 16 * self.CinWs * self.Cout)
-            H.check(H.lib().ramnet_reduce_slabs(_p(self._ws), ns, n, _st()), "ramnet_reduce_slabs")
+        kind, ns = _layout_of(self._ws)
+        if ns > 1 and kind != "direct":
+            H.check(H.lib().ramnet_reduce_slabs(_p(self._ws), ns, self._slab_floats(kind), _st()), "ramnet_reduce_slabs")
             H.check(H.lib().ramnet_reduce_slabs(_p(self._bws), ns, self.Cout, _st()), "ramnet_reduce_slabs")
 
     def _zero_ws(self):
         """Zero what the pass used of the gradient workspace for the next one: slab 0 only where the slabs were joined
         (ramnet_reduce_slabs leaves slabs 1.. zeroed), not the whole buffer sized for the largest layout."""
-        w6, wn, ds = getattr(self._ws, "wino6", False), getattr(self._ws, "wino", False), getattr(self._ws, "wg_dsplit", False)
-        ns = getattr(self._ws, "slabs", 1)
-        if w6:
-            n = H.lib().ramnet_wgrad_wino2x4_ws_floats(self.CinWs, self.Cout)
-        elif wn:
-            n = 16 * self.CinWs * self.Cout
-        elif ds:
-            n = H.lib().ramnet_wgrad_dsplit_ws_floats(self.CinWs, self.Cout)
-        else:
-            n, ns = self.k * self.k * self.CinWs * self.Cout, 1
-        joined = ns > 1 and (w6 or wn or ds)
-        _zero_later(self._ws[:n if joined else min(self._ws.numel(), n * max(ns, 1))])
+        kind, ns = _layout_of(self._ws)
+        n, ns = self._slab_floats(kind), (1 if kind == "direct" else max(ns, 1))
+        joined = ns > 1
+        _zero_later(self._ws[:n if joined else min(self._ws.numel(), n * ns)])
         _zero_later(self._bws[:self.Cout if joined else self._bws.numel()])
+
+    def _unpack(self, g, n, off):
+        """Output channels off .. off + n of the (joined) workspace -> the OIHW gradient g, += (the layout's own unpack launch)."""
+        kind = _layout_of(self._ws)[0]
+        taps = (self.k, self.k) if kind == "direct" else ()
+        H.check(getattr(H.lib(), _LAYOUTS[kind][2])(_p(self._ws), _p(g), n, self.Cin, self.CinWs, self.Cout, off, *taps, _st()), _LAYOUTS[kind][2])
 
     def finalize(self):
         if self._fold_used:
@@ -1185,21 +1180,8 @@ class ConvParam:
             n = w.shape[0]
             # tensors that share the launch (a weight and its bias, the update and reset gates of a ConvGRU) may be frozen one by one
             # (requires_grad == False, read live): the fold writes the trainable ones only
-            g = ensure_grad(w) if w.requires_grad else None
-            if g is None:
-                pass
-            elif getattr(self._ws, "wino6", False):
-                H.check(H.lib().ramnet_unpack_wgrad_wino2x4(_p(self._ws), _p(g), n, self.Cin, self.CinWs, self.Cout, off, _st()),
-                        "ramnet_unpack_wgrad_wino2x4")
-            elif getattr(self._ws, "wg_dsplit", False):
-                H.check(H.lib().ramnet_unpack_wgrad_dsplit(_p(self._ws), _p(g), n, self.Cin, self.CinWs, self.Cout, off, _st()),
-                        "ramnet_unpack_wgrad_dsplit")
-            elif getattr(self._ws, "wino", False):
-                H.check(H.lib().ramnet_unpack_wgrad_wino(_p(self._ws), _p(g), n, self.Cin, self.CinWs, self.Cout, off, _st()),
-                        "ramnet_unpack_wgrad_wino")
-            else:
-                H.check(H.lib().ramnet_unpack_wgrad(_p(self._ws), _p(g), n, self.Cin, self.CinWs, self.Cout, off,
-                                                    self.k, self.k, _st()), "ramnet_unpack_wgrad")
+            if w.requires_grad:
+                self._unpack(ensure_grad(w), n, off)
             if b is not None and b.shape[0] == n and b.requires_grad:      # (transposed conv: bias has Cout_t entries, handled by its op)
                 ensure_grad(b).add_(self._bws[off:off + n])
             off += n
@@ -1218,13 +1200,7 @@ class S2DConvParam(ConvParam):
         self.weights, self.biases, self.gates = parent.weights, parent.biases, 1
         self.Cout, self.Cin, self.k = parent.Cout, 4 * parent.Cin, 3
         self.CinWs = self.Cin
-        self._bias = self._ws = self._bws = None
-        self._vbias = None
-        self._ws_fold = None
-        self._fold_used = self._ws_used = False
-        self._packs = {}
-        self._dirty = False
-        self._defer = []
+        self._init_state()
 
     def _cat_w(self):
         return s2d_weights(self.parent.weights[0].detach()).contiguous()
@@ -1232,19 +1208,9 @@ class S2DConvParam(ConvParam):
     def finalize(self):
         w, b = self.parent.weights[0], self.parent.biases[0]
         g3 = torch.zeros(self.Cout, self.Cin, 3, 3, device=w.device) if w.requires_grad else None
-        L = H.lib()
         self._join_slabs()
-        if g3 is None:          # frozen weight beside a trainable bias: the bias sum below is all there is to fold
-            pass
-        elif getattr(self._ws, "wino6", False):
-            H.check(L.ramnet_unpack_wgrad_wino2x4(_p(self._ws), _p(g3), self.Cout, self.Cin, self.CinWs, self.Cout, 0, _st()), "ramnet_unpack_wgrad_wino2x4")
-        elif getattr(self._ws, "wg_dsplit", False):
-            H.check(L.ramnet_unpack_wgrad_dsplit(_p(self._ws), _p(g3), self.Cout, self.Cin, self.CinWs, self.Cout, 0, _st()), "ramnet_unpack_wgrad_dsplit")
-        elif getattr(self._ws, "wino", False):
-            H.check(L.ramnet_unpack_wgrad_wino(_p(self._ws), _p(g3), self.Cout, self.Cin, self.CinWs, self.Cout, 0, _st()), "ramnet_unpack_wgrad_wino")
-        else:
-            H.check(L.ramnet_unpack_wgrad(_p(self._ws), _p(g3), self.Cout, self.Cin, self.CinWs, self.Cout, 0, 3, 3, _st()), "ramnet_unpack_wgrad")
-        if g3 is not None:
+        if g3 is not None:          # (frozen weight beside a trainable bias: the bias sum below is all there is to fold)
+            self._unpack(g3, self.Cout, 0)
             ensure_grad(w).add_(s2d_weights_adjoint(g3, self.parent.Cin))
         if b is not None and b.requires_grad:
             ensure_grad(b).add_(self._bws[:self.Cout])
@@ -1263,9 +1229,7 @@ class StateHalfConvParam(ConvParam):
         self.weights, self.biases, self.gates = parent.weights, parent.biases, parent.gates
         self.Cout, self.Cin, self.k = parent.Cout, parent.Cin // 2, 3
         self.CinWs = self.Cin
-        self._packs = {}
-        self._dirty = False
-        self._defer = []
+        self._init_state()
 
     def _cat_w(self):
         return self.parent._cat_w()[:, self.Cin:].contiguous()

@@ -610,6 +610,37 @@ int ramnet_metric_depth(const float *y, size_t n, float clip_distance, float reg
 size_t ramnet_eval_table_workspace(int G, size_t npix, int ncut, int has_mask);
 int ramnet_eval_table(const float *const *pred, const float *const *target, const unsigned char *const *mask, int G, size_t npix,
                       float clip_distance, float reg_factor, const float *cutoffs, int ncut, void *workspace, double *out, void *stream);
+/* The table with evaluation.py's --rescale and --down_scale_factor (ABI 27).  The _ex entry points take `flags`, a sum of
+ *   RAMNET_EVAL_RESCALE        the rows are formed after rescale_by_the_median (evaluation.py:99-154), see below;
+ *   RAMNET_EVAL_TARGET_METRIC  the target tables hold float32 METRIC depth already (NaN = no ground truth) and are not converted again:
+ *                              what the resize entry below writes.  The predictions are normalised log depth as before.
+ * flags = 0 IS the plain table: the same kernels, the same rows bit for bit, the same workspace size.  A workspace allocated for one flag
+ * value serves any other call that fits it, with no memset in between (the ticket rule above holds for all of them).
+ * The row of a RESCALED call.  Per (pair, variant), t / p = the float32 metric target / clipped metric prediction of the pixels inside,
+ * exactly as above; everything below in double on those float32 values:
+ *   med_x = np.median of the float32 values (columns 11 / 12 of the plain row)      std_x = sqrt(mean((x - mean(x))^2)), two passes
+ *   T_x(v) = (v - med_x) / std_x + |(min_x - med_x) / std_x|                        x in {t, p}
+ *   m_x = the median of T_x over the pixels = T_x(middle value), (T_x(a) + T_x(b)) * 0.5 for the two middle values of an even count
+ *   md = |m_t - m_p|;  m_t < m_p: t' = T_t(t) + md, p' = T_p(p);  otherwise: t' = T_t(t), p' = T_p(p) + md
+ *   0 n_mask, 1 n as above    2..10 the sums and threshold counts of the plain row on (t', p'), same expressions and epsilons
+ *   11 / 12 the medians of t' / p' (m_x, plus md on the lifted side)    13..15 zero
+ * A variant that holds a NaN target (n != n_mask), or nothing: columns 2..7, 11 and 12 NaN, 8..10 zero (np.median is NaN there and so is
+ * all that follows; an empty variant has ten NaN table entries as without rescaling, where the reference's np.min raises).  A side with
+ * zero spread (one pixel, a constant map) is not special-cased: 0 / 0 makes the sums NaN and the threshold counts 0 (the reference fails
+ * to broadcast there).  Four launches whatever G and V are, joined as the plain table: the same bits on every call.
+ * The resize entry: target = DEVICE table of G pointers to H x W floats of normalised log depth; out[G][H'][W'] float32 METRIC depth,
+ * H' = floor(H * scale_factor), W' likewise, 0 < scale_factor <= 1: torch's F.interpolate(metric target, scale_factor, mode='bilinear') at its
+ * defaults (align_corners=False; source coordinate max((dst + 0.5) / scale_factor - 0.5, 0) from the given factor, not from the size
+ * ratio) on the unclamped metric depths of the conversion above, evaluated in double and rounded once.  A NaN tap makes the output NaN,
+ * at weight zero too.  One launch for the G maps.                                                                                     */
+#define RAMNET_EVAL_RESCALE 1
+#define RAMNET_EVAL_TARGET_METRIC 2
+size_t ramnet_eval_table_ex_workspace(int G, size_t npix, int ncut, int has_mask, int flags);
+int ramnet_eval_table_ex(const float *const *pred, const float *const *target, const unsigned char *const *mask, int G, size_t npix,
+                         float clip_distance, float reg_factor, const float *cutoffs, int ncut, int flags, void *workspace, double *out,
+                         void *stream);
+int ramnet_resize_metric_target(const float *const *target, int G, int H, int W, double scale_factor, float clip_distance, float reg_factor,
+                                float *out, void *stream);
 
 /* ---- multi-scale gradient loss of G pairs together (csrc/grad_loss.hip): the semantics of the per-pair entry points above (model/loss.py:22-70
  * as oracle/loss_ref.py restates it; kornia parity unpinned), batched, without a saved pyramid, a zero-fill or a floating-point atomic: the

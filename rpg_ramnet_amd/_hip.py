@@ -184,6 +184,10 @@ _SIGS = {
     "ramnet_metric_depth": (C.c_int, [_fp, C.c_size_t, C.c_float, C.c_float, C.c_int, _fp, _fp]),
     "ramnet_eval_table_workspace": (C.c_size_t, [C.c_int, C.c_size_t, C.c_int, C.c_int]),
     "ramnet_eval_table": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_size_t, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_int, _fp, _fp, _fp]),
+    "ramnet_eval_table_ex_workspace": (C.c_size_t, [C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int]),
+    "ramnet_eval_table_ex": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_size_t, C.c_float, C.c_float, C.POINTER(C.c_float), C.c_int, C.c_int, _fp, _fp,
+                                       _fp]),
+    "ramnet_resize_metric_target": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_float, C.c_float, _fp, _fp]),
     "ramnet_fill_pointer_table": (C.c_int, [_fp, C.POINTER(C.c_void_p), C.c_int, _fp]),
     "ramnet_grad_loss_workspace": (C.c_size_t, [C.c_int] * 4),
     "ramnet_grad_loss_stats": (C.c_int, [_fp, _fp] + [C.c_int] * 5 + [_fp] * 6),

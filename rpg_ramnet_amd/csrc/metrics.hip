@@ -362,7 +362,19 @@ namespace ramnet {
 // A variant whose mask holds a NaN target, or nothing, has NaN medians (np.median over such a mask is NaN): passes 2 and 3 skip it.
 //
 // Workspace: [64 Ki tickets][G V states][G V x P partial rows][G V x P slabs of 4096 words: 2 x 2048 bins in pass 1, 4 x 1024 after it].
+//
+// RESCALED rows (evaluation.py:99-154, rescale_by_the_median before the metrics are formed; template argument RS): the sums are taken on
+//   t' = T_t(t) [+ md], p' = T_p(p) [+ md],  T_x(v) = (v - med_x) / std_x + |(min_x - med_x) / std_x|,  md = |T_t-median - T_p-median|
+// added to the side with the smaller median, all in double on the float32 depths.  The constants of a (pair, variant) have to exist before the
+// first term: pass 1 adds the sums (-> means) and the minima of t and p, pass 2 the sums of squared deviations from those means (np.std's
+// two passes), pass 3 leaves the two middle values of each map in the state, and a FOURTH pass, et_rescale_kernel, forms the sums and writes
+// columns 2..12.  T_x is monotone: minimum and median of a transformed map are the transforms of the minimum and of the middle values.
+// A variant with a NaN target, or empty, takes no part in passes 2..4 (pass 1 writes its row: NaN sums, zero threshold counts); zero spread
+// is not special-cased: 0 / 0 makes the sums NaN and the comparisons false.  Partial rows are 16 doubles here and the constants live behind
+// the slabs: [...][G V x P slabs][G V x 8 doubles].
 constexpr int ET_ROW = 12;                 // doubles of a partial row: n_mask, n, six sums, three threshold counts, (unused)
+constexpr int ET_ROWX = 16;                // ... of a rescaled call: the same, then sum t, sum p, min t, min p, (unused)
+constexpr int ET_CST = 8;                  // doubles per (pair, variant) of a rescaled call: mean t, mean p, min t, min p, std t, std p, (unused)
 constexpr int ET_COLS = 11;
 constexpr int ET_OUT = 16;                 // doubles of an output row
 constexpr int ET_STATE = 12;               // uint32 per (pair, variant): target prefix0, rank0, prefix1, rank1; the same of the prediction; n; medians wanted
@@ -378,14 +390,15 @@ struct et_args_t {
     float clip, reg, cut[ET_MAXCUT];
     int ncut, V, Ws;
     unsigned npix;
+    int tmetric;                           // the target tables hold float32 metric depth already
 };
 
 struct et_plan_t {
     int V, Ws;
-    size_t off_state, off_part, off_slab, total;
+    size_t off_state, off_part, off_slab, off_cst, total;
 };
 
-static et_plan_t et_plan(int G, size_t npix, int ncut, int has_mask) {
+static et_plan_t et_plan(int G, size_t npix, int ncut, int has_mask, bool rescale = false) {
     et_plan_t p;
     size_t ws = (npix + ET_SPAN - 1) / ET_SPAN;
     if (ws > ET_MAX_PER_MAP) ws = ET_MAX_PER_MAP;
@@ -394,8 +407,9 @@ static et_plan_t et_plan(int G, size_t npix, int ncut, int has_mask) {
     const size_t cells = (size_t)G * p.V;
     p.off_state = RAMNET_EVAL_TABLE_TICKET_BYTES;
     p.off_part = p.off_state + ((cells * ET_STATE * sizeof(unsigned) + 255) & ~(size_t)255);
-    p.off_slab = p.off_part + ((cells * p.Ws * ET_ROW * sizeof(double) + 255) & ~(size_t)255);
-    p.total = p.off_slab + cells * p.Ws * ET_SLAB * sizeof(unsigned);
+    p.off_slab = p.off_part + ((cells * p.Ws * (rescale ? ET_ROWX : ET_ROW) * sizeof(double) + 255) & ~(size_t)255);
+    p.off_cst = p.off_slab + cells * p.Ws * ET_SLAB * sizeof(unsigned);
+    p.total = p.off_cst + (rescale ? cells * ET_CST * sizeof(double) : 0);
     return p;
 }
 
@@ -455,7 +469,7 @@ struct et_view_t {
     et_msk_t m;
     unsigned lo, hi;
     float reg, clip, lo_d, cutoff;
-    bool cut;
+    bool cut, tmetric;
     __device__ __forceinline__ et_view_t(const float *const *preds, const float *const *targets, const unsigned char *const *masks, const et_args_t &a,
                                          int w, int v, size_t g) {
         const int c = v % (a.ncut + 1);
@@ -464,11 +478,12 @@ struct et_view_t {
         et_range(a.npix, a.Ws, w, lo, hi);
         reg = a.reg, clip = a.clip, lo_d = expf(-a.reg) * a.clip;
         cut = c != 0, cutoff = c ? a.cut[c - 1] : 0.f;
+        tmetric = a.tmetric != 0;
     }
     // metric target of a pixel that is inside -> tm; nan: it has no ground truth
     __device__ __forceinline__ bool inside(float tn, unsigned char mv, float &tm, bool &nan) const {
         nan = !(tn == tn);
-        tm = et_metric_depth(tn, reg, clip, lo_d, false);
+        tm = tmetric ? tn : et_metric_depth(tn, reg, clip, lo_d, false);
         return mv != 0 && (!cut || nan || tm < cutoff);
     }
     __device__ __forceinline__ float pred(float pn) const { return et_metric_depth(pn, reg, clip, lo_d, true); }
@@ -486,11 +501,20 @@ __device__ __forceinline__ bool et_arrive(unsigned (*hist)[BM_BINS / 2], unsigne
     return bm_ticket(cell, P, tickets, flag);
 }
 
+__device__ __forceinline__ float et_wave_min(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_down(v, o));
+    return v;
+}
+
+// RS: a rescaled call (rows of ET_ROWX doubles; cst = the constants of the (pair, variant) cells)
+template <bool RS>
 __global__ void __launch_bounds__(BM_T) et_sums_kernel(const float *const *__restrict__ preds, const float *const *__restrict__ targets,
                                                        const unsigned char *const *__restrict__ masks, et_args_t a, unsigned *tickets, unsigned *state,
-                                                       double *part, unsigned *slab, double *__restrict__ out) {
+                                                       double *part, unsigned *slab, double *cst, double *__restrict__ out) {
+    constexpr int ROW = RS ? ET_ROWX : ET_ROW;
     __shared__ unsigned hist[2][BM_BINS];
-    __shared__ double red[ET_COLS][BM_T / 64], stage[ET_MAX_PER_MAP * ET_ROW];
+    __shared__ double red[ET_OUT][BM_T / 64], stage[ET_MAX_PER_MAP * ROW];
     __shared__ unsigned scan[BM_T / 64], res[2];
     __shared__ int flag;
     const int w = blockIdx.x, v = blockIdx.y, P = a.Ws;
@@ -500,6 +524,8 @@ __global__ void __launch_bounds__(BM_T) et_sums_kernel(const float *const *__res
     __syncthreads();
     const et_view_t vw(preds, targets, masks, a, w, v, g);
     double acc[ET_COLS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    double sum_t = 0.0, sum_p = 0.0;
+    float min_t = __uint_as_float(0x7f800000u), min_p = __uint_as_float(0x7f800000u);
     unsigned nmask = 0, n = 0;
     const double eps = 1e-5;
     et_sweep(vw.p, vw.t, vw.m, vw.lo, vw.hi, [&](float pn, float tn, unsigned char mv) {
@@ -517,6 +543,7 @@ __global__ void __launch_bounds__(BM_T) et_sums_kernel(const float *const *__res
         acc[8] += r <= 1.25, acc[9] += r <= 1.5625, acc[10] += r <= 1.953125;
         atomicAdd(&hist[0][et_key(t) >> 20], 1u);
         atomicAdd(&hist[1][et_key(p) >> 20], 1u);
+        if (RS) sum_t += (double)t, sum_p += (double)p, min_t = fminf(min_t, t), min_p = fminf(min_p, p);
     });
     acc[0] = (double)nmask, acc[1] = (double)n;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -525,31 +552,53 @@ __global__ void __launch_bounds__(BM_T) et_sums_kernel(const float *const *__res
         const double s = bm_wave_sum(acc[k]);
         if (lane == 0) red[k][wave] = s;
     }
+    if (RS) {
+        const double st = bm_wave_sum(sum_t), sp = bm_wave_sum(sum_p);
+        const float mt = et_wave_min(min_t), mp = et_wave_min(min_p);
+        if (lane == 0) red[11][wave] = st, red[12][wave] = sp, red[13][wave] = (double)mt, red[14][wave] = (double)mp;
+    }
     __syncthreads();
-    if (threadIdx.x < ET_COLS) {
+    if (threadIdx.x < (RS ? 13 : ET_COLS)) {
         double s = 0.0;
         for (int i = 0; i < BM_T / 64; ++i) s += red[threadIdx.x][i];
-        part[(cell * P + w) * ET_ROW + threadIdx.x] = s;
+        part[(cell * P + w) * ROW + threadIdx.x] = s;
+    } else if (RS && threadIdx.x < 15) {
+        double s = red[threadIdx.x][0];
+        for (int i = 1; i < BM_T / 64; ++i) s = fmin(s, red[threadIdx.x][i]);
+        part[(cell * P + w) * ROW + threadIdx.x] = s;
     }
     for (int b = threadIdx.x; b < 2 * BM_BINS; b += BM_T) slab[(cell * P + w) * ET_SLAB + b] = both[b];
     if (!bm_ticket(cell, P, tickets, &flag)) return;
 
     // last arrival of (pair, variant): the P <= 32 rows through LDS, one thread per column adds them in index order
-    const double *rows = part + cell * P * ET_ROW;
-    for (int i = threadIdx.x; i < P * ET_ROW; i += BM_T) stage[i] = bm_ld(rows + i);
+    const double *rows = part + cell * P * ROW;
+    for (int i = threadIdx.x; i < P * ROW; i += BM_T) stage[i] = bm_ld(rows + i);
     __syncthreads();
-    if (threadIdx.x < ET_COLS) {
+    if (threadIdx.x < (RS ? 13 : ET_COLS)) {
         double s = 0.0;
-        for (int r = 0; r < P; ++r) s += stage[r * ET_ROW + threadIdx.x];
+        for (int r = 0; r < P; ++r) s += stage[r * ROW + threadIdx.x];
         red[threadIdx.x][0] = s;
-        out[cell * ET_OUT + threadIdx.x] = s;
-    } else if (threadIdx.x < ET_OUT) {
+        if (!RS) out[cell * ET_OUT + threadIdx.x] = s;
+    } else if (RS && threadIdx.x < 15) {
+        double s = stage[threadIdx.x];
+        for (int r = 1; r < P; ++r) s = fmin(s, stage[r * ROW + threadIdx.x]);
+        red[threadIdx.x][0] = s;
+    } else if (!RS && threadIdx.x < ET_OUT) {
         out[cell * ET_OUT + threadIdx.x] = threadIdx.x < 13 ? (double)__uint_as_float(0x7fc00000u) : 0.0;      // (pass 3 writes the medians it finds)
     }
     __syncthreads();
     const unsigned total = (unsigned)red[1][0];
     const bool wanted = total != 0 && red[0][0] == red[1][0];
     unsigned *st = state + cell * ET_STATE;
+    if (RS) {
+        // the row of a variant that takes no part in the later passes, and what pass 4 leaves alone; it overwrites columns 2..12 of the others
+        if (threadIdx.x < ET_OUT) {
+            const int c = threadIdx.x;
+            out[cell * ET_OUT + c] = c < 2 ? red[c][0] : ((c < 8 || c == 11 || c == 12) ? (double)__uint_as_float(0x7fc00000u) : 0.0);
+        }
+        if (threadIdx.x < 2) cst[cell * ET_CST + threadIdx.x] = red[11 + threadIdx.x][0] / red[1][0];
+        else if (threadIdx.x < 4) cst[cell * ET_CST + threadIdx.x] = red[11 + threadIdx.x][0];
+    }
     if (wanted) {
         const unsigned r0 = (total - 1) / 2, r1 = total / 2;
         for (int s = 0; s < 2; ++s) {
@@ -566,12 +615,16 @@ __global__ void __launch_bounds__(BM_T) et_sums_kernel(const float *const *__res
     }
 }
 
-template <int SHIFT>
+// RS, SHIFT = 10: the sums of (t - mean t)^2 and (p - mean p)^2 ride along (rows of ET_ROWX doubles, columns 0 and 1) and the last arrival
+// leaves both standard deviations in cst.  RS, SHIFT = 0: the middle values stay in the state for pass 4, which writes the medians.
+template <int SHIFT, bool RS>
 __global__ void __launch_bounds__(BM_T) et_select_kernel(const float *const *__restrict__ preds, const float *const *__restrict__ targets,
                                                          const unsigned char *const *__restrict__ masks, et_args_t a, unsigned *tickets, unsigned *state,
-                                                         unsigned *slab, double *__restrict__ out) {
+                                                         double *part, unsigned *slab, double *cst, double *__restrict__ out) {
     constexpr int NB = BM_BINS / 2;
+    constexpr bool DEV = RS && SHIFT == 10;
     __shared__ unsigned hist[4][NB];
+    __shared__ double red[2][BM_T / 64];
     __shared__ unsigned scan[BM_T / 64], res[2];
     __shared__ int flag;
     const int w = blockIdx.x, v = blockIdx.y, P = a.Ws;
@@ -587,20 +640,41 @@ __global__ void __launch_bounds__(BM_T) et_select_kernel(const float *const *__r
         for (int b = threadIdx.x; b < NB; b += BM_T) hist[h][b] = 0;
     __syncthreads();
     const et_view_t vw(preds, targets, masks, a, w, v, g);
+    const double mean_t = DEV ? cst[cell * ET_CST] : 0.0, mean_p = DEV ? cst[cell * ET_CST + 1] : 0.0;
+    double dev_t = 0.0, dev_p = 0.0;
     et_sweep(vw.p, vw.t, vw.m, vw.lo, vw.hi, [&](float pn, float tn, unsigned char mv) {
         float t;
         bool nan;
         if (!vw.inside(tn, mv, t, nan) || nan) return;
-        const unsigned kt = et_key(t), kp = et_key(vw.pred(pn));
+        const float p = vw.pred(pn);
+        if (DEV) {
+            const double et = (double)t - mean_t, ep = (double)p - mean_p;
+            dev_t += et * et, dev_p += ep * ep;
+        }
+        const unsigned kt = et_key(t), kp = et_key(p);
         const unsigned tt = kt >> (SHIFT + 10), tp = kp >> (SHIFT + 10);
         if (tt == pre[0]) atomicAdd(&hist[0][(kt >> SHIFT) & (NB - 1)], 1u);
         else if (tt == pre[1]) atomicAdd(&hist[1][(kt >> SHIFT) & (NB - 1)], 1u);
         if (tp == pre[2]) atomicAdd(&hist[2][(kp >> SHIFT) & (NB - 1)], 1u);
         else if (tp == pre[3]) atomicAdd(&hist[3][(kp >> SHIFT) & (NB - 1)], 1u);
     });
+    if (DEV) {
+        const double st_ = bm_wave_sum(dev_t), sp_ = bm_wave_sum(dev_p);
+        if ((threadIdx.x & 63) == 0) red[0][threadIdx.x >> 6] = st_, red[1][threadIdx.x >> 6] = sp_;
+    }
     __syncthreads();
+    if (DEV && threadIdx.x < 2) {
+        double s = 0.0;
+        for (int i = 0; i < BM_T / 64; ++i) s += red[threadIdx.x][i];
+        part[(cell * P + w) * ET_ROWX + threadIdx.x] = s;
+    }
     if (!et_arrive(hist, 1u | (two_t ? 2u : 0u) | 4u | (two_p ? 8u : 0u), slab, cell, P, w, tickets, &flag)) return;
 
+    if (DEV && threadIdx.x < 2) {                                 // np.std: sqrt(mean((x - mean(x))^2)), the rows in index order
+        double s = 0.0;
+        for (int r = 0; r < P; ++r) s += bm_ld(part + (cell * P + r) * ET_ROWX + threadIdx.x);
+        cst[cell * ET_CST + 4 + threadIdx.x] = sqrt(s / (double)total);
+    }
     unsigned found[4], inside[4];
     for (int s = 0; s < 2; ++s) {
         const bool two = s ? two_p : two_t;
@@ -614,7 +688,7 @@ __global__ void __launch_bounds__(BM_T) et_select_kernel(const float *const *__r
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        if (SHIFT) {
+        if (SHIFT || RS) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) st[2 * k] = found[k], st[2 * k + 1] = inside[k];
         } else {
@@ -626,6 +700,96 @@ __global__ void __launch_bounds__(BM_T) et_select_kernel(const float *const *__r
         }
         atomicExch(tickets + cell, 0u);
     }
+}
+
+// Pass 4 of a rescaled call: columns 2..12 of the row on the transformed pair (the header of this section; include/ramnet_hip.h).
+__global__ void __launch_bounds__(BM_T) et_rescale_kernel(const float *const *__restrict__ preds, const float *const *__restrict__ targets,
+                                                          const unsigned char *const *__restrict__ masks, et_args_t a, unsigned *tickets,
+                                                          const unsigned *state, double *part, const double *cst, double *__restrict__ out) {
+    __shared__ double red[ET_COLS][BM_T / 64], stage[ET_MAX_PER_MAP * ET_ROWX];
+    __shared__ int flag;
+    const int w = blockIdx.x, v = blockIdx.y, P = a.Ws;
+    const size_t g = blockIdx.z, cell = g * a.V + v;
+    const unsigned *st = state + cell * ET_STATE;
+    if (st[9] == 0) return;                                       // its row was written by pass 1, no ticket is taken
+    const bool odd = (st[8] & 1u) != 0;
+    const double *c = cst + cell * ET_CST;
+    double med[2], sd[2], off[2], m[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const float fa = __uint_as_float(st[4 * s]), fb = __uint_as_float(st[4 * s + 2]);
+        med[s] = (double)(odd ? fa : (fa + fb) * 0.5f);           // np.median of the float32 values
+        sd[s] = c[4 + s];
+        off[s] = fabs((c[2 + s] - med[s]) / sd[s]);
+        const double ta = ((double)fa - med[s]) / sd[s] + off[s], tb = ((double)fb - med[s]) / sd[s] + off[s];
+        m[s] = odd ? ta : (ta + tb) * 0.5;
+    }
+    const double md = fabs(m[0] - m[1]);
+    const bool up_t = m[0] < m[1];                                // the side with the smaller median is lifted (a NaN: the prediction)
+    const et_view_t vw(preds, targets, masks, a, w, v, g);
+    double acc[ET_COLS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const double eps = 1e-5;
+    et_sweep(vw.p, vw.t, vw.m, vw.lo, vw.hi, [&](float pn, float tn, unsigned char mv) {
+        float tf;
+        bool nan;
+        if (!vw.inside(tn, mv, tf, nan) || nan) return;
+        double t = ((double)tf - med[0]) / sd[0] + off[0], p = ((double)vw.pred(pn) - med[1]) / sd[1] + off[1];
+        if (up_t) t += md;
+        else p += md;
+        const double d = t - p, ld = log(t + eps) - log(p + eps);
+        acc[2] += fabs(d) / (t + 1e-6), acc[3] += d * d / (t * t + 1e-6), acc[4] += d * d;
+        acc[5] += ld * ld, acc[6] += fabs(ld), acc[7] += fabs(d);
+        const double r = fmax(t / (p + eps), p / (t + eps));
+        acc[8] += r <= 1.25, acc[9] += r <= 1.5625, acc[10] += r <= 1.953125;
+    });
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 2; k < ET_COLS; ++k) {
+        const double s = bm_wave_sum(acc[k]);
+        if (lane == 0) red[k][wave] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x >= 2 && threadIdx.x < ET_COLS) {
+        double s = 0.0;
+        for (int i = 0; i < BM_T / 64; ++i) s += red[threadIdx.x][i];
+        part[(cell * P + w) * ET_ROWX + threadIdx.x] = s;
+    }
+    if (!bm_ticket(cell, P, tickets, &flag)) return;
+
+    const double *rows = part + cell * P * ET_ROWX;
+    for (int i = threadIdx.x; i < P * ET_ROWX; i += BM_T) stage[i] = bm_ld(rows + i);
+    __syncthreads();
+    if (threadIdx.x >= 2 && threadIdx.x < ET_COLS) {
+        double s = 0.0;
+        for (int r = 0; r < P; ++r) s += stage[r * ET_ROWX + threadIdx.x];
+        out[cell * ET_OUT + threadIdx.x] = s;
+    } else if (threadIdx.x == 11) {
+        out[cell * ET_OUT + 11] = up_t ? m[0] + md : m[0];
+    } else if (threadIdx.x == 12) {
+        out[cell * ET_OUT + 12] = up_t ? m[1] : m[1] + md;
+    }
+    if (threadIdx.x == 0) atomicExch(tickets + cell, 0u);
+}
+
+// Metric targets at reduced resolution (evaluation.py:87-94): F.interpolate(metric target, scale_factor = s, mode = 'bilinear') at its
+// defaults — align_corners = False, source coordinate (dst + 0.5) / s - 0.5 from the GIVEN factor, clamped at 0 — on the metric depths of
+// et_metric_depth (no clamp), the four products in double, rounded once to float32.  A NaN tap makes the output NaN, at weight zero too.
+__global__ void __launch_bounds__(256) resize_metric_target_kernel(const float *const *__restrict__ targets, int H, int W, int Ho, int Wo, double rs,
+                                                                   float clip, float reg, float *__restrict__ out) {
+    const size_t g = blockIdx.y, n = (size_t)Ho * Wo;
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int oy = (int)(i / Wo), ox = (int)(i % Wo);
+    const double sy = fmax(rs * ((double)oy + 0.5) - 0.5, 0.0), sx = fmax(rs * ((double)ox + 0.5) - 0.5, 0.0);
+    const int y0 = min((int)sy, H - 1), x0 = min((int)sx, W - 1);
+    const int y1 = y0 + (y0 < H - 1), x1 = x0 + (x0 < W - 1);
+    const double ly = sy - (double)y0, lx = sx - (double)x0;
+    const float *t = targets[g];
+    const double t00 = (double)et_metric_depth(t[(size_t)y0 * W + x0], reg, clip, 0.f, false);
+    const double t01 = (double)et_metric_depth(t[(size_t)y0 * W + x1], reg, clip, 0.f, false);
+    const double t10 = (double)et_metric_depth(t[(size_t)y1 * W + x0], reg, clip, 0.f, false);
+    const double t11 = (double)et_metric_depth(t[(size_t)y1 * W + x1], reg, clip, 0.f, false);
+    out[g * n + i] = (float)((1.0 - ly) * ((1.0 - lx) * t00 + lx * t01) + ly * ((1.0 - lx) * t10 + lx * t11));
 }
 
 __global__ void __launch_bounds__(256) metric_depth_kernel(const float *__restrict__ y, size_t n, float clip, float reg, int clamp, float *__restrict__ out) {
@@ -645,31 +809,73 @@ extern "C" int ramnet_metric_depth(const float *y, size_t n, float clip_distance
     return 0;
 }
 
+static int et_launch(const float *const *pred, const float *const *target, const unsigned char *const *mask, int G, size_t npix, float clip_distance,
+                     float reg_factor, const float *cutoffs, int ncut, int flags, void *workspace, double *out, void *stream) {
+    RAMNET_CHECK_ARG(pred && target && workspace && out && clip_distance > 0.f);
+    RAMNET_CHECK_ARG(et_sizes_ok(G, npix, ncut, mask != nullptr));
+    RAMNET_CHECK_ARG(ncut == 0 || cutoffs);
+    for (int i = 0; i < ncut; ++i) RAMNET_CHECK_ARG(cutoffs[i] > (i ? cutoffs[i - 1] : 0.f));
+    RAMNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0);
+    RAMNET_CHECK_ARG((flags & ~(RAMNET_EVAL_RESCALE | RAMNET_EVAL_TARGET_METRIC)) == 0);
+    const bool rescale = (flags & RAMNET_EVAL_RESCALE) != 0;
+    const et_plan_t pl = et_plan(G, npix, ncut, mask != nullptr, rescale);
+    et_args_t a;
+    a.clip = clip_distance, a.reg = reg_factor, a.ncut = ncut, a.V = pl.V, a.Ws = pl.Ws, a.npix = (unsigned)npix;
+    a.tmetric = (flags & RAMNET_EVAL_TARGET_METRIC) != 0;
+    for (int i = 0; i < ET_MAXCUT; ++i) a.cut[i] = i < ncut ? cutoffs[i] : 0.f;
+    char *ws = static_cast<char *>(workspace);
+    unsigned *tickets = reinterpret_cast<unsigned *>(ws), *state = reinterpret_cast<unsigned *>(ws + pl.off_state);
+    double *part = reinterpret_cast<double *>(ws + pl.off_part), *cst = reinterpret_cast<double *>(ws + pl.off_cst);
+    unsigned *slab = reinterpret_cast<unsigned *>(ws + pl.off_slab);
+    const dim3 grid(pl.Ws, pl.V, G);
+    hipStream_t st = (hipStream_t)stream;
+    if (rescale) {
+        hipLaunchKernelGGL(et_sums_kernel<true>, grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, part, slab, cst, out);
+        hipLaunchKernelGGL((et_select_kernel<10, true>), grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, part, slab, cst, out);
+        hipLaunchKernelGGL((et_select_kernel<0, true>), grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, part, slab, cst, out);
+        hipLaunchKernelGGL(et_rescale_kernel, grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, part, cst, out);
+        RAMNET_LAUNCH_CHECK();
+        note_kernel("et_sums_kernel<rescale> + et_select_kernel<10> + et_select_kernel<0> + et_rescale_kernel");
+        return 0;
+    }
+    hipLaunchKernelGGL(et_sums_kernel<false>, grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, part, slab, cst, out);
+    hipLaunchKernelGGL((et_select_kernel<10, false>), grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, part, slab, cst, out);
+    hipLaunchKernelGGL((et_select_kernel<0, false>), grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, part, slab, cst, out);
+    RAMNET_LAUNCH_CHECK();
+    note_kernel("et_sums_kernel + et_select_kernel<10> + et_select_kernel<0>");
+    return 0;
+}
+
 extern "C" size_t ramnet_eval_table_workspace(int G, size_t npix, int ncut, int has_mask) {
     return et_sizes_ok(G, npix, ncut, has_mask) ? et_plan(G, npix, ncut, has_mask).total : 0;
 }
 
 extern "C" int ramnet_eval_table(const float *const *pred, const float *const *target, const unsigned char *const *mask, int G, size_t npix,
                                  float clip_distance, float reg_factor, const float *cutoffs, int ncut, void *workspace, double *out, void *stream) {
-    RAMNET_CHECK_ARG(pred && target && workspace && out && clip_distance > 0.f);
-    RAMNET_CHECK_ARG(et_sizes_ok(G, npix, ncut, mask != nullptr));
-    RAMNET_CHECK_ARG(ncut == 0 || cutoffs);
-    for (int i = 0; i < ncut; ++i) RAMNET_CHECK_ARG(cutoffs[i] > (i ? cutoffs[i - 1] : 0.f));
-    RAMNET_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 255) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0);
-    const et_plan_t pl = et_plan(G, npix, ncut, mask != nullptr);
-    et_args_t a;
-    a.clip = clip_distance, a.reg = reg_factor, a.ncut = ncut, a.V = pl.V, a.Ws = pl.Ws, a.npix = (unsigned)npix;
-    for (int i = 0; i < ET_MAXCUT; ++i) a.cut[i] = i < ncut ? cutoffs[i] : 0.f;
-    char *ws = static_cast<char *>(workspace);
-    unsigned *tickets = reinterpret_cast<unsigned *>(ws), *state = reinterpret_cast<unsigned *>(ws + pl.off_state);
-    double *part = reinterpret_cast<double *>(ws + pl.off_part);
-    unsigned *slab = reinterpret_cast<unsigned *>(ws + pl.off_slab);
-    const dim3 grid(pl.Ws, pl.V, G);
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(et_sums_kernel, grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, part, slab, out);
-    hipLaunchKernelGGL(et_select_kernel<10>, grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, slab, out);
-    hipLaunchKernelGGL(et_select_kernel<0>, grid, dim3(BM_T), 0, st, pred, target, mask, a, tickets, state, slab, out);
+    return et_launch(pred, target, mask, G, npix, clip_distance, reg_factor, cutoffs, ncut, 0, workspace, out, stream);
+}
+
+extern "C" size_t ramnet_eval_table_ex_workspace(int G, size_t npix, int ncut, int has_mask, int flags) {
+    if ((flags & ~(RAMNET_EVAL_RESCALE | RAMNET_EVAL_TARGET_METRIC)) != 0 || !et_sizes_ok(G, npix, ncut, has_mask)) return 0;
+    return et_plan(G, npix, ncut, has_mask, (flags & RAMNET_EVAL_RESCALE) != 0).total;
+}
+
+extern "C" int ramnet_eval_table_ex(const float *const *pred, const float *const *target, const unsigned char *const *mask, int G, size_t npix,
+                                    float clip_distance, float reg_factor, const float *cutoffs, int ncut, int flags, void *workspace, double *out,
+                                    void *stream) {
+    return et_launch(pred, target, mask, G, npix, clip_distance, reg_factor, cutoffs, ncut, flags, workspace, out, stream);
+}
+
+extern "C" int ramnet_resize_metric_target(const float *const *target, int G, int H, int W, double scale_factor, float clip_distance, float reg_factor,
+                                           float *out, void *stream) {
+    RAMNET_CHECK_ARG(target && out && clip_distance > 0.f);
+    RAMNET_CHECK_ARG(G >= 1 && G <= 65535 && H >= 1 && W >= 1 && (size_t)H * W < ((size_t)1 << 31));
+    RAMNET_CHECK_ARG(scale_factor > 0.0 && scale_factor <= 1.0);
+    const int Ho = (int)floor((double)H * scale_factor), Wo = (int)floor((double)W * scale_factor);
+    RAMNET_CHECK_ARG(Ho >= 1 && Wo >= 1);
+    const size_t n = (size_t)Ho * Wo;
+    hipLaunchKernelGGL(resize_metric_target_kernel, dim3((unsigned)((n + 255) / 256), G), dim3(256), 0, (hipStream_t)stream, target, H, W, Ho, Wo,
+                       1.0 / scale_factor, clip_distance, reg_factor, out);
     RAMNET_LAUNCH_CHECK();
-    note_kernel("et_sums_kernel + et_select_kernel<10> + et_select_kernel<0>");
     return 0;
 }

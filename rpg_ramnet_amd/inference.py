@@ -35,7 +35,7 @@ def _time_batched_ok(model):
 
 
 def stream_dataset(model, dataset, every_x_rgb_frame, output_folder=None, settle=2, calculate_scale=False,
-                   reg_factor=5.70378, clip_distance=1000.0, max_items=None, time_batched="auto", table=None):
+                   reg_factor=5.70378, clip_distance=1000.0, max_items=None, time_batched="auto", table=None, rescale=False):
     """Run ``model`` over ``dataset`` (items ``(sequence, dataset_idx)``, sequence_length 1) the way test.py does and
     optionally write predictions / targets as .npy.  Returns {'items', 'saved', 'scale': (mean, min, max) or None}.
 
@@ -45,7 +45,8 @@ def stream_dataset(model, dataset, every_x_rgb_frame, output_folder=None, settle
 
     table: a dict prediction key -> ``metrics.EvalTable``, or True to create one per prediction key from ``clip_distance`` /
     ``reg_factor``: every package past ``settle`` adds each prediction with its ``depth_<key>`` target to that key's table while it is
-    still on the device — no ``output_folder`` and no read-back inside the loop; the tables come back under ``info["tables"]``."""
+    still on the device — no ``output_folder`` and no read-back inside the loop; the tables come back under ``info["tables"]``.
+    rescale: the tables that ``table=True`` creates are rescaled ones (evaluation.py's --rescale)."""
     tables = {} if table is True else table
     was_training = model.training
     model.eval()
@@ -94,7 +95,7 @@ def stream_dataset(model, dataset, every_x_rgb_frame, output_folder=None, settle
                     if key not in tables:
                         if table is not True:
                             continue
-                        tables[key] = EvalTable(clip_distance, reg_factor)
+                        tables[key] = EvalTable(clip_distance, reg_factor, rescale=rescale)
                     tables[key].add([img[0]], [package['depth_' + key][0]])      # (launched now: img is a view of a static buffer)
             if calculate_scale:      # least-squares scale between metric prediction and target (test.py:365-378; last key wins there, too)
                 for key, img in preds.items():
@@ -142,12 +143,15 @@ def evaluate_folders(predictions_dir, targets_dir, clip_distance, reg_factor, cr
 
 
 def evaluate_table(predictions_dir, targets_dir, clip_distance, reg_factor, crop_ymax=None, prediction_offset=0, target_offset=0,
-                   cutoffs=EVAL_CUTOFFS, event_masks_dir=None, batch_files=64, skip_empty=True, device="cuda:0"):
+                   cutoffs=EVAL_CUTOFFS, event_masks_dir=None, batch_files=64, skip_empty=True, device="cuda:0", rescale=False,
+                   down_scale_factor=1.0):
     """evaluation.py:295-397 with the whole table on the device: the file pairing of ``evaluate_folders``, ``batch_files`` files at a time
     into one ``metrics.EvalTable`` (three launches per batch, one read-back at the end), all ten metrics for all pixels and every cut-off.
     event_masks_dir: the sorted ``*png`` event frames of that folder, from ``prediction_offset`` on, give the ``event_masked_*`` half of the
     table (mask = ``sum(frame.astype(float32), -1) > 0``, cropped like the maps; evaluation.py:371-390).
-    skip_empty: ``evaluate_folders``' rule (True) or the reference's sum / number of files (False), see ``metrics.finish_eval_rows``."""
+    skip_empty: ``evaluate_folders``' rule (True) or the reference's sum / number of files (False), see ``metrics.finish_eval_rows``.
+    rescale / down_scale_factor: evaluation.py's --rescale and --down_scale_factor, see ``metrics.EvalTable``; ``crop_ymax`` is applied to
+    every map first, as the reference does, and event frames must already have the size of the predictions."""
     p_files = sorted(glob.glob(join(predictions_dir, '*.npy')))[prediction_offset:]
     t_files = sorted(glob.glob(join(targets_dir, '*.npy')))[target_offset:]
     assert len(p_files) > 0 and len(t_files) > 0
@@ -157,22 +161,23 @@ def evaluate_table(predictions_dir, targets_dir, clip_distance, reg_factor, crop
         from .data import _imread
         e_files = sorted(glob.glob(join(event_masks_dir, '*png')))[prediction_offset:]
         assert len(e_files) >= len(pairs), "%d event frames for %d file pairs" % (len(e_files), len(pairs))
-    tab = EvalTable(clip_distance, reg_factor, cutoffs)
+    tab = EvalTable(clip_distance, reg_factor, cutoffs, rescale=rescale, down_scale_factor=down_scale_factor)
+    same_size = down_scale_factor >= 1.0
     for i0 in range(0, len(pairs), batch_files):
         ps, ts, ms = [], [], []
         for i in range(i0, min(i0 + batch_files, len(pairs))):
             t, p = np.load(pairs[i][1])[0], np.load(pairs[i][0])[0]
             if crop_ymax is not None:
                 t, p = t[:crop_ymax], p[:crop_ymax]
-            assert p.shape == t.shape
+            assert p.shape == t.shape or not same_size
             ps.append(p), ts.append(t)
             if e_files is not None:
                 frame = _imread(e_files[i])
                 frame = frame[:crop_ymax] if crop_ymax is not None else frame
                 m = np.sum(frame.astype("float32").reshape(frame.shape[:2] + (-1,)), axis=-1) > 0
-                assert m.shape == t.shape
+                assert m.shape == t.shape or not same_size      # (a down-scaled table checks the masks against the predictions itself)
                 ms.append(m)
-        if len(set(p.shape for p in ps)) == 1:                      # one upload per batch
+        if len(set(p.shape for p in ps)) == 1 and len(set(t.shape for t in ts)) == 1:                      # one upload per batch
             tab.add(torch.from_numpy(np.stack(ps)).to(device), torch.from_numpy(np.stack(ts)).to(device),
                     torch.from_numpy(np.stack(ms)).to(device) if e_files is not None else None)
         else:                                                       # (recordings of different resolution in one folder: one call per file)

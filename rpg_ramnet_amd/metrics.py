@@ -10,7 +10,9 @@ normalised log-depth maps themselves: `batch_metrics` computes all of them for a
 reduction (exact median included) and leaves the table on the device; `eval_metrics` is the one-pair drop-in for `_eval_metrics`.
 
 `EvalTable` is the batched form of the evaluation table: all ten rows for any number of files, every depth cut-off and the event-masked
-half (evaluation.py:359-390) in three launches per batch, rows kept on the device, one read-back (`finish_eval_rows` is its host part)."""
+half (evaluation.py:359-390) in three launches per batch, rows kept on the device, one read-back (`finish_eval_rows` is its host part).
+`rescale=True` is evaluation.py's --rescale (rescale_by_the_median before the metrics, a fourth launch), `down_scale_factor` its
+--down_scale_factor (the metric target resized on the device by `resize_metric_target`)."""
 import ctypes as C
 import math
 
@@ -169,6 +171,7 @@ EVAL_KEYS = ("abs_rel_diff", "squ_rel_diff", "RMS_linear", "RMS_log", "SILog", "
 EVAL_CUTOFFS = (10, 20, 30, 80, 250, 500)       # depth_values of evaluation.py
 EVAL_ROW = 16           # doubles of a row of ramnet_eval_table (include/ramnet_hip.h lists the columns)
 EVAL_TICKET_BYTES = 262144   # RAMNET_EVAL_TABLE_TICKET_BYTES
+EVAL_RESCALE, EVAL_TARGET_METRIC = 1, 2      # RAMNET_EVAL_RESCALE, RAMNET_EVAL_TARGET_METRIC: flags of ramnet_eval_table_ex
 
 _eval_workspaces = {}   # (device index, raw stream) -> uint8 workspace of ramnet_eval_table (tickets zeroed once, at allocation)
 
@@ -185,6 +188,45 @@ def metric_depth(y, clip_distance, reg_factor, clamp=False):
         with torch.cuda.device(x.device):
             H.check(H.lib().ramnet_metric_depth(_p(x), x.numel(), float(clip_distance), float(reg_factor), int(bool(clamp)), _p(out), _st()),
                     "ramnet_metric_depth")
+    return out
+
+
+def _fill_table(device, ptrs, rows):
+    """Device table [rows, len(ptrs) / rows] of int64 pointers, written by kernel argument on the current stream."""
+    tab = torch.empty((rows, len(ptrs) // rows), device=device, dtype=torch.int64)
+    host = (C.c_void_p * len(ptrs))(*ptrs)
+    H.check(H.lib().ramnet_fill_pointer_table(C.c_void_p(tab.data_ptr()), host, len(ptrs), _st()), "ramnet_fill_pointer_table")
+    return tab
+
+
+def resized_shape(shape, scale_factor):
+    """(H', W') of a map resized by F.interpolate(..., scale_factor=s): floor(H * s), floor(W * s)."""
+    return int(math.floor(shape[-2] * float(scale_factor))), int(math.floor(shape[-1] * float(scale_factor)))
+
+
+def resize_metric_target(targets, clip_distance, reg_factor, scale_factor):
+    """The target side of prepare_depth_data with down_scale_factor < 1 (evaluation.py:87-94) on the device: targets = a list of H x W
+    maps or a [G, 1, H, W] / [G, H, W] tensor of normalised log depth -> [G, H', W'] float32 METRIC depth, the bilinear interpolation of
+    the metric depths with F.interpolate's default coordinates (align_corners=False, the given factor).  One launch for the G maps."""
+    s = float(scale_factor)
+    if not 0.0 < s <= 1.0:
+        raise ValueError("resize_metric_target: scale_factor must be in (0, 1], got %r" % (scale_factor,))
+    first = targets[0]
+    device = first.device
+    if device.type != "cuda":
+        raise ValueError("resize_metric_target: the targets must live on the GPU (no CPU fallback)")
+    with torch.cuda.device(device):
+        ts = _eval_maps(targets, device, torch.float32, "targets")
+        shape = tuple(ts[0].shape[-2:])
+        if any(t is None or t.numel() != shape[0] * shape[1] or tuple(t.shape[-2:]) != shape for t in ts):
+            raise ValueError("resize_metric_target: every target is one %s map" % (shape,))
+        Ho, Wo = resized_shape(shape, s)
+        if Ho < 1 or Wo < 1:
+            raise ValueError("resize_metric_target: %s maps have no pixel left at scale_factor %r" % (shape, scale_factor))
+        tab = _fill_table(device, [t.data_ptr() for t in ts], 1)
+        out = torch.empty((len(ts), Ho, Wo), device=device, dtype=torch.float32)
+        H.check(H.lib().ramnet_resize_metric_target(C.c_void_p(tab.data_ptr()), len(ts), shape[0], shape[1], s, float(clip_distance),
+                                                    float(reg_factor), _p(out), _st()), "ramnet_resize_metric_target")
     return out
 
 
@@ -254,9 +296,12 @@ class EvalTable:
     ramnet_eval_table for its maps at once and appends their rows to a device-side table without a synchronisation; `result` reads the
     table back once and averages over the files on the host."""
 
-    def __init__(self, clip_distance, reg_factor, cutoffs=EVAL_CUTOFFS):
+    def __init__(self, clip_distance, reg_factor, cutoffs=EVAL_CUTOFFS, rescale=False, down_scale_factor=1.0):
         self.clip_distance, self.reg_factor = float(clip_distance), float(reg_factor)
         self.cutoffs = tuple(cutoffs)
+        self.rescale, self.down_scale_factor = bool(rescale), float(down_scale_factor)
+        if not 0.0 < self.down_scale_factor <= 1.0:
+            raise ValueError("EvalTable: down_scale_factor must be in (0, 1], got %r" % (down_scale_factor,))
         if len(self.cutoffs) > 8 or any(not b > a for a, b in zip((0,) + self.cutoffs, self.cutoffs)):
             raise ValueError("EvalTable: at most 8 ascending positive cut-offs, got %r" % (self.cutoffs,))
         self._cut = (C.c_float * max(len(self.cutoffs), 1))(*[float(c) for c in self.cutoffs])
@@ -269,7 +314,8 @@ class EvalTable:
         """preds / targets: lists of same-shape maps (targets may live on the host: moved once) or [G, 1, H, W] / [G, H, W] tensors;
         masks: the same of uint8 / bool (non-zero = inside the event mask; a list entry may be None: all inside).  Enqueued on the
         current stream for exactly these maps; no reference to them is kept (what had to be copied belongs to the stream-ordered allocator).
-        Returns the [G, V, 16] rows (device)."""
+        down_scale_factor < 1: predictions (and masks) are H' x W' = floor(H s) x floor(W s), targets H x W; the metric targets are resized
+        on the device first.  Returns the [G, V, 16] rows (device)."""
         has_mask = masks is not None
         if self.has_mask is None:
             self.has_mask = has_mask
@@ -290,6 +336,21 @@ class EvalTable:
             if G == 0 or len(ts) != G or (has_mask and len(ms) != G):
                 raise ValueError("EvalTable.add: %d predictions, %d targets, %s masks" % (G, len(ts), len(ms) if has_mask else "no"))
             npix = ps[0].numel()
+            flags = EVAL_RESCALE if self.rescale else 0
+            if self.down_scale_factor < 1.0:
+                if any(p is None or t is None or t.dim() < 2 or p.dim() < 2 for p, t in zip(ps, ts)):
+                    raise ValueError("EvalTable.add: a down-scaled table takes 2-D maps")
+                small = tuple(ps[0].shape[-2:])
+                for p, t in zip(ps, ts):
+                    if tuple(p.shape[-2:]) != small or p.numel() != npix or resized_shape(t.shape, self.down_scale_factor) != small:
+                        raise ValueError("EvalTable.add: predictions are %s, targets must resize to that by %r, got %s -> %s"
+                                         % (small, self.down_scale_factor, tuple(t.shape), resized_shape(t.shape, self.down_scale_factor)))
+                for m in ms:
+                    if m is not None and (tuple(m.shape[-2:]) != small or m.numel() != npix):
+                        raise ValueError("EvalTable.add: masks must have the size of the predictions, %s, got %s (resized event frames are not "
+                                         "covered)" % (small, tuple(m.shape)))
+                ts = list(resize_metric_target(ts, self.clip_distance, self.reg_factor, self.down_scale_factor))
+                flags |= EVAL_TARGET_METRIC
             for p, t in zip(ps, ts):
                 if p is None or t is None or p.numel() != npix or t.numel() != npix:
                     raise ValueError("EvalTable.add: every prediction and target holds %d pixels" % npix)
@@ -297,7 +358,8 @@ class EvalTable:
                 if m is not None and (m.numel() != npix or m.dtype != torch.uint8):
                     raise ValueError("EvalTable.add: every mask holds %d uint8 / bool pixels" % npix)
             L = H.lib()
-            nbytes = L.ramnet_eval_table_workspace(G, npix, len(self.cutoffs), int(has_mask))
+            nbytes = L.ramnet_eval_table_ex_workspace(G, npix, len(self.cutoffs), int(has_mask), flags) if flags else \
+                L.ramnet_eval_table_workspace(G, npix, len(self.cutoffs), int(has_mask))
             if nbytes == 0:
                 raise ValueError("EvalTable.add: unsupported sizes G=%d npix=%d cut-offs=%d" % (G, npix, len(self.cutoffs)))
             key = (device.index, _st().value or 0)
@@ -312,10 +374,16 @@ class EvalTable:
             H.check(L.ramnet_fill_pointer_table(C.c_void_p(tab.data_ptr()), host, len(ptrs), _st()), "ramnet_fill_pointer_table")
             V = (1 + len(self.cutoffs)) * (2 if has_mask else 1)
             out = torch.empty((G, V, EVAL_ROW), device=device, dtype=torch.float64)
-            H.check(L.ramnet_eval_table(C.c_void_p(tab[0].data_ptr()), C.c_void_p(tab[1].data_ptr()),
-                                        C.c_void_p(tab[2].data_ptr()) if has_mask else None, G, npix, self.clip_distance, self.reg_factor,
-                                        self._cut, len(self.cutoffs), C.c_void_p(ws.data_ptr()), C.c_void_p(out.data_ptr()), _st()),
-                    "ramnet_eval_table")
+            if flags:
+                H.check(L.ramnet_eval_table_ex(C.c_void_p(tab[0].data_ptr()), C.c_void_p(tab[1].data_ptr()),
+                                               C.c_void_p(tab[2].data_ptr()) if has_mask else None, G, npix, self.clip_distance, self.reg_factor,
+                                               self._cut, len(self.cutoffs), flags, C.c_void_p(ws.data_ptr()), C.c_void_p(out.data_ptr()), _st()),
+                        "ramnet_eval_table_ex")
+            else:
+                H.check(L.ramnet_eval_table(C.c_void_p(tab[0].data_ptr()), C.c_void_p(tab[1].data_ptr()),
+                                            C.c_void_p(tab[2].data_ptr()) if has_mask else None, G, npix, self.clip_distance, self.reg_factor,
+                                            self._cut, len(self.cutoffs), C.c_void_p(ws.data_ptr()), C.c_void_p(out.data_ptr()), _st()),
+                        "ramnet_eval_table")
         self._chunks.append(out)
         return out
 

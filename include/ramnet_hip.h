@@ -342,6 +342,15 @@ int ramnet_unpack_wgrad_wino2x4(const float *ws, float *grad_oihw, int Cout, int
                                 void *stream);
 
 /* ---- the two MFMA kernels ----------------------------------------------------------------------- */
+/* What ramnet_conv_launch / ramnet_conv_launch_multi refuse (RAMNET_E_BADARG, nothing launched) on RAMNET_ALGO_DIRECT, _WINOGRAD, _WINOGRAD_2X4 and
+ * _WINOGRAD_2X4_SPLIT besides the conditions stated at the fields: a leading dimension below the channels addressed through it — ld0 < C0, ld1 < C1
+ * (CAT*), ldm < C1 (CAT_MUL) or < C0 (RELUMASK), ldo < Cout (< out_s2d under out_s2d), and of the epilogue operands lde0 < Cout (RES_RELU, GRU_BLEND,
+ * GRU_BWD, the LSTM's e0 under `active`), lde1 < Cout (GRU_BLEND, LSTM) or < Cout / 2 (GRU_BWD, SIGMOID_HR), ldo1 < Cout (GRU_BLEND, LSTM, GRU_BWD)
+ * or < Cout / 2 (SIGMOID_HR), ldo2 < 4 * Cout (LSTM); negative output offsets, and an (a, b) grid that leaves the full output:
+ * (Ho - 1) * osy + ooy >= HoF or (Wo - 1) * osx + oox >= WoF (under out_s2d: HoF < 2 * Ho or WoF < 2 * Wo).  The descriptors of a ramnet_conv_launch_multi must also agree in HoF, WoF, ldo, Hin, Win,
+ * C0, C1, ld0, ld1 and ldm (the kernel takes them from descs[0]).  Hin / Win need not agree with Ho / Wo, stride and taps: every tap is tested
+ * against the image and reads zero outside it.
+ * ramnet_wgrad_launch refuses, for every algorithm, ld0 < C0, ld1 < C1 (CAT*), ldm < C1 (CAT_MUL) or < C0 (RELUMASK), ldg < Cout and ldgm < Cout. */
 int ramnet_conv_launch(const ramnet_conv_desc *d, void *stream);    /* forward and backward-data   */
 /* n <= 4 descriptors that differ only in tap list and output sub-grid (ntaps, dy, dx, wtap, Ho, Wo, ooy, oox): the four
  * output-parity classes of a stride-2 backward-data / transposed convolution, executed as ONE launch.            */

@@ -248,6 +248,29 @@ static int check_desc(const ramnet_conv_desc &d) {
                                    (d.algo == RAMNET_ALGO_DIRECT || d.algo == RAMNET_ALGO_WINOGRAD || d.algo == RAMNET_ALGO_WINOGRAD_2X4 ||
                                     d.algo == RAMNET_ALGO_WINOGRAD_2X4_SPLIT));
     if (d.frame > 0) RAMNET_CHECK_ARG(d.e0 && d.e1 && (d.epi == RAMNET_EPI_RELU || d.epi == RAMNET_EPI_LINEAR));
+    // The 3x3 / direct families (ramnet_hip.h, "what ramnet_conv_launch refuses"): every leading dimension covers the channels read or
+    // written through it, and the (a, b) grid lies inside the full output — the kernels index with them as they are.
+    if (d.algo == RAMNET_ALGO_DIRECT || d.algo == RAMNET_ALGO_WINOGRAD || d.algo == RAMNET_ALGO_WINOGRAD_2X4 || d.algo == RAMNET_ALGO_WINOGRAD_2X4_SPLIT) {
+        RAMNET_CHECK_ARG(d.ld0 >= d.C0);
+        if (cat) RAMNET_CHECK_ARG(d.ld1 >= d.C1);
+        if (d.in_mode == RAMNET_IN_CAT_MUL) RAMNET_CHECK_ARG(d.ldm >= d.C1);
+        if (d.in_mode == RAMNET_IN_RELUMASK) RAMNET_CHECK_ARG(d.ldm >= d.C0);
+        RAMNET_CHECK_ARG(d.out_s2d >= 0 && d.ldo >= (d.out_s2d > 0 ? d.out_s2d : d.Cout));
+        if (d.out_s2d == 0) {
+            RAMNET_CHECK_ARG(d.ooy >= 0 && d.oox >= 0 && d.HoF > 0 && d.WoF > 0);
+            RAMNET_CHECK_ARG((long)(d.Ho - 1) * d.osy + d.ooy < d.HoF && (long)(d.Wo - 1) * d.osx + d.oox < d.WoF);
+        } else {                     // the space-to-depth store addresses pixel (2a + parity, 2b + parity) of the full output
+            RAMNET_CHECK_ARG(d.HoF >= 2 * d.Ho && d.WoF >= 2 * d.Wo);
+        }
+        if (d.frame == 0) {
+            if (d.epi == RAMNET_EPI_RES_RELU) RAMNET_CHECK_ARG(d.lde0 >= d.Cout);
+            if (d.epi == RAMNET_EPI_GRU_BLEND) RAMNET_CHECK_ARG(d.lde0 >= d.Cout && (!d.e1 || d.lde1 >= d.Cout) && (!d.o1 || d.ldo1 >= d.Cout));
+            if (d.epi == RAMNET_EPI_LSTM) RAMNET_CHECK_ARG(d.ldo1 >= d.Cout && (!d.e1 || d.lde1 >= d.Cout) && (!d.o2 || d.ldo2 >= 4 * d.Cout) &&
+                                                           (!d.active || d.lde0 >= d.Cout));
+            if (d.epi == RAMNET_EPI_GRU_BWD) RAMNET_CHECK_ARG(d.lde0 >= d.Cout && d.ldo1 >= d.Cout && (!d.e1 || d.lde1 >= d.Cout / 2));
+            if (d.epi == RAMNET_EPI_SIGMOID_HR) RAMNET_CHECK_ARG(d.lde1 >= d.Cout / 2 && d.ldo1 >= d.Cout / 2);
+        }
+    }
     return 0;
 }
 
@@ -260,6 +283,9 @@ static int launch_classes(const ramnet_conv_desc *ds, int n, hipStream_t st) {
         RAMNET_CHECK_ARG(ds[i].x0 == d.x0 && ds[i].w == d.w && ds[i].out == d.out && ds[i].stride == d.stride &&
                          ds[i].Cout == d.Cout && ds[i].epi == d.epi && ds[i].osy == d.osy && ds[i].osx == d.osx &&
                          ds[i].B == d.B && ds[i].in_mode == d.in_mode && ds[i].active == d.active);
+        // (the kernel takes everything but the tap list and the sub-grid from descs[0]: what bounds the sub-grids must be the same)
+        RAMNET_CHECK_ARG(ds[i].HoF == d.HoF && ds[i].WoF == d.WoF && ds[i].ldo == d.ldo && ds[i].Hin == d.Hin && ds[i].Win == d.Win &&
+                         ds[i].C0 == d.C0 && ds[i].C1 == d.C1 && ds[i].ld0 == d.ld0 && ds[i].ld1 == d.ld1 && ds[i].ldm == d.ldm);
     }
     const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
     ConvCommon qc;

@@ -460,9 +460,10 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad_wino_r6_kernel(const ramnet
 // [Cout][Cin][3][3] (+=): dg = G_r^T dU G_c
 __global__ void unpack_wgrad_wino2x4_kernel(const float *__restrict__ ws, float *__restrict__ g, int Cout, int Cin, int CinWs, int CoutWs,
                                             int n_off, size_t total) {
-    const float G2[4][3] = {{1.f, 0.f, 0.f}, {0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f}, {0.f, 0.f, 1.f}};
-    const double G4[6][3] = {{1.0 / 4, 0, 0}, {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                             {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
+    // G2 and G4 as integers over 2 and 24 (as in the packs of conv_wino6.hip): the fold of an integer-valued dU is exact in double and one
+    // division rounds it; with 1.0 / 6 and 1.0 / 24 as factors a gradient that cancels came out as a residue instead of 0
+    const int G2n[4][3] = {{2, 0, 0}, {1, 1, 1}, {1, -1, 1}, {0, 0, 2}};
+    const int G4n[6][3] = {{6, 0, 0}, {-4, -4, -4}, {-4, 4, -4}, {1, 2, 4}, {1, -2, 4}, {0, 0, 24}};
     const int nCiB = (CinWs + 31) / 32, nCoB = (CoutWs + 31) / 32;
     const size_t pos_stride = (size_t)nCiB * nCoB * 1024;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -476,8 +477,8 @@ __global__ void unpack_wgrad_wino2x4_kernel(const float *__restrict__ ws, float 
             for (int kb = 0; kb < 3; ++kb) {
                 double sum = 0;
                 for (int a = 0; a < 4; ++a)
-                    for (int b = 0; b < 6; ++b) sum += G2[a][ka] * u[a][b] * G4[b][kb];
-                g[((size_t)n * Cin + c) * 9 + ka * 3 + kb] += (float)sum;
+                    for (int b = 0; b < 6; ++b) sum += (double)(G2n[a][ka] * G4n[b][kb]) * u[a][b];
+                g[((size_t)n * Cin + c) * 9 + ka * 3 + kb] += (float)(sum / 48.0);
             }
     }
 }

@@ -511,13 +511,15 @@ __global__ void pack_weight_wino_r6_kernel(const float *__restrict__ w, float *_
                 for (int bb = 0; bb < 3; ++bb)
                     g[a][bb] = transposed ? (double)w[((size_t)r * Cin + no) * 9 + (2 - a) * 3 + (2 - bb)]
                                           : (double)w[((size_t)no * Cin + r) * 9 + a * 3 + bb];
-            const double G2[4][3] = {{1, 0, 0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0, 0, 1}};
-            const double G4[6][3] = {{1.0 / 4, 0, 0},           {-1.0 / 6, -1.0 / 6, -1.0 / 6}, {-1.0 / 6, 1.0 / 6, -1.0 / 6},
-                                     {1.0 / 24, 1.0 / 12, 1.0 / 6}, {1.0 / 24, -1.0 / 12, 1.0 / 6}, {0, 0, 1}};
+            // G2 and G4 as integers over 2 and 24: every product of a weight with an integer up to 48 is exact in double and so, for weights
+            // of comparable size, is their sum; ONE division rounds it.  (With 1.0 / 6 and 1.0 / 24 as factors a sum that cancels left 2^-50
+            // instead of 0, which the bf16 matrix pipe's accumulation turned into an error of one unit of a partial sum.)
+            const int G2n[4][3] = {{2, 0, 0}, {1, 1, 1}, {1, -1, 1}, {0, 0, 2}};
+            const int G4n[6][3] = {{6, 0, 0}, {-4, -4, -4}, {-4, 4, -4}, {1, 2, 4}, {1, -2, 4}, {0, 0, 24}};
             double s = 0;
             for (int a = 0; a < 3; ++a)
-                for (int bb = 0; bb < 3; ++bb) s += G2[wv][a] * g[a][bb] * G4[pl][bb];
-            v = (float)s;
+                for (int bb = 0; bb < 3; ++bb) s += (double)(G2n[wv][a] * G4n[pl][bb]) * g[a][bb];
+            v = (float)(s / 48.0);
         }
         wp[i] = v;
     }

@@ -1,4 +1,4 @@
-"""The guarded call of the direct kernel tests (tests/test_hip_pointwise.py, tests/test_hip_reductions.py): device buffers between
+"""The guarded call of the direct kernel tests (tests/test_hip_pointwise.py, tests/test_hip_reductions.py, tests/test_hip_conv_launch.py): device buffers between
 sentinel / NaN guards, the one way to an entry point of the C ABI, and the comparison rules of profiles/pointwise_tests_notes.md §1.
 
 `dtype`: float32 (default), float64 (`stats`, `part`, `mean`, `rstd`) or int64 (`num_batches_tracked`), guards and gaps in that dtype.
@@ -38,22 +38,23 @@ def _sentinel(dtype):
 class In:
     """device input [rows][cols] at pitch ld: NaN in the gaps between rows and in the guards"""
 
-    def __init__(self, data, ld=None, fill=float("nan"), dtype=torch.float32, skew=0):
+    def __init__(self, data, ld=None, fill=float("nan"), dtype=torch.float32, skew=0, col0=0):
+        """col0: the data are the column window [col0, col0 + cols) of the rows, and the pointer is the window's"""
         data = data.reshape(1, -1) if data.dim() == 1 else data.reshape(-1, data.shape[-1])
         rows, cols = data.shape
         ld = cols if ld is None else ld
         off = GUARD + skew
         host = torch.full((2 * GUARD + skew + rows * ld,), fill, dtype=dtype)
-        host[off:off + rows * ld].view(rows, ld)[:, :cols] = data.to(dtype)
+        host[off:off + rows * ld].view(rows, ld)[:, col0:col0 + cols] = data.to(dtype)
         self.dev = host.to(_dev())
-        self.ptr = self.dev.data_ptr() + host.element_size() * off
+        self.ptr = self.dev.data_ptr() + host.element_size() * (off + col0)
 
 
 class Out:
     """device output: columns [col0, col0 + cols) of [rows] rows at pitch ld; everything else (guards, gaps) is sentinel and must stay so.
     prefill: what the valid region holds before the launch (`+=` outputs, in-place operands); else sentinel."""
 
-    def __init__(self, rows, cols, ld=None, col0=0, prefill=None, dtype=torch.float32, skew=0):
+    def __init__(self, rows, cols, ld=None, col0=0, prefill=None, dtype=torch.float32, skew=0, at_window=False):
         self.rows, self.cols, self.ld, self.col0 = rows, cols, cols if ld is None else ld, col0
         self.off = GUARD + skew
         host = torch.full((2 * GUARD + skew + rows * self.ld,), _sentinel(dtype), dtype=dtype)
@@ -61,8 +62,14 @@ class Out:
             host[self.off:self.off + rows * self.ld].view(rows, self.ld)[:, col0:col0 + cols] = prefill.reshape(rows, cols).to(dtype)
         self.before = host
         self.dev = host.to(_dev())
-        self.ptr = self.dev.data_ptr() + host.element_size() * self.off
-        self._host = None
+        self.ptr = self.dev.data_ptr() + host.element_size() * (self.off + (col0 if at_window else 0))     # (at_window: the window's own pointer)
+        self._host, self.frozen = None, False
+
+    def freeze(self):
+        """what the buffer holds now (packed weights, a zeroed workspace) is what later launches must leave in place, guards and gaps included"""
+        self.before = self.dev.cpu()
+        self._host, self.frozen = None, True
+        return self
 
     def _fetch(self):
         if self._host is None:
@@ -79,10 +86,10 @@ class Out:
         assert torch.equal(got[:off], ref[:off]), "%s wrote in front of an output" % what
         assert torch.equal(got[off + n:], ref[off + n:]), "%s wrote behind an output" % what
         keep = torch.ones(self.rows, self.ld, dtype=torch.bool)
-        if not untouched:
+        if not untouched and not self.frozen:
             keep[:, self.col0:self.col0 + self.cols] = False
         assert torch.equal(got[off:off + n].view(self.rows, self.ld)[keep], ref[off:off + n].view(self.rows, self.ld)[keep]), \
-            "%s wrote into the gap of a pitched output" % what if not untouched else "%s launched although it refused its arguments" % what
+            "%s wrote into the gap of a pitched output" % what if not untouched and not self.frozen else "%s changed a frozen buffer" % what if not untouched else "%s launched although it refused its arguments" % what
 
 
 def call(name, *args, rc=0, stream=None, defer=False):
@@ -95,6 +102,32 @@ def call(name, *args, rc=0, stream=None, defer=False):
         assert got == rc, (name, got, L.ramnet_last_error())
         return
     settle(name, *args, rc=rc, got=got)
+
+
+def call_desc(name, cls, fields, rc=0, also=()):
+    """A descriptor entry point (ramnet_conv_launch, ramnet_conv_launch_multi, ramnet_wgrad_launch): `fields` = {field of the ctypes struct
+    `cls` of rpg_ramnet_amd/_hip.py: value}, pointer fields as In / Out objects, arrays as lists; a list of such dicts = the descriptor
+    array of a _multi call.  Fills the struct(s), launches on the NULL stream, synchronises and checks the return code and the guards and gaps
+    of every Out among the fields and in `also`, as `call` does.  Returns the struct(s)."""
+    many = isinstance(fields, (list, tuple))
+    arr = (cls * (len(fields) if many else 1))()
+    bufs = list(also)
+    for i, f in enumerate(fields if many else [fields]):
+        for k, v in f.items():
+            if isinstance(v, (In, Out)):
+                if isinstance(v, Out) and not any(v is b for b in bufs):
+                    bufs.append(v)
+                v = v.ptr
+            if isinstance(v, (list, tuple)):
+                a = getattr(arr[i], k)
+                for j, e in enumerate(v):
+                    a[j] = e
+            else:
+                setattr(arr[i], k, v)
+    fn = getattr(_hip.lib(), name)
+    got = fn(arr, len(fields), None) if many else fn(C.byref(arr[0]), None)
+    settle(name, *bufs, rc=rc, got=got)
+    return arr if many else arr[0]
 
 
 def settle(name, *args, rc=0, got=0):

@@ -180,7 +180,8 @@ typedef struct ramnet_wgrad_desc {
                                      * layout of ramnet_wgrad_wino2x4_ws_floats(), of F(2x4,3x3) (24 multiplies per 8 outputs instead of 32), folded by ramnet_unpack_wgrad_wino2x4();
                                      * or RAMNET_ALGO_WINOGRAD24 (folded upsample-conv): x0 = [B][Hin = Ho+4][Win = Wo+4][C0] as for the
                                      * forward launch, dout / gmask = the full-resolution [B][HoG = 2*Ho][WoG = 2*Wo][Cout] tensors,
-                                     * dw = dU [4 classes][25 positions][C0][Cout] (dW4 = G^T dU G per class); C0 % 32 == 0 and Cout % 64 == 0, or C0 % 64 == 0 and Cout % 32 == 0 */
+                                     * dw = dU [4 classes][25 positions][C0][Cout] (dW4 = G^T dU G per class); C0 % 32 == 0 and Cout % 64 == 0, or C0 % 64 == 0 and Cout % 32 == 0;
+                                     * or RAMNET_ALGO_WINOGRAD24_2X3 where ramnet_fold_wgrad_variant() says so: dw = [4][30][C0][Cout] */
     int gsy, gsx, goy, gox;         /* dout / gmask are read at pixel (oy*gsy + goy, ox*gsx + gox) of a [B, HoG, WoG] tensor      */
     int HoG, WoG;                   /* (all 0 = dense [B, Ho, Wo]; DIRECT only): one output parity of the folded upsample-conv  */
     int head_cin;                   /* RAMNET_ALGO_HEAD (dense 5x5 stride-1 taps, Cout <= 32): real input channels (1, 3 or 5); dw keeps
@@ -319,6 +320,16 @@ size_t ramnet_packed_weight_elems_fold_wino2x3(int Cout, int Cin);
 int ramnet_pack_weight_fold_wino2x3(const float *w_oihw, float *wp, int Cout, int Cin, void *stream);
 int ramnet_pack_weight_fold_wino2x3_dgrad(const float *w_oihw, float *wp, int Cout, int Cin, void *stream);
 int ramnet_fold_unpack_wgrad(float *w4, float *dU, float *wr, float *wc, float *grad, int Cout, int Cin, int CinWs, void *stream);
+/* F(2x3,4x4) backward-weights of the folded upsample-conv (ABI 27, two new entry points; csrc/conv_wgrad_wino24.hip).
+ * ramnet_fold_wgrad_variant: 1 when a RAMNET_ALGO_WINOGRAD24 backward-weights launch (d->algo set so, every other field final) runs
+ * faster with ramnet_wgrad_desc.algo = RAMNET_ALGO_WINOGRAD24_2X3 — 2 x 3 gradient tiles, 30 instead of 25 positions per tile (5.0 instead of
+ * 6.25 products per output), the row matrices of RAMNET_ALGO_WINOGRAD24 and the column matrices of F(3,4) on the points 0, 1, -1, 1/2, -1/2, inf
+ * (Gc above) — the caller then sets d->algo and hands d->dw = dU3 [4 classes][30 positions pos = a*6 + b][C0][Cout], zero at pass start
+ * (dW4 = G^T dU3 Gc per class); the same tensors and channel shapes as RAMNET_ALGO_WINOGRAD24 otherwise.  force: every launch the kernel
+ * takes (tests, sweeps), not only those the size rule picks.
+ * ramnet_fold_unpack_wgrad2x3: ramnet_fold_unpack_wgrad with that workspace beside dU (either may be NULL); zeroes what it reads.       */
+int ramnet_fold_wgrad_variant(const ramnet_wgrad_desc *d, int force);
+int ramnet_fold_unpack_wgrad2x3(float *w4, float *dU, float *dU3, float *wr, float *wc, float *grad, int Cout, int Cin, int CinWs, void *stream);
 /* Head layers (RAMNET_ALGO_HEAD): OIHW [Cout<=32][Cin][5][5] -> [25*Cin rounded up to even][32], row = tap*Cin + channel.
  * ramnet_head_supported: does the head kernel serve this channel pair (Cin in {1,3,5,10}, Cout <= 32)?           */
 size_t ramnet_packed_weight_elems_head(int Cin);

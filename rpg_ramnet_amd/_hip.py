@@ -114,6 +114,7 @@ _SIGS = {
     "ramnet_pack_weight_fold_wino2x3_dgrad": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp]),
     "ramnet_pack_border_weights": (C.c_int, [_fp] * 5 + [C.c_int, C.c_int, _fp]),
     "ramnet_fold_unpack_wgrad": (C.c_int, [_fp] * 5 + [C.c_int, C.c_int, C.c_int, _fp]),
+    "ramnet_fold_unpack_wgrad2x3": (C.c_int, [_fp] * 6 + [C.c_int, C.c_int, C.c_int, _fp]),
     "ramnet_unpad2_fold": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ramnet_up2x_border_col2im": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     "ramnet_pad2_sum": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
@@ -127,6 +128,7 @@ _SIGS = {
     "ramnet_conv_launch": (C.c_int, [C.POINTER(ConvDesc), _fp]),
     "ramnet_conv_launch_multi": (C.c_int, [C.POINTER(ConvDesc), C.c_int, _fp]),
     "ramnet_wgrad_launch": (C.c_int, [C.POINTER(WgradDesc), _fp]),
+    "ramnet_fold_wgrad_variant": (C.c_int, [C.POINTER(WgradDesc), C.c_int]),
     "ramnet_pred_sigmoid_fwd": (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp, _fp, C.c_size_t, _fp]),
     "ramnet_pred_sigmoid_bwd": (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, C.c_size_t, _fp]),
     "ramnet_pred_si_scratch_doubles": (C.c_size_t, [C.c_size_t, C.c_int]),

@@ -10,7 +10,8 @@
 // coalesced), transforms them in registers and writes V[25][8][32] / Z[25][8][64] to LDS (double-buffered, one barrier per
 // batch).  Wave (position group of 7/6/6/6, channel half) accumulates 32 x 32 per position (112 VGPRs) over its whole tile range;
 // loads and transforms of the next batches are issued between the MFMAs; tile splits meet by atomics in the [4][25][Cin][Cout]
-// workspace; the bias gradient rides along.
+// workspace; the bias gradient rides along.  conv_wgrad_wino24_kernel_2x3 below is the F(2x3,4x4) form of the same launch
+// (RAMNET_ALGO_WINOGRAD24_2X3, picked by wgrad_wino24_variant).
 #include <stdlib.h>
 #include "common.hpp"
 
@@ -241,8 +242,273 @@ __global__ void __launch_bounds__(512, 1) conv_wgrad_wino24_kernel(const Wgrad24
     }
 }
 
+// ---- F(2x3,4x4): 2 x 3 gradient tiles, 30 positions per 6 outputs (5.0 products per output instead of 6.25) ---------------------------
+//     dU_cls[pos = a*6 + b][ci][co] = sum_tiles V * Z,   V = B^T d Bc over the 5 x 6 window,   Z = A g Ac^T of the 2 x 3 tile,
+// rows as above, columns on the 6-point F(3,4) of csrc/conv_wino24.hip (TW = 3; points 0, 1, -1, 1/2, -1/2, inf):
+//     Bc^T = [1/4 0 -5/4 0 1 0; 0 -1/4 -1/4 1 1 0; 0 1/4 -1/4 -1 1 0; 0 -1/2 -1 1/2 1 0; 0 1/2 -1 -1/2 1 0; 0 1/4 0 -5/4 0 1]
+//     Ac^T = [1 1 1 1 1 0; 0 1 -1 1/2 -1/2 0; 0 1 1 1/4 1/4 1];   dW4 = G^T dU Gc (ramnet_fold_unpack_wgrad2x3).
+// Two buffers of 30 positions x 8 tiles do not fit the 160 KB of a CU: a batch is 6 tiles (3 MFMAs of K = 2 per position; 2 x 30 x 6 x 96 x 4 B
+// = 138 KB).  A batch has 192 input and 384 gradient items (or 384 and 192, WCI), one per lane: three (six) waves load and transform inputs,
+// the other five (two) gradients, one of them two items per lane — no wave loads both operands.  Wave (position group of 8/8/7/7, channel
+// half) accumulates 32 x 32 per position (128 VGPRs).  What differs from the F(2x2) loop above besides the tile (isolated launches at batch 16,
+// profiles/fold23_wgrad_notes.md): the ReLU mask and the bias sum are applied when the transform reads the gradients, not next to their
+// loads, and each operand's loads are issued as soon as its registers are free (-6 %); loaders apart per wave (a further -3 to -15 %).
+//
+// Overhang.  Rows are those of the F(2x2) kernel: window row 4 of a tile whose second gradient row lies outside the grid enters Winograd
+// row 4 only, which multiplies (A g)'s last row, the out-of-grid gradient itself: zero.  Columns: a window that starts at 3 tx + px reaches
+// column 3 tx + px + 5 of the Wo + 4 padded ones.  Window column 5 enters position b = 5 only (Bc^T's last row), whose Z is g's third column
+// alone; it lies past the row's end only where that gradient column is outside the grid (Wo % 3 != 0): it meets zeros.  Window column 4 enters
+// positions 0-4, which also carry g's FIRST column; it lies past the row's end exactly for px = 1 in the last tile column when Wo % 3 == 1
+// (one valid gradient column) — in exact arithmetic G^T (.) Gc annihilates that product (it belongs to filter tap 4 of 0..3), in fp32 only
+// up to rounding, so the loader reads that column as zeros (one select per batch on its lane offset).  Everything else a window reads past
+// a row's end is finite data of the next row (or the zeros past the tensor) times a zero gradient.
+constexpr int G23_T = 6, G23_NP = 30;             // tiles per batch, positions
+
+template <bool GM, bool WCI>
+__global__ void __launch_bounds__(512, 1) conv_wgrad_wino24_kernel_2x3(const Wgrad24Params p) {
+    constexpr int CI = WCI ? 64 : 32, CO = WCI ? 32 : 64;
+    constexpr int NV = G23_NP * G23_T * CI, NZ = G23_NP * G23_T * CO;            // 5760 / 11520 floats (or swapped)
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float *V = smem;                   // [2][30][6][CI]
+    float *Z = smem + 2 * NV;          // [2][30][6][CO]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, kk = lane >> 5;
+    const int pg = wave >> 1, ch = wave & 1;                  // position group, half of the wider channel dimension
+    const int p0 = pg < 2 ? 8 * pg : 2 + 7 * pg;              // positions p0 .. p0 + (pg < 2 ? 8 : 7) - 1
+    const int cls = blockIdx.z / p.ncob, cob = blockIdx.z % p.ncob;
+    const int py = cls >> 1, px = cls & 1;
+    const int c0 = blockIdx.y * CI, n0 = cob * CO;
+    // 192 or 384 input items (three or six waves, one item per lane) and 384 or 192 gradient items per batch: no wave loads both operands
+    // (its waits for the older loads of one would also wait for the younger loads of the other), so one gradient wave carries two items per lane
+    const bool vrole = WCI ? wave < 6 : wave >= 5, zrole = WCI ? wave >= 6 : wave < 5;
+    const bool z2 = wave == (WCI ? 6 : 4);
+    const int vi = WCI ? tid : max(tid - 320, 0), zi = WCI ? (wave == 7 ? 128 + lane : lane) : tid;
+    const int vt = vi / CI, vc = vi % CI;                     // input item: (tile of the batch, input channel)
+    const int zt = zi / CO, zc = zi % CO;                     // gradient item: (tile, output channel)
+
+    f32x16 acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+
+    float vraw[30], zraw[12], zmraw[GM ? 12 : 1];          // (gradient items: the second one of a z2 wave at 6..11)
+    float bsum = 0.f;
+    bool zcnt = false;                                  // do the gradients in zraw enter the bias sum (not a repeat of the clamped tail)?
+    // the walks of the F(2x2) kernel over the grid of 2 x 3 tiles
+    struct Walk { int tx, ty, b, T; };
+    const int dT = G23_T * (int)gridDim.x;
+    const int d_tx = dT % p.tiles_x, d_ty = (dT / p.tiles_x) % p.tiles_y, d_b = (dT / p.tiles_x) / p.tiles_y;
+    auto walk_init = [&](Walk &w, int batch, int tile) {
+        w.T = batch * G23_T + tile;
+        int t = w.T;
+        w.tx = t % p.tiles_x;
+        t /= p.tiles_x;
+        w.ty = t % p.tiles_y, w.b = t / p.tiles_y;
+    };
+    auto walk_step = [&](Walk &w, int adv) {            // adv = 1: the next batch of this workgroup, 0: the same one again (clamped tail)
+        w.T += adv * dT;
+        w.tx += adv * d_tx;
+        const int cx = w.tx >= p.tiles_x ? 1 : 0;
+        w.tx -= cx * p.tiles_x;
+        w.ty += adv * d_ty + cx;
+        const int cy = w.ty >= p.tiles_y ? 1 : 0;
+        w.ty -= cy * p.tiles_y;
+        w.b += adv * d_b + cy;
+    };
+    Walk wv, wz, wz2;
+    int lbv = 0, lbz = 0;                               // batch the walks stand at
+    const auto rx = wino_rsrc(p.x, (unsigned)min((size_t)p.xbytes, (size_t)WOOB));
+    const auto rg = wino_rsrc(p.g, (unsigned)min((size_t)p.gbytes, (size_t)WOOB));
+    const auto rgm = GM ? wino_rsrc(p.gm, (unsigned)min((size_t)p.gmbytes, (size_t)WOOB)) : rg;
+    const bool vch_ok = c0 + vc < p.Cin, zch_ok = n0 + zc < p.Cout;
+    const unsigned zch = (unsigned)(n0 + zc);
+    const int rowB = p.Wp * p.ldx * 4, colB = p.ldx * 4;                              // bytes per window row / column
+    auto load_v = [&](int batch) {
+        walk_step(wv, batch != lbv ? 1 : 0);
+        lbv = batch;
+        const int wx = 3 * wv.tx + px;
+        const unsigned base = (unsigned)(((wv.b * p.Hp + 2 * wv.ty + py) * p.Wp + wx) * p.ldx + c0 + vc) * 4u;
+        const bool ok = (wv.T < p.ntiles) & vch_ok;
+        const unsigned lane_off = ok ? base : WOOB;
+        const unsigned lane_off4 = (ok & (wx + 4 < p.Wp)) ? base : WOOB;          // window column 4 past the row's end: zeros (header)
+#pragma unroll
+        for (int r = 0; r < 5; ++r)
+#pragma unroll
+            for (int c = 0; c < 6; ++c)
+                vraw[r * 6 + c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, (int)((c == 4 ? lane_off4 : lane_off) + (unsigned)(r * rowB)), c * colB, 0));
+    };
+    auto load_z1 = [&](Walk &wz, int o, int adv) {
+        walk_step(wz, adv);
+        const bool tok = (wz.T < p.ntiles) & zch_ok;
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int oy = 2 * wz.ty + a, ox = 3 * wz.tx + c;
+                const bool ok = tok & (oy < p.Hc) & (ox < p.Wc);
+                const unsigned pix = (unsigned)((wz.b * p.H2 + 2 * oy + py) * p.W2 + 2 * ox + px);
+                // (the top bit instead of a select between the offset and WOOB: the compiler turns that select into two loads of one register
+                //  under complementary masks, the second behind a wait for the first — six memory latencies in a row)
+                const unsigned oob = ok ? 0u : 0x80000000u;
+                zraw[o + a * 3 + c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rg, (int)(((pix * p.ldg + zch) * 4u) | oob), 0, 0));
+                if (GM) zmraw[o + a * 3 + c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rgm, (int)(((pix * p.ldgm + zch) * 4u) | oob), 0, 0));
+            }
+    };
+    auto load_z = [&](int batch, bool count) {
+        const int adv = batch != lbz ? 1 : 0;
+        lbz = batch;
+        load_z1(wz, 0, adv);
+        if (z2) load_z1(wz2, 6, adv);
+        zcnt = count;
+    };
+    // The ReLU mask and the bias sum wait until the transform reads the values: a use next to the loads would hold the wave (and its MFMAs)
+    // for the whole memory latency once per batch.
+    auto z_mask = [&]() {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            if (i < 6 || z2) {
+                if (GM) zraw[i] = zmraw[i] > 0.f ? zraw[i] : 0.f;
+                bsum += zcnt ? zraw[i] : 0.f;
+            }
+        }
+    };
+    // rows: B^T of F(2,4) down the 5 window rows, for each of the 6 window columns
+    auto v_cols = [&]() {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+            const float d0 = vraw[c], d1 = vraw[6 + c], d2 = vraw[12 + c], d3 = vraw[18 + c], d4 = vraw[24 + c];
+            vraw[c] = 2.f * (d0 - d2) - d1 + d3;
+            vraw[6 + c] = d3 - d2 - 2.f * d1;
+            vraw[12 + c] = 2.f * d1 - 3.f * d2 + d3;
+            vraw[18 + c] = d3 - d1;
+            vraw[24 + c] = 2.f * (d1 - d3) - d2 + d4;
+        }
+    };
+    // columns: Bc^T of F(3,4) along the 6 window columns of Winograd row i
+    auto v_row = [&](float *vbuf, int i) {
+        const float d0 = vraw[i * 6], d1 = vraw[i * 6 + 1], d2 = vraw[i * 6 + 2], d3 = vraw[i * 6 + 3], d4 = vraw[i * 6 + 4], d5 = vraw[i * 6 + 5];
+        float *dst = vbuf + ((i * 6) * G23_T + vt) * CI + vc;
+        const float e = d4 - 0.25f * d2, o = d3 - 0.25f * d1;            // even / odd parts of the +-1 pair
+        const float f = d4 - d2, h = 0.5f * (d3 - d1);                   // ... and of the +-1/2 pair
+        dst[0 * G23_T * CI] = 0.25f * d0 - 1.25f * d2 + d4;
+        dst[1 * G23_T * CI] = e + o;
+        dst[2 * G23_T * CI] = e - o;
+        dst[3 * G23_T * CI] = f + h;
+        dst[4 * G23_T * CI] = f - h;
+        dst[5 * G23_T * CI] = 0.25f * d1 - 1.25f * d3 + d5;
+    };
+    // Z = A g Ac^T: row i of (A g) = (g0*, g0*+g1*, g0*-g1*, g0*+2 g1*, g1*), then its three entries through Ac^T
+    auto z_row1 = [&](float *zbuf, int i, const float *zraw, int zt) {
+        float w0, w1, w2;
+        if (i == 0) w0 = zraw[0], w1 = zraw[1], w2 = zraw[2];
+        if (i == 1) w0 = zraw[0] + zraw[3], w1 = zraw[1] + zraw[4], w2 = zraw[2] + zraw[5];
+        if (i == 2) w0 = zraw[0] - zraw[3], w1 = zraw[1] - zraw[4], w2 = zraw[2] - zraw[5];
+        if (i == 3) w0 = zraw[0] + 2.f * zraw[3], w1 = zraw[1] + 2.f * zraw[4], w2 = zraw[2] + 2.f * zraw[5];
+        if (i == 4) w0 = zraw[3], w1 = zraw[4], w2 = zraw[5];
+        float *dst = zbuf + ((i * 6) * G23_T + zt) * CO + zc;
+        const float s = w0 + w2, q = w0 + 0.25f * w2;
+        dst[0 * G23_T * CO] = w0;
+        dst[1 * G23_T * CO] = s + w1;
+        dst[2 * G23_T * CO] = s - w1;
+        dst[3 * G23_T * CO] = q + 0.5f * w1;
+        dst[4 * G23_T * CO] = q - 0.5f * w1;
+        dst[5 * G23_T * CO] = w2;
+    };
+    auto z_row = [&](float *zbuf, int i) {
+        z_row1(zbuf, i, zraw, zt);
+        if (z2) z_row1(zbuf, i, zraw + 6, zt + 64 / CO);
+    };
+
+    const int step = gridDim.x;
+    int batch = blockIdx.x;
+    if (batch < p.nbatch) {
+        const int last = batch + ((p.nbatch - 1 - batch) / step) * step;
+        // prologue: batch -> buffer 0; raw data of the next batch in registers
+        walk_init(wv, batch, vt), walk_init(wz, batch, zt), walk_init(wz2, batch, zt + 64 / CO);
+        lbv = lbz = batch;
+        if (zrole) load_z(batch, true);
+        if (vrole) load_v(batch);
+        if (zrole) {
+            z_mask();
+#pragma unroll
+            for (int i = 0; i < 5; ++i) z_row(Z, i);
+        }
+        if (vrole) {
+            v_cols();
+#pragma unroll
+            for (int i = 0; i < 5; ++i) v_row(V, i);
+        }
+        {
+            const bool more = batch + step <= last;
+            if (zrole) load_z(min(batch + step, last), more);
+            if (vrole) load_v(min(batch + step, last));
+        }
+        __syncthreads();
+        const int aoff = (kk * 3) * CI + (WCI ? ch * 32 : 0) + l31, boff = (kk * 3) * CO + (WCI ? 0 : ch * 32) + l31;
+        int buf = 0;
+        for (; batch <= last; batch += step, buf ^= 1) {
+            const float *vb = V + buf * NV, *zb = Z + buf * NZ;
+            float *vn = V + (buf ^ 1) * NV, *zn = Z + (buf ^ 1) * NZ;
+            const int b2 = min(batch + 2 * step, last);
+            const bool more2 = batch + 2 * step <= last;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                if (q < 7 || pg < 2) {
+                    const int pos = p0 + q;
+                    const float *ap = vb + pos * (G23_T * CI) + aoff, *bp = zb + pos * (G23_T * CO) + boff;
+                    const float a0 = ap[0], a1 = ap[CI], a2 = ap[2 * CI];
+                    const float b0 = bp[0], b1 = bp[CO], b2v = bp[2 * CO];
+                    __builtin_amdgcn_sched_barrier(0);
+                    acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[q], 0, 0, 0);
+                    acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[q], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    // raw data of the next batch (in registers) -> the other LDS buffer; the loads of the batch after it are issued as soon as
+                    // their registers are free and stay in flight for 5-6 positions
+                    if (q == 0 && zrole) z_mask(), z_row(zn, 0), z_row(zn, 1), z_row(zn, 2);
+                    if (q == 1 && zrole) z_row(zn, 3), z_row(zn, 4), load_z(b2, more2);
+                    if (q == 2 && vrole) v_cols();
+                    if (q == 3 && vrole) v_row(vn, 0), v_row(vn, 1), v_row(vn, 2);
+                    if (q == 4 && vrole) v_row(vn, 3), v_row(vn, 4), load_v(b2);
+                    __builtin_amdgcn_sched_barrier(0);
+                    acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, b2v, acc[q], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    // D[row = input channel][col = output channel] of position p0 + q -> dw[((cls*30 + pos)*Cin + c)*Cout + n]
+    const int n = n0 + (WCI ? 0 : ch * 32) + l31;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        if (q < 7 || pg < 2) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int c = c0 + (WCI ? ch * 32 : 0) + (r & 3) + 8 * (r >> 2) + 4 * kk;
+                if (c < p.Cin && n < p.Cout) atomicAdd(p.dw + (((size_t)cls * G23_NP + p0 + q) * p.Cin + c) * p.Cout + n, acc[q][r]);
+            }
+        }
+    }
+    if (p.dbias != nullptr && blockIdx.y == 0) {
+        __syncthreads();
+        float *red = smem;                        // [6][CO]
+        if (zrole) red[zt * CO + zc] = bsum;              // (a z2 wave summed both of its items, of the same channel)
+        if (z2) red[(zt + 64 / CO) * CO + zc] = 0.f;
+        __syncthreads();
+        if (tid < CO) {
+            float t = 0.f;
+            for (int g = 0; g < G23_T; ++g) t += red[g * CO + tid];
+            if (n0 + tid < p.Cout) atomicAdd(p.dbias + n0 + tid, t);
+        }
+    }
+}
+
 int launch_wgrad_wino24(const ramnet_wgrad_desc &d, hipStream_t st) {
     // x0 = replicate-padded low-res input [B][Hin = H+4][Win = W+4][C0]; dout / gmask = [B][HoG = 2H][WoG = 2W][Cout]; Ho, Wo = H, W
+    const bool f23 = d.algo == RAMNET_ALGO_WINOGRAD24_2X3;       // 2 x 3 tiles in batches of 6, dw = [4][30][C0][Cout]
     const bool wci = d.Cout % 64 != 0;           // 32-output-channel layers: 64 x 32 channels per workgroup
     const int G24_CI = wci ? 64 : 32, G24_CO = wci ? 32 : 64;
     RAMNET_CHECK_ARG(d.in_mode == RAMNET_IN_PLAIN && d.stride == 1 && d.C0 % G24_CI == 0 && d.Cout % 32 == 0);
@@ -255,25 +521,46 @@ int launch_wgrad_wino24(const ramnet_wgrad_desc &d, hipStream_t st) {
     q.gmbytes = d.gmask ? (size_t)d.B * d.HoG * d.WoG * d.ldgm * 4 : 0;
     // per-lane 32-bit byte offsets; a tile past the last one may stand up to one grid stride of images beyond the tensor
     RAMNET_CHECK_ARG(2 * q.xbytes < WOOB && 2 * q.gbytes < WOOB && 2 * q.gmbytes < WOOB);
-    q.tiles_x = cdiv(d.Wo, 2), q.tiles_y = cdiv(d.Ho, 2), q.ntiles = q.tiles_x * q.tiles_y * d.B, q.nbatch = cdiv(q.ntiles, G24_T);
+    const int tiles_per_batch = f23 ? G23_T : G24_T;
+    q.tiles_x = cdiv(d.Wo, f23 ? 3 : 2), q.tiles_y = cdiv(d.Ho, 2), q.ntiles = q.tiles_x * q.tiles_y * d.B, q.nbatch = cdiv(q.ntiles, tiles_per_batch);
     q.ncob = cdiv(d.Cout, G24_CO);
     const int gy = d.C0 / G24_CI, gz = q.ncob * 4;
     int splits = 256 / (gy * gz);                   // (128 / 384 workgroups measured the same training step)
     if (splits > q.nbatch) splits = q.nbatch;
     if (splits < 1) splits = 1;
-    const size_t lds = (size_t)2 * 25 * G24_T * (32 + 64) * sizeof(float);
+    const size_t lds = (size_t)2 * (f23 ? G23_NP : 25) * tiles_per_batch * (32 + 64) * sizeof(float);
     const dim3 grid(splits, gy, gz);
     auto go = [&](auto kern) -> int {
         RAMNET_FULL_LDS((kern));
-        note_kernel("conv_wgrad_wino24_kernel<%d,%d>", d.gmask ? 1 : 0, (int)wci);
+        note_kernel(f23 ? "conv_wgrad_wino24_kernel_2x3<%d,%d>" : "conv_wgrad_wino24_kernel<%d,%d>", d.gmask ? 1 : 0, (int)wci);
         hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, q);
         return 0;
     };
-    const int rc = wci ? (d.gmask ? go(conv_wgrad_wino24_kernel<true, true>) : go(conv_wgrad_wino24_kernel<false, true>))
+    const int rc = f23 ? (wci ? (d.gmask ? go(conv_wgrad_wino24_kernel_2x3<true, true>) : go(conv_wgrad_wino24_kernel_2x3<false, true>))
+                              : (d.gmask ? go(conv_wgrad_wino24_kernel_2x3<true, false>) : go(conv_wgrad_wino24_kernel_2x3<false, false>)))
+                 : wci ? (d.gmask ? go(conv_wgrad_wino24_kernel<true, true>) : go(conv_wgrad_wino24_kernel<false, true>))
                        : (d.gmask ? go(conv_wgrad_wino24_kernel<true, false>) : go(conv_wgrad_wino24_kernel<false, false>));
     if (rc) return rc;
     RAMNET_LAUNCH_CHECK();
     return 0;
 }
 
+// Does this RAMNET_ALGO_WINOGRAD24 backward-weights launch run F(2x3,4x4) (RAMNET_ALGO_WINOGRAD24_2X3)?  force: every launch the kernel takes.
+// Otherwise the launches whose workgroups walk at least 24 batches of 6 tiles each: the fixed part of a launch (accumulator set-up, prologue,
+// 30 instead of 25 positions of atomic joins) is larger on F(2x3) and the part per batch smaller.  In the isolated sweep of the three decoder
+// layers over batch 1-32 (tools/bench_fold23_wgrad.py, profiles/fold23_wgrad_sweep.jsonl: about 10 batches per workgroup and image on all
+// three) F(2x3) is 2-5 % slower at batch 1, 1-3 % faster at batch 2 (left on F(2x2): a tie), 6-7 % faster at batch 3 and 18-33 % at batch 16.
+int wgrad_wino24_variant(const ramnet_wgrad_desc &d, int force) {
+    if (d.algo != RAMNET_ALGO_WINOGRAD24 || d.in_mode != RAMNET_IN_PLAIN || d.stride != 1 || d.Ho < 2 || d.Wo < 2 || d.B < 1) return 0;
+    const bool wci = d.Cout % 64 != 0;
+    const int ci = wci ? 64 : 32, co = wci ? 32 : 64;
+    if (d.C0 % ci != 0 || d.Cout % 32 != 0) return 0;
+    if (force) return 1;
+    const long nbatch = ((long)cdiv(d.Wo, 3) * cdiv(d.Ho, 2) * d.B + G23_T - 1) / G23_T;
+    const int per_split = 256 / ((d.C0 / ci) * cdiv(d.Cout, co) * 4);                       // (launch_wgrad_wino24)
+    return nbatch >= 24L * (per_split < 1 ? 1 : per_split) ? 1 : 0;
+}
+
 }  // namespace ramnet
+
+extern "C" int ramnet_fold_wgrad_variant(const ramnet_wgrad_desc *d, int force) { return d ? ramnet::wgrad_wino24_variant(*d, force) : 0; }

@@ -733,10 +733,11 @@ __global__ void pack_border_weights_kernel(const float *__restrict__ w, float *_
 }
 
 // End of a backward pass of a folded decoder: dW5[o][i][k][l] += sum_{p,q,t,s} FA[p][t][k] FA[q][s][l] dW4[p][q][t][s][i][o]
-//   - (border-GEMM gradients routed back to the taps they summed),   dW4 = w4 (direct parity launches) + G^T dU G (Winograd-domain launches).
+//   - (border-GEMM gradients routed back to the taps they summed),   dW4 = w4 (direct parity launches) + G^T dU G (Winograd-domain launches)
+//   + G^T dU3 Gc (F(2x3,4x4) launches, csrc/conv_wgrad_wino24.hip: [4][30][CinWs][Cout], Gc = fold_wino_gc(3, ., .)).
 // One thread per (o, i); the workspaces it reads are zeroed for the next pass.
-__global__ void fold_unpack_wgrad_kernel(float *__restrict__ w4, float *__restrict__ dU, float *__restrict__ wr, float *__restrict__ wc,
-                                         float *__restrict__ grad, int Cout, int Cin, int CinWs) {
+__global__ void fold_unpack_wgrad_kernel(float *__restrict__ w4, float *__restrict__ dU, float *__restrict__ dU3, float *__restrict__ wr,
+                                         float *__restrict__ wc, float *__restrict__ grad, int Cout, int Cin, int CinWs) {
     const float FA[2][4][5] = {{{.25f, 0, 0, 0, 0}, {.75f, .75f, .25f, 0, 0}, {0, .25f, .75f, .75f, .25f}, {0, 0, 0, .25f, .75f}},
                                {{.75f, .25f, 0, 0, 0}, {.25f, .75f, .75f, .25f, 0}, {0, 0, .25f, .75f, .75f}, {0, 0, 0, 0, .25f}}};
     const float G[5][4] = {{0.5f, 0, 0, 0}, {-0.5f, -0.5f, -0.5f, -0.5f}, {-1.f / 6, 1.f / 6, -1.f / 6, 1.f / 6}, {1.f / 6, 1.f / 3, 2.f / 3, 4.f / 3}, {0, 0, 0, 1.f}};
@@ -761,6 +762,16 @@ __global__ void fold_unpack_wgrad_kernel(float *__restrict__ w4, float *__restri
                     const int a = ab / 5, b = ab % 5;
                     for (int t = 0; t < 4; ++t)
                         for (int s = 0; s < 4; ++s) d4[t * 4 + s] += G[a][t] * G[b][s] * u;
+                }
+            }
+            if (dU3 != nullptr) {
+                for (int ab = 0; ab < 30; ++ab) {
+                    float *cell = dU3 + ((size_t)(pq * 30 + ab) * CinWs + i) * Cout + o;
+                    const float u = *cell;
+                    *cell = 0.f;
+                    const int a = ab / 6, b = ab % 6;
+                    for (int t = 0; t < 4; ++t)
+                        for (int s = 0; s < 4; ++s) d4[t * 4 + s] += G[a][t] * (float)fold_wino_gc(3, b, s) * u;
                 }
             }
             for (int t = 0; t < 4; ++t)
@@ -838,5 +849,12 @@ extern "C" int ramnet_pack_border_weights(const float *w, float *rows, float *co
 extern "C" int ramnet_fold_unpack_wgrad(float *w4, float *dU, float *wr, float *wc, float *grad, int Cout, int Cin, int CinWs, void *stream) {
     RAMNET_CHECK_ARG(w4 && wr && wc && grad && Cout > 0 && Cin > 0 && CinWs >= Cin);
     const size_t total = (size_t)Cout * Cin;
-    return launch_1d<128>(fold_unpack_wgrad_kernel, total, stream, w4, dU, wr, wc, grad, Cout, Cin, CinWs);
+    return launch_1d<128>(fold_unpack_wgrad_kernel, total, stream, w4, dU, (float *)nullptr, wr, wc, grad, Cout, Cin, CinWs);
+}
+
+extern "C" int ramnet_fold_unpack_wgrad2x3(float *w4, float *dU, float *dU3, float *wr, float *wc, float *grad, int Cout, int Cin, int CinWs,
+                                           void *stream) {
+    RAMNET_CHECK_ARG(w4 && wr && wc && grad && Cout > 0 && Cin > 0 && CinWs >= Cin);
+    const size_t total = (size_t)Cout * Cin;
+    return launch_1d<128>(fold_unpack_wgrad_kernel, total, stream, w4, dU, dU3, wr, wc, grad, Cout, Cin, CinWs);
 }

@@ -192,6 +192,34 @@ def set_fold_winograd_2x3(mode):
     _FOLD_2X3 = mode
 
 
+_FOLD_WGRAD_2X3 = "auto"
+_FOLD_WGRAD_VARIANT = {}
+
+
+def set_fold_winograd_wgrad_2x3(mode):
+    """Backward-weights of the folded upsample-conv on 2 x 3 gradient tiles (F(2x3,4x4), csrc/conv_wgrad_wino24.hip): "auto" = where the
+    library's size rule picks it (ramnet_fold_wgrad_variant), "off" = F(2x2,4x4) everywhere, "force" = every launch the kernel takes."""
+    global _FOLD_WGRAD_2X3
+    assert mode in ("auto", "off", "force")
+    _FOLD_WGRAD_2X3 = mode
+
+
+def _fold_wgrad_2x3(B, Hh, W, Cin, Cout):
+    """Does the one-launch backward-weights of a folded decoder at this shape run as F(2x3,4x4)?  (The library decides; cached per shape.)"""
+    if _FOLD_WGRAD_2X3 == "off":
+        return False
+    key = (B, Hh, W, Cin, Cout, _FOLD_WGRAD_2X3, _DESC_EPOCH)
+    hit = _FOLD_WGRAD_VARIANT.get(key)
+    if hit is None:
+        d = H.WgradDesc()
+        d.algo, d.in_mode, d.stride = H.ALGO_WINOGRAD24, H.IN_PLAIN, 1
+        d.B, d.Hin, d.Win, d.Ho, d.Wo, d.HoG, d.WoG = B, Hh + 4, W + 4, Hh, W, 2 * Hh, 2 * W
+        d.C0 = d.ld0 = Cin
+        d.Cout = d.ldg = d.ldgm = Cout
+        hit = _FOLD_WGRAD_VARIANT[key] = bool(H.lib().ramnet_fold_wgrad_variant(C.byref(d), int(_FOLD_WGRAD_2X3 == "force")))
+    return hit
+
+
 def set_fold_upsample(on):
     global _FOLD_UP
     _FOLD_UP = bool(on)
@@ -466,6 +494,15 @@ _LAYOUTS = {
 }
 
 
+# ... and of the folded upsample-conv's one-launch form, per variant of the launch: kind -> (positions per parity class, value of
+# wgrad_launch's wino24 argument: True = RAMNET_ALGO_WINOGRAD24, "2x3" = RAMNET_ALGO_WINOGRAD24_2X3); the workspace is
+# [4 classes][positions][CinWs][Cout], folded by ramnet_fold_unpack_wgrad[2x3].
+_FOLD_LAYOUTS = {
+    "fold24": (25, True),
+    "fold23": (30, "2x3"),
+}
+
+
 def _stamp_layout(dw, kind, slabs, head_cin=0):
     """Write the layout of a pass onto its workspace tensor (the protocol stated at wgrad_launch); ConvParam.grad_ws is the one caller."""
     dw.wino, dw.wino6, dw.wg_dsplit = kind == "wino", kind == "wino6", kind == "dsplit"
@@ -497,8 +534,8 @@ def _wgrad_desc_build(x0, taps, dout, dw, Cout, stride, x1, xm, xm_off, in_mode,
     kind, slabs = _layout_of(dw)
     d.algo = _LAYOUTS[kind][3]
     d.dw_slabs = slabs if (kind != "direct" and _WGRAD_SLABS) else 0     # per-split slabs (read-modify-write joins)
-    if wino24:          # folded upsample-conv in the Winograd F(2x2,4x4) domain: dw = [4][25][C0][Cout]
-        d.algo = H.ALGO_WINOGRAD24
+    if wino24:          # folded upsample-conv in the Winograd F(2x2,4x4) domain: dw = [4][25][C0][Cout]; "2x3": F(2x3,4x4), dw = [4][30][C0][Cout]
+        d.algo = H.ALGO_WINOGRAD24_2X3 if wino24 == "2x3" else H.ALGO_WINOGRAD24
     hc = getattr(dw, "head_cin", 0)
     if hc and _HEAD and taps.head and stride == 1 and in_mode == H.IN_PLAIN and gview is None and dw_off == 0:
         d.algo, d.head_cin = H.ALGO_HEAD, hc
@@ -919,8 +956,8 @@ class ConvParam:
         self._state_half = self._s2d = None
         self._ws = self._bws = self._slabs = None
         self._ws_fold = None             # (dW4 [64][CinWs][Cout], dWrows, dWcols) of the folded upsample-conv backward-weights
-        self._ws_fold24 = None
-        self._fold_used = self._fold24_used = self._ws_used = False
+        self._ws_fold24 = self._ws_fold23 = None
+        self._fold_used = self._fold24_used = self._fold23_used = self._ws_used = False
         self._dirty = False
         self._defer = []                 # queued backward-weights launches of a recurrent cell (_wgrad_cell)
 
@@ -1111,12 +1148,18 @@ class ConvParam:
         self._fold_used = True
         return self._ws_fold + (self._bws,)
 
-    def grad_ws_fold24(self):
-        """dU [4 parity classes][25 positions][Cin][Cout]: Winograd-domain gradient of the four 4x4 parity filters."""
-        if self._ws_fold24 is None:
-            self._ws_fold24 = torch.zeros(4 * 25 * self.CinWs * self.Cout, device=self.weights[0].device)
-        self._fold24_used = True
-        return self._ws_fold24
+    def grad_ws_fold24(self, kind="fold24"):
+        """dU [4 parity classes][25 positions][Cin][Cout]: Winograd-domain gradient of the four 4x4 parity filters — or, kind "fold23", the
+        [4][30][Cin][Cout] of the F(2x3,4x4) launches (_FOLD_LAYOUTS): the workspace of the variant the launch takes."""
+        f23 = kind == "fold23"
+        ws = self._ws_fold23 if f23 else self._ws_fold24
+        if ws is None:
+            ws = torch.zeros(4 * _FOLD_LAYOUTS[kind][0] * self.CinWs * self.Cout, device=self.weights[0].device)
+        if f23:
+            self._ws_fold23, self._fold23_used = ws, True
+        else:
+            self._ws_fold24, self._fold24_used = ws, True
+        return ws
 
     def _finalize_fold(self):
         """dW5 += sum_parities A_py^T dW4 A_px  -  (border GEMM gradients routed back to the taps they summed), dW4 = the direct parity
@@ -1124,23 +1167,28 @@ class ConvParam:
         workspaces for the next pass."""
         w4, wr, wc = self._ws_fold
         dU = self._ws_fold24 if self._fold24_used else None
+        dU3 = self._ws_fold23 if self._fold23_used else None       # F(2x3,4x4) launches of the pass: + G^T dU3 Gc
         if self.weights[0].requires_grad:
             g = ensure_grad(self.weights[0])
-            H.check(H.lib().ramnet_fold_unpack_wgrad(_p(w4), _p(dU), _p(wr), _p(wc), _p(g), self.Cout, self.Cin, self.CinWs, _st()),
-                    "ramnet_fold_unpack_wgrad")
+            if dU3 is not None:
+                H.check(H.lib().ramnet_fold_unpack_wgrad2x3(_p(w4), _p(dU), _p(dU3), _p(wr), _p(wc), _p(g), self.Cout, self.Cin, self.CinWs, _st()),
+                        "ramnet_fold_unpack_wgrad2x3")
+            else:
+                H.check(H.lib().ramnet_fold_unpack_wgrad(_p(w4), _p(dU), _p(wr), _p(wc), _p(g), self.Cout, self.Cin, self.CinWs, _st()),
+                        "ramnet_fold_unpack_wgrad")
         else:       # frozen weight beside a trainable bias (they share the launches): nothing to fold, the workspaces start the next pass at zero
-            for t in (w4, dU, wr, wc):
+            for t in (w4, dU, dU3, wr, wc):
                 if t is not None:
                     _zero_later(t)
-        self._fold24_used = False
+        self._fold24_used = self._fold23_used = False
         self._fold_used = False
 
     def discard(self):
         """Zero every gradient workspace without folding it (aborted backward pass)."""
-        for t in (self._ws, self._bws, self._ws_fold24) + tuple(self._ws_fold or ()):
+        for t in (self._ws, self._bws, self._ws_fold24, self._ws_fold23) + tuple(self._ws_fold or ()):
             if t is not None:
                 t.zero_()
-        self._dirty = self._ws_used = self._fold_used = self._fold24_used = False
+        self._dirty = self._ws_used = self._fold_used = self._fold24_used = self._fold23_used = False
 
     def _join_slabs(self):
         """Winograd backward-weights slabs -> slab 0 (fixed order), weights and bias."""
@@ -1474,9 +1522,10 @@ def _folded_upsample_wgrad(x, skip, dy, y, cp, xpad=None):
             H.check(L.ramnet_up2x_border_im2col(_p(x), _p(skip), _p(a_rows), _p(a_cols), B, Hh, W, Cc, _st()), "ramnet_up2x_border_im2col")
         if _FOLD_WINO_WGRAD and Cc == cp.CinWs and ((Cc % 32 == 0 and cp.Cout % 64 == 0) or
                                                                                  (Cc % 64 == 0 and cp.Cout % 32 == 0)):
-            # one launch, all four parities, in the Winograd F(2x2,4x4) domain (csrc/conv_wgrad_wino24.hip)
-            wgrad_launch(xpad, Taps.get("fold", 4, 0, 0, 0), dy, cp.grad_ws_fold24(), cp.Cout, gmask=y, dbias=bws, Ho=Hh, Wo=W,
-                         gview=(0, 0, 0, 0, H2, W2), wino24=True)
+            # one launch, all four parities, in the Winograd F(2x2,4x4) or F(2x3,4x4) domain (csrc/conv_wgrad_wino24.hip)
+            kind = "fold23" if _fold_wgrad_2x3(B, Hh, W, Cc, cp.Cout) else "fold24"
+            wgrad_launch(xpad, Taps.get("fold", 4, 0, 0, 0), dy, cp.grad_ws_fold24(kind), cp.Cout, gmask=y, dbias=bws, Ho=Hh, Wo=W,
+                         gview=(0, 0, 0, 0, H2, W2), wino24=_FOLD_LAYOUTS[kind][1])
         else:
             for py in range(2):
                 for px in range(2):

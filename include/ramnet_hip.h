@@ -693,6 +693,45 @@ int ramnet_grad_loss_bwd(const float *const *pred, const float *const *target, i
                          const double *stats, double Bg, const double *Bg_dev, double gain, const float *weights, const float *up,
                          const float *up_sum, float *dpred, void *stream);
 
+/* ---- the images and the scale of RAM_Net/test.py for a saved data package (test.py:36-43, 259-378; csrc/render.hip) ------------------
+ * All image outputs are uint8 in FILE order, RGBA and RGB: what cv2.imwrite leaves on disk (make_colormap's BGR is swapped back by it).
+ * Tables of device pointers (maps, inputs, scale_pred, scale_target) are DEVICE tables, as the pointer-table entry above writes them.
+ *
+ * Depth maps: maps[g] = H x W fp32 of normalised log depth (NaN = no ground truth; +-inf is OUT OF CONTRACT: the reference's nan_to_num
+ * replaces it by the largest float, which is not restated).  grey[G][H][W] = rint(v * 255) in fp32, half to even, saturated to
+ * [0, 255], NaN -> 0 (OpenCV's saturate_cast on `img * 255.0`).  color[G][H][W][4] = the row of lut the pixel selects:
+ *   a = amax(map), NaN propagating; inv = nan_to_num(a - v, nan = 1); q = nan_to_num(inv / amax(inv)), all fp32 (make_colormap);
+ *   x = fp32(double(q) - vmin), then x = fp32(double(x) / (vmax - vmin)), or 0 when vmin == vmax (matplotlib's Normalize on a float32
+ *   array under NumPy 2: its limits are Python floats); xa = x * 256 in fp32; row 255 when xa == 256, row 256 (under) when xa < 0,
+ *   row 257 (over) when xa >= 256, row int(xa) otherwise (Colormap.__call__).
+ * lut: DEVICE, 258 x 4 bytes: 256 colours, then under, then over.  vmin <= vmax, both finite.  A map that holds a NaN is the constant
+ * colour of q = 1; a constant map has q = 0 (0 / 0 -> 0).  color must be 4-byte aligned.
+ * The least-squares scale (test.py:365-378): scale[k] = sum(p * t) / sum(p * p) of pair k over its npix pixels, p / t the UNCLAMPED fp32
+ * metric depths of the conversion above, products rounded to fp32, sums in double; NaN propagates (a NaN target makes the scale NaN).
+ * It has its own entry point and also rides in the depth call (n_scale pairs of H x W maps; n_scale = 0: the three scale arguments may be
+ * NULL), where it costs no launch.
+ * Launches: depth two (statistics per map joined by ticket and last arrival in index order, then the map), scale alone one, inputs one;
+ * no host synchronisation, the same input gives the same bytes on every call.  workspace: the size the workspace function returns for
+ * (G, n_scale, npix) (0 for sizes the calls would reject; the scale entry point asks with G = 0), 256-byte aligned; its first
+ * RAMNET_RENDER_TICKET_BYTES must be ZERO WHEN IT IS ALLOCATED, every call leaves them zero again and writes whatever else it reads (one
+ * call at a time per workspace: order them on one stream).  G >= 1, G + n_scale <= 65535, npix < 2^31.
+ *
+ * Inputs: inputs[g] = channels[g] x H x W fp32 planes (NCHW, batch 1); channels / kinds are HOST arrays of G, read during the call.
+ * s = the planes added in channel order in fp32 (np.sum(axis = 0)).  rgb[G][H][W][3]: RAMNET_RENDER_EVENTS: R = 255 where s > 0.9,
+ * G = 0, B = 255 where s <= -0.5 (the thresholds are doubles, test.py:342-345); RAMNET_RENDER_FRAME: all three rint(s * 255) saturated
+ * as grey above.  One launch per 256 inputs.                                                                                          */
+#define RAMNET_RENDER_TICKET_BYTES 262144
+#define RAMNET_RENDER_EVENTS 0
+#define RAMNET_RENDER_FRAME 1
+size_t ramnet_render_depth_workspace(int G, int n_scale, size_t npix);
+int ramnet_render_depth(const float *const *maps, int G, int H, int W, double vmin, double vmax, const unsigned char *lut,
+                        const float *const *scale_pred, const float *const *scale_target, int n_scale, float clip_distance,
+                        float reg_factor, void *workspace, unsigned char *grey, unsigned char *color, double *scale, void *stream);
+int ramnet_least_squares_scale(const float *const *pred, const float *const *target, int G, size_t npix, float clip_distance,
+                               float reg_factor, void *workspace, double *scale, void *stream);
+int ramnet_render_inputs(const float *const *inputs, const int *channels, const int *kinds, int G, int H, int W, unsigned char *rgb,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,11 @@ _SIGS = {
     "ramnet_grad_loss_stats": (C.c_int, [_fp, _fp] + [C.c_int] * 5 + [_fp] * 6),
     "ramnet_grad_loss_from_stats": (C.c_int, [_fp, C.c_int, C.c_int, C.c_double, _fp, _fp, _fp, _fp, _fp]),
     "ramnet_grad_loss_bwd": (C.c_int, [_fp, _fp] + [C.c_int] * 5 + [_fp, C.c_double, _fp, C.c_double, _fp, _fp, _fp, _fp, _fp]),
+    "ramnet_render_depth_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_size_t]),
+    "ramnet_render_depth": (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, _fp, _fp, _fp, C.c_int, C.c_float, C.c_float,
+                                      _fp, _fp, _fp, _fp, _fp]),
+    "ramnet_least_squares_scale": (C.c_int, [_fp, _fp, C.c_int, C.c_size_t, C.c_float, C.c_float, _fp, _fp, _fp]),
+    "ramnet_render_inputs": (C.c_int, [_fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, _fp, _fp]),
 }
 EXPORTS = tuple(_SIGS)
 

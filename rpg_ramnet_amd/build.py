@@ -22,7 +22,9 @@ EXTRA_FLAGS = {"conv_wino6.hip": ["-fno-slp-vectorize"], "conv_wgrad_wino.hip": 
                "conv_wgrad_wino6.hip": ["-fno-slp-vectorize"], "conv_wino6s.hip": ["-fno-slp-vectorize"],
                "conv_wgrad_dsplit.hip": ["-fno-slp-vectorize"],          # (its split arithmetic: 576 instead of 595 instructions per batch)
                # metrics.hip restates numpy's float32 element arithmetic (d * d / (t * t + eps)): a fused multiply-add would round once less
-               "metrics.hip": ["-ffp-contract=off"]}
+               "metrics.hip": ["-ffp-contract=off"],
+               # render.hip restates numpy's and matplotlib's element arithmetic the same way, and shares metrics.hip's depth conversion
+               "render.hip": ["-ffp-contract=off"]}
 
 
 def sources():

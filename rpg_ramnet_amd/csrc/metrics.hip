@@ -25,13 +25,11 @@
 // Element arithmetic is numpy's on float32 arrays: fabsf(t - p), d / (t + 1e-6f), d * d / (t * t + 1e-6f) with IEEE division and no
 // contraction (this file is built with -ffp-contract=off; the divisions are __fdiv_rn), accumulated in double.
 #include "common.hpp"
+#include "metrics_common.hpp"
 
 namespace ramnet {
 
-typedef float bm_f4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef const float __attribute__((address_space(1))) *bm_src_t;
 
-constexpr int BM_T = 256;                  // threads of a workgroup
 constexpr int BM_BINS = 2048;              // bins of pass 1 (11 bits); passes 2 and 3 use the first 1024 of a slab
 constexpr int BM_ROW = 8;                  // doubles of a partial row: n, n_target, sum d/(t+eps), sum d^2/(t^2+eps), sum d^2, sum d, sum (p-t)^2 | t valid, (unused)
 constexpr int BM_STATE = 8;                // uint32 of a pair's state: prefix0, rank0, prefix1, rank1, n
@@ -58,15 +56,6 @@ static bm_plan_t bm_plan(int G, int N, size_t npix) {
     p.total = p.off_slab + (size_t)G * p.P * 2 * BM_BINS * sizeof(unsigned);
     return p;
 }
-
-__device__ __forceinline__ double bm_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
-
-__device__ __forceinline__ unsigned bm_ld(const unsigned *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double bm_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // The part of sample s that workgroup w of Ws reads: [lo, hi) in elements of the sample, lo a multiple of 4.
 __device__ __forceinline__ void bm_range(unsigned npix, int Ws, int w, unsigned &lo, unsigned &hi) {
@@ -153,22 +142,6 @@ __device__ __forceinline__ void bm_select(const unsigned *lds, int nbins, unsign
         }
     }
     __syncthreads();
-}
-
-// Takes the pair's ticket after the workgroup's stores; true in every thread of the last arrival of the pair.
-__device__ __forceinline__ bool bm_ticket(size_t g, int P, unsigned *tickets, int *flag) {
-    // Release ONCE per workgroup (a __threadfence() in each of the 6144 waves of a G = 48 launch writes the L2 back 6144 times): every wave
-    // waits until its own stores have reached the L2 (the barrier alone does not), then thread 0 fences at device scope and takes the ticket.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        *flag = atomicAdd(tickets + g, 1u) == (unsigned)P - 1u;
-    }
-    __syncthreads();
-    const bool last = *flag != 0;
-    if (last) __threadfence();
-    return last;
 }
 
 // Stores the workgroup's histogram(s) to its slab(s), takes the pair's ticket; true in every thread of the last arrival of the pair.
@@ -416,14 +389,6 @@ static et_plan_t et_plan(int G, size_t npix, int ncut, int has_mask, bool rescal
 static bool et_sizes_ok(int G, size_t npix, int ncut, int has_mask) {
     if (G < 1 || G > 65535 || npix == 0 || npix >= ((size_t)1 << 32) || ncut < 0 || ncut > ET_MAXCUT) return false;
     return (size_t)G * (1 + ncut) * (has_mask ? 2 : 1) <= RAMNET_EVAL_TABLE_TICKET_BYTES / sizeof(unsigned);
-}
-
-// Normalised log depth -> metric depth (evaluation.py:76-85), the ONE conversion of ramnet_metric_depth and of the table kernels.
-// lo = expf(-reg) * clip.  The clamp keeps a NaN (both comparisons are false); on numbers it is fminf(fmaxf(d, lo), clip).
-__device__ __forceinline__ float et_metric_depth(float y, float reg, float clip, float lo, bool clamp) {
-    float d = expf(reg * (y - 1.0f)) * clip;
-    if (clamp) d = d < lo ? lo : (d > clip ? clip : d);
-    return d;
 }
 
 // bm_range for a map of up to 2^32 - 1 pixels

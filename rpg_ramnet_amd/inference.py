@@ -8,6 +8,13 @@ dependencies of the network are settled").  Written files (the layout evaluation
 
     <out>/npy/<key>/depth_{idx:010d}.npy                      prediction, normalised log depth, float32 [1, H, W]
     <out>/ground_truth/npy/depth_<key>/frame_{idx:010d}.npy   target, same encoding
+and, with ``images=True``, test.py's pictures of the same packages (test.py:259-360; rendered on the device by ``render``):
+    <out>/depth/<key>/frame_{idx:010d}.png                          prediction * 255, greyscale
+    <out>/color_map/<key>/frame_{idx:010d}.png                      prediction through make_colormap and the run's colour mapper, RGBA
+    <out>/ground_truth/grey/depth_<key>/frame_{idx:010d}.png        the same two of the target
+    <out>/ground_truth/color_map/depth_<key>/frame_{idx:010d}.png
+    <out>/video/predictions|gt|inputs/frame_{video_idx:010d}.png    colour maps again and the input previews (events red / blue, the frame
+                                                                    grey), one per key of test.py's video list, numbered through the run
 """
 import glob
 import os
@@ -17,6 +24,8 @@ import numpy as np
 import torch
 
 from .metrics import EVAL_CUTOFFS, EvalTable, depth_metrics
+
+TEST_METRICS = ("mse", "abs_rel_diff", "scale_invariant_error", "median_error", "mean_error", "rms_linear")      # test.py:27, in its order
 
 
 def empty_states(every_x_rgb_frame):
@@ -34,8 +43,38 @@ def _time_batched_ok(model):
             and torch.device(model.gpu).type == "cuda")
 
 
+def video_keys(model, every_x_rgb_frame):
+    """The keys test.py draws into video/ (test.py:318-326)."""
+    baseline = getattr(model, "baseline", False)
+    if baseline == "rgb" or type(model).__name__ == "ERGB2Depth":
+        return ["image"]
+    keys = ["events{}".format(i) for i in range(every_x_rgb_frame - 1)]
+    if not baseline:
+        keys.append("events{}".format(every_x_rgb_frame - 1))
+    return keys + ["image"]
+
+
+def _write_images(R, output_folder, idx, video_idx, pkeys, tkeys, vkeys, color, grey, rgb):
+    """test.py:262-360 for one package from the planes of render.render_package (host arrays); returns the next video index."""
+    name = 'frame_{:010d}.png'.format(idx)
+    for j, key in enumerate(pkeys + tkeys):
+        gdir, cdir = ("depth", "color_map") if j < len(pkeys) else ("ground_truth/grey", "ground_truth/color_map")
+        for d, plane in ((join(output_folder, gdir, key), grey[j]), (join(output_folder, cdir, key), color[j])):
+            os.makedirs(d, exist_ok=True)
+            R.write_png(join(d, name), plane)
+    for j, key in enumerate(vkeys):
+        name = 'frame_{:010d}.png'.format(video_idx)
+        for sub, plane in (("predictions", color[pkeys.index(key)]), ("gt", color[len(pkeys) + tkeys.index("depth_" + key)]), ("inputs", rgb[j])):
+            d = join(output_folder, "video", sub)
+            os.makedirs(d, exist_ok=True)
+            R.write_png(join(d, name), plane)
+        video_idx += 1
+    return video_idx
+
+
 def stream_dataset(model, dataset, every_x_rgb_frame, output_folder=None, settle=2, calculate_scale=False,
-                   reg_factor=5.70378, clip_distance=1000.0, max_items=None, time_batched="auto", table=None, rescale=False):
+                   reg_factor=5.70378, clip_distance=1000.0, max_items=None, time_batched="auto", table=None, rescale=False,
+                   images=False, color_mapper=None, metrics=False):
     """Run ``model`` over ``dataset`` (items ``(sequence, dataset_idx)``, sequence_length 1) the way test.py does and
     optionally write predictions / targets as .npy.  Returns {'items', 'saved', 'scale': (mean, min, max) or None}.
 
@@ -46,15 +85,42 @@ def stream_dataset(model, dataset, every_x_rgb_frame, output_folder=None, settle
     table: a dict prediction key -> ``metrics.EvalTable``, or True to create one per prediction key from ``clip_distance`` /
     ``reg_factor``: every package past ``settle`` adds each prediction with its ``depth_<key>`` target to that key's table while it is
     still on the device — no ``output_folder`` and no read-back inside the loop; the tables come back under ``info["tables"]``.
-    rescale: the tables that ``table=True`` creates are rescaled ones (evaluation.py's --rescale)."""
+    rescale: the tables that ``table=True`` creates are rescaled ones (evaluation.py's --rescale).
+
+    images (with ``output_folder``): every saved package also gets test.py's pictures (the module docstring lists them): ONE call of
+    ``render.render_package`` and ONE device-to-host copy of its uint8 planes per package.  color_mapper: the ``render.ColorMapper`` of
+    the run; None builds it as test.py does, from the target of package 20 (``ColorMapper.from_target``).  The .npy files do not change.
+    calculate_scale="device": the same (mean, min, max) from ``render.least_squares_scale`` (float64 sums on the device; it rides in the
+    render call of a drawn package), one read-back after the loop; True keeps the float32 host path of test.py:365-378.
+    metrics: ``info["total_metrics"]`` = test.py:394, the mean over every package past ``settle`` and every key of TEST_METRICS (test.py's
+    six, in its order) from ``metrics.batch_metrics``, one read-back after the loop (None when there was no such package).
+    With any of the three the package is moved to the model's device once, and model, renderer and metrics read that copy."""
     tables = {} if table is True else table
-    was_training = model.training
-    model.eval()
     use_tb = _time_batched_ok(model) if time_batched == "auto" else bool(time_batched)
     tb, K = None, every_x_rgb_frame
     n = len(dataset) if max_items is None else min(len(dataset), max_items)
-    scale = np.empty(n) if calculate_scale else None
+    device_scale = isinstance(calculate_scale, str) and calculate_scale == "device"
+    if isinstance(calculate_scale, str) and not device_scale:
+        raise ValueError("stream_dataset: calculate_scale is False, True or \"device\", got %r" % (calculate_scale,))
+    host_scale = bool(calculate_scale) and not device_scale
+    scale = np.empty(n) if host_scale else None
+    draw = bool(images) and bool(output_folder)
+    device = torch.device(model.gpu) if (draw or device_scale or metrics) else None
+    R, vkeys, video_idx, device_scales, metric_rows = None, [], 0, [], []
+    if draw or device_scale:
+        from . import render as R
+    if draw:
+        if color_mapper is None:
+            if len(dataset) <= 20:
+                raise ValueError("stream_dataset: images=True takes its colour mapper from package 20 (test.py:197), the dataset has %d; "
+                                 "pass color_mapper=" % len(dataset))
+            color_mapper = R.ColorMapper.from_target(dataset[20][0][0]['depth_image'])
+        vkeys = video_keys(model, every_x_rgb_frame)
+    if metrics:
+        from .metrics import batch_metrics
     saved = 0
+    was_training = model.training
+    model.eval()
     with torch.no_grad():
         prev_dataset_idx = -1
         for idx in range(n):
@@ -63,6 +129,8 @@ def stream_dataset(model, dataset, every_x_rgb_frame, output_folder=None, settle
                 prev_super, prev_lstm = empty_states(every_x_rgb_frame)
                 sequence_idx = 0
             package = {k: v[None, :] for k, v in item[0].items()}
+            if device is not None:                                  # moved once: the model, the renderer and the metrics read this copy
+                package = {k: v.to(device, non_blocking=True) for k, v in package.items()}
             if use_tb:
                 hw = tuple(package['image'].shape[2:])
                 if tb is None or (tb.H, tb.W) != hw:                # a ConcatDatasetCustom may mix recordings of different resolution:
@@ -90,6 +158,22 @@ def stream_dataset(model, dataset, every_x_rgb_frame, output_folder=None, settle
                         os.makedirs(d, exist_ok=True)
                         np.save(join(d, 'frame_{:010d}.npy'.format(idx)), value[0].cpu().numpy())
                 saved += 1
+            if device is not None:
+                pkeys = list(preds)
+                pairs = ([preds[k] for k in pkeys], [package['depth_' + k] for k in pkeys])
+            if draw and sequence_idx >= settle:
+                tkeys = [k for k in package if 'depth' in k]
+                maps = pairs[0] + [package[k] for k in tkeys]
+                buf, _, _, _, s = R.render_package(maps, color_mapper, [package[k] for k in vkeys], vkeys,
+                                                   scale=pairs + (clip_distance, reg_factor) if device_scale else None)
+                color, grey, rgb = R.split_package(buf.cpu().numpy(), len(maps), len(vkeys), tuple(maps[0].shape[-2:]))
+                video_idx = _write_images(R, output_folder, idx, video_idx, pkeys, tkeys, vkeys, color, grey, rgb)
+            elif device_scale:
+                s = R.least_squares_scale(pairs[0], pairs[1], clip_distance, reg_factor)
+            if device_scale:
+                device_scales.append(s[-1:])                        # (the last key wins, as on the host path)
+            if metrics and sequence_idx >= settle:
+                metric_rows.append(batch_metrics(pairs[0], pairs[1], TEST_METRICS))
             if tables is not None and sequence_idx >= settle:
                 for key, img in preds.items():
                     if key not in tables:
@@ -97,7 +181,7 @@ def stream_dataset(model, dataset, every_x_rgb_frame, output_folder=None, settle
                             continue
                         tables[key] = EvalTable(clip_distance, reg_factor, rescale=rescale)
                     tables[key].add([img[0]], [package['depth_' + key][0]])      # (launched now: img is a view of a static buffer)
-            if calculate_scale:      # least-squares scale between metric prediction and target (test.py:365-378; last key wins there, too)
+            if host_scale:           # least-squares scale between metric prediction and target (test.py:365-378; last key wins there, too)
                 for key, img in preds.items():
                     p = np.exp(reg_factor * (img[0][0].cpu().numpy() - np.float32(1.0))) * clip_distance
                     t = np.exp(reg_factor * (package['depth_' + key][0][0].cpu().numpy() - np.float32(1.0))) * clip_distance
@@ -106,8 +190,13 @@ def stream_dataset(model, dataset, every_x_rgb_frame, output_folder=None, settle
             sequence_idx += 1
             prev_dataset_idx = dataset_idx
     model.train(was_training)
+    if device_scale:
+        scale = torch.cat(device_scales).cpu().numpy() if device_scales else np.empty(0)         # the one read-back
     info = {"items": n, "saved": saved,
             "scale": (float(np.mean(scale)), float(np.min(scale)), float(np.max(scale))) if calculate_scale else None}
+    if metrics:
+        rows = torch.cat(metric_rows).cpu().numpy() if metric_rows else None                       # the one read-back
+        info["total_metrics"] = None if rows is None else np.sum(rows, 0) / len(rows)
     if tables is not None:
         info["tables"] = tables
     return info

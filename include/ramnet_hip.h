@@ -45,7 +45,7 @@ enum ramnet_in_mode {
 /* ---- arithmetic of the MFMA contraction: exact fp32 on v_mfma_f32_32x32x2_f32 / v_mfma_f32_16x16x4_f32 (bit-identical to
  * an fmaf chain, 157 TFLOP/s peak).  There is no reduced-precision mode. */
 /* RAMNET_ALGO_WINOGRAD: F(2x2,3x3), fp32; only the dense 3x3 stride-1 tap list, w from ramnet_pack_weight_wino() */
-/* RAMNET_ALGO_HEAD: the 5x5 stride-1 head layers with 1, 3 or 5 real input channels and <= 32 outputs (statenet.py:160-175):
+/* RAMNET_ALGO_HEAD: the 5x5 stride-1 head layers with 1, 3, 5 or 10 real input channels and <= 32 outputs (statenet.py:160-175):
  * dense (tap, channel) reduction, weights from ramnet_pack_weight_head() held in registers; fp32 */
 /* RAMNET_ALGO_WINOGRAD24: all four output parities of the folded upsample-conv (decoders, statenet.py:305-308) as Winograd
  * F(2x2,4x4) convolutions of the replicate-padded low-res input: x0 = [B][Hin = H+4][Win = W+4][C0] (ramnet_pad2_sum),
@@ -128,7 +128,7 @@ typedef struct ramnet_conv_desc {
     int out_s2d;                    /* C > 0 (WINOGRAD, LINEAR epilogue, no bias, beta = 0): the Cout = 4*C output channels are the
                                      * space-to-depth view of out [B][HoF = 2*Ho][WoF = 2*Wo][C]: channel (a*2+c)*C + ch of pixel (i, j)
                                      * is stored at out(2i+a, 2j+c, ch) — backward-data of the encoders.  C a power of two >= 8  */
-    int head_cin;                   /* RAMNET_ALGO_HEAD: real input channels (1, 3 or 5) among the C0 padded ones of x0       */
+    int head_cin;                   /* RAMNET_ALGO_HEAD: real input channels (1, 3, 5 or 10) among the C0 padded ones of x0   */
     int s2d_5x5;                    /* 1 (WINOGRAD with in_mode RAMNET_IN_S2D, or with out_s2d): the 3x3 filter over the space-to-depth
                                      * view is that of a 5x5 stride-2 layer — its slices (dy = +1, row parity 1) and (dx = +1, column
                                      * parity 1) are zero (11 of 36) — and the kernel skips the Winograd positions those zeros annihilate
@@ -184,7 +184,7 @@ typedef struct ramnet_wgrad_desc {
                                      * or RAMNET_ALGO_WINOGRAD24_2X3 where ramnet_fold_wgrad_variant() says so: dw = [4][30][C0][Cout] */
     int gsy, gsx, goy, gox;         /* dout / gmask are read at pixel (oy*gsy + goy, ox*gsx + gox) of a [B, HoG, WoG] tensor      */
     int HoG, WoG;                   /* (all 0 = dense [B, Ho, Wo]; DIRECT only): one output parity of the folded upsample-conv  */
-    int head_cin;                   /* RAMNET_ALGO_HEAD (dense 5x5 stride-1 taps, Cout <= 32): real input channels (1, 3 or 5); dw keeps
+    int head_cin;                   /* RAMNET_ALGO_HEAD (dense 5x5 stride-1 taps, Cout <= 32): real input channels (1, 3, 5 or 10); dw keeps
                                      * the DIRECT layout [25][C0][Cout]                                                          */
     int dw_slabs;                   /* RAMNET_ALGO_WINOGRAD: 0 = dw is ONE [16][Cin][Cout] workspace, the tile splits of a launch meet in it by
                                      * atomic adds; S > 0 = dw is [S][16][Cin][Cout] and dbias [S][Cout] (S >= 1, ramnet_wgrad_wino_slabs()):
@@ -314,7 +314,9 @@ int ramnet_pack_border_weights(const float *w_oihw, float *rows, float *cols, fl
  * 64-column workgroups (the pair form included) and backward-data launches; force: skip the size heuristics (tests), which keep
  * launches below a few rounds of workgroups and launches that would split their reduction on F(2x2).
  * ramnet_pack_weight_fold_wino2x3 (forward; 64-column layouts only) / _dgrad (RAMNET_IN_PARITY4; Cin % 64 == 0): 120*Cout*Cin floats
- * (ramnet_packed_weight_elems_fold_wino2x3), evaluated in double like the F(2x2) packs.                                               */
+ * (ramnet_packed_weight_elems_fold_wino2x3).  All four fold packs are the fp32 rounding of the rational U: they evaluate
+ * (6 G)(4 FA) w (4 FA)^T (6 G | 3 Gc)^T with integer matrices (sums in double) and divide once by 576 | 288; ramnet_fold_unpack_wgrad[2x3] folds
+ * the same way (double, one division by 576).                                                                                           */
 int ramnet_fold_wino_variant(const ramnet_conv_desc *d, int force);
 size_t ramnet_packed_weight_elems_fold_wino2x3(int Cout, int Cin);
 int ramnet_pack_weight_fold_wino2x3(const float *w_oihw, float *wp, int Cout, int Cin, void *stream);
@@ -361,7 +363,11 @@ int ramnet_unpack_wgrad_wino2x4(const float *ws, float *grad_oihw, int Cout, int
  * (Ho - 1) * osy + ooy >= HoF or (Wo - 1) * osx + oox >= WoF (under out_s2d: HoF < 2 * Ho or WoF < 2 * Wo).  The descriptors of a ramnet_conv_launch_multi must also agree in HoF, WoF, ldo, Hin, Win,
  * C0, C1, ld0, ld1 and ldm (the kernel takes them from descs[0]).  Hin / Win need not agree with Ho / Wo, stride and taps: every tap is tested
  * against the image and reads zero outside it.
- * ramnet_wgrad_launch refuses, for every algorithm, ld0 < C0, ld1 < C1 (CAT*), ldm < C1 (CAT_MUL) or < C0 (RELUMASK), ldg < Cout and ldgm < Cout. */
+ * RAMNET_ALGO_HEAD, _WINOGRAD24 and _WINOGRAD24_2X3 (forward and RAMNET_IN_PARITY4) refuse ld0 < C0 and ldo < Cout as well (their other conditions stand at
+ * the algorithms above: exact Hin / Win / HoF / WoF relations, unit output strides).  With frame > 0 EVERY family refuses lde0 < frame * Cout,
+ * lde1 < frame * Cout and bands that would meet (2 * frame > HoF or > WoF).
+ * ramnet_wgrad_launch refuses, for every algorithm, ld0 < C0, ld1 < C1 (CAT*), ldm < C1 (CAT_MUL) or < C0 (RELUMASK), ldg < Cout and ldgm < Cout, and
+ * Cout % 4 != 0 or ldg % 4 != 0 (ldgm % 4 != 0 with a mask): every backward-weights kernel, the head's included, loads the gradient in quads. */
 int ramnet_conv_launch(const ramnet_conv_desc *d, void *stream);    /* forward and backward-data   */
 /* n <= 4 descriptors that differ only in tap list and output sub-grid (ntaps, dy, dx, wtap, Ho, Wo, ooy, oox): the four
  * output-parity classes of a stride-2 backward-data / transposed convolution, executed as ONE launch.            */

@@ -283,7 +283,7 @@ int launch_head(const ramnet_conv_desc &d, hipStream_t st) {
     q.ld = d.ld0, q.ldo = d.ldo, q.B = d.B, q.H = d.Hin, q.W = d.Win, q.Cout = d.Cout, q.relu = d.epi == RAMNET_EPI_RELU;
     q.tiles_x = cdiv(d.Wo, HT_W), q.tiles_y = cdiv(d.Ho, HF_H);
     const dim3 grid(q.tiles_x * q.tiles_y * d.B);
-    note_kernel("conv_head_fwd_kernel<%d>", d.head_cin == 1 ? 1 : d.head_cin == 3 ? 3 : 5);
+    note_kernel("conv_head_fwd_kernel<%d>", d.head_cin);      // (head_channels_ok: 1, 3, 5 or 10, one instantiation each)
     if (d.head_cin == 1) hipLaunchKernelGGL(conv_head_fwd_kernel<1>, grid, dim3(256), 0, st, q);
     else if (d.head_cin == 3) hipLaunchKernelGGL(conv_head_fwd_kernel<3>, grid, dim3(256), 0, st, q);
     else if (d.head_cin == 10) hipLaunchKernelGGL(conv_head_fwd_kernel<10>, grid, dim3(256), 0, st, q);

@@ -271,6 +271,12 @@ static int check_desc(const ramnet_conv_desc &d) {
             if (d.epi == RAMNET_EPI_SIGMOID_HR) RAMNET_CHECK_ARG(d.lde1 >= d.Cout / 2 && d.ldo1 >= d.Cout / 2);
         }
     }
+    // The head and the folded families index x0 and out with ld0 / ldo as they are too (the folded kernels bound x0 by a buffer resource of
+    // B * Hin * Win * ld0 floats, so a short ld0 would read zeros, not fault; a short ldo stores past the last pixel).
+    if (d.algo == RAMNET_ALGO_HEAD || d.algo == RAMNET_ALGO_WINOGRAD24 || d.algo == RAMNET_ALGO_WINOGRAD24_2X3)
+        RAMNET_CHECK_ARG(d.ld0 >= d.C0 && d.ldo >= d.Cout && d.HoF > 0 && d.WoF > 0);
+    // frame (every family that takes it: epilogue_side reads slot * Cout + n, slot < frame, of a row of lde1 / lde0 floats)
+    if (d.frame > 0) RAMNET_CHECK_ARG((long)d.lde0 >= (long)d.frame * d.Cout && (long)d.lde1 >= (long)d.frame * d.Cout && 2 * d.frame <= d.HoF && 2 * d.frame <= d.WoF);
     return 0;
 }
 

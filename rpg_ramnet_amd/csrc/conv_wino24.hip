@@ -416,21 +416,43 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
 }
 
 // OIHW 5x5 weights of an UpsampleConvLayer -> U = G W4 G^T of the four 4x4 parity filters W4 = A_py w A_px^T (the bilinear x2
-// upsample folded into the filter) in the lane order of the kernel's B operand; evaluated in double.
+// upsample folded into the filter) in the lane order of the kernel's B operand; integer matrices, double sums, one division.
 // TW = 3: F(2x3, 4x4), U = G W4 Gc^T with the 6 x 4 column matrix Gc (30 positions, pos = a*6 + b).
-__device__ __forceinline__ double fold_wino_gc(int tw, int b, int s) {
-    const double G[5][4] = {{0.5, 0, 0, 0}, {-0.5, -0.5, -0.5, -0.5}, {-1.0 / 6, 1.0 / 6, -1.0 / 6, 1.0 / 6}, {1.0 / 6, 1.0 / 3, 2.0 / 3, 4.0 / 3}, {0, 0, 0, 1}};
-    const double G3[6][4] = {{4, 0, 0, 0}, {2.0 / 3, 2.0 / 3, 2.0 / 3, 2.0 / 3}, {2.0 / 3, -2.0 / 3, 2.0 / 3, -2.0 / 3},
-                             {-8.0 / 3, -4.0 / 3, -2.0 / 3, -1.0 / 3}, {-8.0 / 3, 4.0 / 3, -2.0 / 3, 1.0 / 3}, {0, 0, 0, 1}};
-    return tw == 2 ? G[b][s] : G3[b][s];
+// The packs evaluate U through the INTEGER matrices 6 G, 3 Gc and 4 FA and divide once: U = (6 G)(4 FA) w (4 FA)^T (6 G | 3 Gc)^T / (16 x 36 | 16 x 18)
+// is then the rounding of the rational (a transformed weight that cancels comes out as 0, not as a 2^-5x residue of the double 1.0 / 6).
+__device__ __forceinline__ int fold_wino_g6(int a, int t) {            // 6 G of F(2,4), points 0, 1, -1, 2, inf
+    const int G6[5][4] = {{3, 0, 0, 0}, {-3, -3, -3, -3}, {-1, 1, -1, 1}, {1, 2, 4, 8}, {0, 0, 0, 6}};
+    return G6[a][t];
+}
+__device__ __forceinline__ int fold_wino_gc3(int b, int s) {           // 3 Gc of F(3,4), points 0, 1, -1, 1/2, -1/2, inf
+    const int G3[6][4] = {{12, 0, 0, 0}, {2, 2, 2, 2}, {2, -2, 2, -2}, {-8, -4, -2, -1}, {-8, 4, -2, 1}, {0, 0, 0, 3}};
+    return G3[b][s];
+}
+__device__ __forceinline__ int fold_fa4(int p, int t, int k) {         // 4 FA: the bilinear fold (ops.FOLD_A)
+    const int FA4[2][4][5] = {{{1, 0, 0, 0, 0}, {3, 3, 1, 0, 0}, {0, 1, 3, 3, 1}, {0, 0, 0, 1, 3}}, {{3, 1, 0, 0, 0}, {1, 3, 3, 1, 0}, {0, 0, 1, 3, 3}, {0, 0, 0, 0, 1}}};
+    return FA4[p][t][k];
+}
+// column matrix of a TW-wide tile times its denominator (6 for F(2,4), 3 for F(3,4))
+__device__ __forceinline__ int fold_wino_gci(int tw, int b, int s) { return tw == 2 ? fold_wino_g6(b, s) : fold_wino_gc3(b, s); }
+// U of one (position (a, b), parities (py, px), flipped or not) from the 25 taps wk of one (output, input) channel pair
+__device__ __forceinline__ float fold_wino_u(int tw, int a, int b, int py, int px, bool flip, const float *__restrict__ wk) {
+    int ga[5], gb[5];                               // ga[kh] = sum_t (6 G)[a][t] (4 FA)[py][t][kh], gb the same along the columns
+    for (int kh = 0; kh < 5; ++kh) {
+        ga[kh] = 0, gb[kh] = 0;
+        for (int t = 0; t < 4; ++t) {
+            const int tt = flip ? 3 - t : t;
+            ga[kh] += fold_wino_g6(a, t) * fold_fa4(py, tt, kh), gb[kh] += fold_wino_gci(tw, b, t) * fold_fa4(px, tt, kh);
+        }
+    }
+    double u = 0;                                   // (integer x fp32 products: exact in double)
+    for (int kh = 0; kh < 5; ++kh)
+        for (int kw = 0; kw < 5; ++kw) u += (double)(ga[kh] * gb[kw]) * (double)wk[kh * 5 + kw];
+    return (float)(u / (tw == 2 ? 576.0 : 288.0));
 }
 
 template <int TW>
 __global__ void pack_weight_fold_wino_kernel(const float *__restrict__ w, float *__restrict__ wp, int Cout, int Cin, int kc, int ncq,
                                              int pair, size_t total) {
-    const double FA[2][4][5] = {{{.25, 0, 0, 0, 0}, {.75, .75, .25, 0, 0}, {0, .25, .75, .75, .25}, {0, 0, 0, .25, .75}},
-                                {{.75, .25, 0, 0, 0}, {.25, .75, .75, .25, 0}, {0, 0, .25, .75, .75}, {0, 0, 0, 0, .25}}};
-    const double G[5][4] = {{0.5, 0, 0, 0}, {-0.5, -0.5, -0.5, -0.5}, {-1.0 / 6, 1.0 / 6, -1.0 / 6, 1.0 / 6}, {1.0 / 6, 1.0 / 3, 2.0 / 3, 4.0 / 3}, {0, 0, 0, 1}};
     constexpr int WC = TW + 3, NP = 5 * WC;
     const int vec = kc / 4, nblk = pair ? 1 : Cout / (16 * ncq), nch = Cin / kc;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -454,16 +476,7 @@ __global__ void pack_weight_fold_wino_kernel(const float *__restrict__ w, float 
         const int n = pair ? col & 31 : col;
         const int py = pair ? cls : cls >> 1, px = pair ? col >> 5 : cls & 1, a = pos / WC, b = pos % WC;
         // U[a][b] = sum_{t,s} G[a][t] G[b][s] sum_{kh,kw} FA[py][t][kh] FA[px][s][kw] w[n][k][kh][kw]
-        double ga[5], gb[5];                        // rows of G^T... combined with the fold: ga[kh] = sum_t G[a][t] FA[py][t][kh]
-        for (int kh = 0; kh < 5; ++kh) {
-            ga[kh] = 0, gb[kh] = 0;
-            for (int t = 0; t < 4; ++t) ga[kh] += G[a][t] * FA[py][t][kh], gb[kh] += fold_wino_gc(TW, b, t) * FA[px][t][kh];
-        }
-        double u = 0;
-        const float *wk = w + ((size_t)n * Cin + k) * 25;
-        for (int kh = 0; kh < 5; ++kh)
-            for (int kw = 0; kw < 5; ++kw) u += ga[kh] * gb[kw] * (double)wk[kh * 5 + kw];
-        wp[i] = (float)u;
+        wp[i] = fold_wino_u(TW, a, b, py, px, false, w + ((size_t)n * Cin + k) * 25);
     }
 }
 
@@ -675,12 +688,9 @@ int launch_wino24(const ramnet_conv_desc &d, hipStream_t st) {
 // of the channels swapped — reduce over k = (parity class (p, q), output channel n), produce input channels c.  Layout = the forward pack's
 // with one class, chunks of 16 and 64-column blocks: i = ((((chunk*NB + nb)*25 + pos)*4 + cq)*4 + ks)*64 + l15*4 + j,
 // k = chunk*16 + ks*4 + j = (p*2 + q)*Cout + n, c = nb*64 + cq*16 + l15;
-// U[a][b][k][c] = sum_{t,s} G[a][t] G[b][s] W4[n][c][p][q][3-t][3-s],  W4 = FA_p w FA_q^T (double arithmetic, like the forward pack)
+// U[a][b][k][c] = sum_{t,s} G[a][t] G[b][s] W4[n][c][p][q][3-t][3-s],  W4 = FA_p w FA_q^T (integer matrices and one division, like the forward pack)
 template <int TW>
 __global__ void pack_weight_fold_wino_dgrad_kernel(const float *__restrict__ w, float *__restrict__ wp, int Cout, int Cin, size_t total) {
-    const double FA[2][4][5] = {{{.25, 0, 0, 0, 0}, {.75, .75, .25, 0, 0}, {0, .25, .75, .75, .25}, {0, 0, 0, .25, .75}},
-                                {{.75, .25, 0, 0, 0}, {.25, .75, .75, .25, 0}, {0, 0, .25, .75, .75}, {0, 0, 0, 0, .25}}};
-    const double G[5][4] = {{0.5, 0, 0, 0}, {-0.5, -0.5, -0.5, -0.5}, {-1.0 / 6, 1.0 / 6, -1.0 / 6, 1.0 / 6}, {1.0 / 6, 1.0 / 3, 2.0 / 3, 4.0 / 3}, {0, 0, 0, 1}};
     constexpr int WC = TW + 3, NP = 5 * WC;
     const int NB = Cin / 64;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -692,16 +702,7 @@ __global__ void pack_weight_fold_wino_dgrad_kernel(const float *__restrict__ w, 
         const int nb = (int)(r % NB), chunk = (int)(r / NB);
         const int k = chunk * 16 + ks * 4 + j, c = nb * 64 + cq * 16 + l15;
         const int pq = k / Cout, n = k - pq * Cout, pp = pq >> 1, qq = pq & 1, a = pos / WC, b = pos % WC;
-        double ga[5], gb[5];
-        for (int kh = 0; kh < 5; ++kh) {
-            ga[kh] = 0, gb[kh] = 0;
-            for (int t = 0; t < 4; ++t) ga[kh] += G[a][t] * FA[pp][3 - t][kh], gb[kh] += fold_wino_gc(TW, b, t) * FA[qq][3 - t][kh];
-        }
-        double u = 0;
-        const float *wk = w + ((size_t)n * Cin + c) * 25;
-        for (int kh = 0; kh < 5; ++kh)
-            for (int kw = 0; kw < 5; ++kw) u += ga[kh] * gb[kw] * (double)wk[kh * 5 + kw];
-        wp[i] = (float)u;
+        wp[i] = fold_wino_u(TW, a, b, pp, qq, true, w + ((size_t)n * Cin + c) * 25);
     }
 }
 
@@ -734,68 +735,69 @@ __global__ void pack_border_weights_kernel(const float *__restrict__ w, float *_
 
 // End of a backward pass of a folded decoder: dW5[o][i][k][l] += sum_{p,q,t,s} FA[p][t][k] FA[q][s][l] dW4[p][q][t][s][i][o]
 //   - (border-GEMM gradients routed back to the taps they summed),   dW4 = w4 (direct parity launches) + G^T dU G (Winograd-domain launches)
-//   + G^T dU3 Gc (F(2x3,4x4) launches, csrc/conv_wgrad_wino24.hip: [4][30][CinWs][Cout], Gc = fold_wino_gc(3, ., .)).
+//   + G^T dU3 Gc (F(2x3,4x4) launches, csrc/conv_wgrad_wino24.hip: [4][30][CinWs][Cout], Gc = fold_wino_gc3 / 3).
 // One thread per (o, i); the workspaces it reads are zeroed for the next pass.
 __global__ void fold_unpack_wgrad_kernel(float *__restrict__ w4, float *__restrict__ dU, float *__restrict__ dU3, float *__restrict__ wr,
                                          float *__restrict__ wc, float *__restrict__ grad, int Cout, int Cin, int CinWs) {
-    const float FA[2][4][5] = {{{.25f, 0, 0, 0, 0}, {.75f, .75f, .25f, 0, 0}, {0, .25f, .75f, .75f, .25f}, {0, 0, 0, .25f, .75f}},
-                               {{.75f, .25f, 0, 0, 0}, {.25f, .75f, .75f, .25f, 0}, {0, 0, .25f, .75f, .75f}, {0, 0, 0, 0, .25f}}};
-    const float G[5][4] = {{0.5f, 0, 0, 0}, {-0.5f, -0.5f, -0.5f, -0.5f}, {-1.f / 6, 1.f / 6, -1.f / 6, 1.f / 6}, {1.f / 6, 1.f / 3, 2.f / 3, 4.f / 3}, {0, 0, 0, 1.f}};
+    // Folded in double through the integer matrices 4 FA, 6 G and 3 Gc with ONE division (as the packs above and unpack_wgrad_wino2x4_kernel):
+    // 576 dW5 = sum (4 FA)(4 FA) [36 w4 + (6 G)^T dU (6 G) + 2 (6 G)^T dU3 (3 Gc)] — a gradient that is an fp32 number comes out as that number.
     const size_t total = (size_t)Cout * Cin;
     for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
         const int o = (int)(idx % Cout), i = (int)(idx / Cout);        // (consecutive threads: consecutive o = the workspaces' fastest index)
-        float g5[25];
-        for (int e = 0; e < 25; ++e) g5[e] = 0.f;
+        double g5[25];
+        for (int e = 0; e < 25; ++e) g5[e] = 0.0;
         for (int pq = 0; pq < 4; ++pq) {
             const int pp = pq >> 1, qq = pq & 1;
-            float d4[16];
+            double d4[16];                          // 36 dW4 of the class
             for (int ts = 0; ts < 16; ++ts) {
                 float *cell = w4 + ((size_t)(pq * 16 + ts) * CinWs + i) * Cout + o;
-                d4[ts] = *cell;
+                d4[ts] = 36.0 * (double)*cell;
                 *cell = 0.f;
             }
             if (dU != nullptr) {
                 for (int ab = 0; ab < 25; ++ab) {
                     float *cell = dU + ((size_t)(pq * 25 + ab) * CinWs + i) * Cout + o;
-                    const float u = *cell;
+                    const double u = (double)*cell;
                     *cell = 0.f;
                     const int a = ab / 5, b = ab % 5;
                     for (int t = 0; t < 4; ++t)
-                        for (int s = 0; s < 4; ++s) d4[t * 4 + s] += G[a][t] * G[b][s] * u;
+                        for (int s = 0; s < 4; ++s) d4[t * 4 + s] += (double)(fold_wino_g6(a, t) * fold_wino_g6(b, s)) * u;
                 }
             }
             if (dU3 != nullptr) {
                 for (int ab = 0; ab < 30; ++ab) {
                     float *cell = dU3 + ((size_t)(pq * 30 + ab) * CinWs + i) * Cout + o;
-                    const float u = *cell;
+                    const double u = (double)*cell;
                     *cell = 0.f;
                     const int a = ab / 6, b = ab % 6;
                     for (int t = 0; t < 4; ++t)
-                        for (int s = 0; s < 4; ++s) d4[t * 4 + s] += G[a][t] * (float)fold_wino_gc(3, b, s) * u;
+                        for (int s = 0; s < 4; ++s) d4[t * 4 + s] += (double)(2 * fold_wino_g6(a, t) * fold_wino_gc3(b, s)) * u;
                 }
             }
             for (int t = 0; t < 4; ++t)
                 for (int s = 0; s < 4; ++s) {
-                    const float v = d4[t * 4 + s];
+                    const double v = d4[t * 4 + s];
                     for (int k = 0; k < 5; ++k) {
-                        const float fk = FA[pp][t][k] * v;
-                        for (int l = 0; l < 5; ++l) g5[k * 5 + l] += fk * FA[qq][s][l];
+                        const int fk = fold_fa4(pp, t, k);
+                        if (fk == 0) continue;
+                        for (int l = 0; l < 5; ++l) g5[k * 5 + l] += (double)(fk * fold_fa4(qq, s, l)) * v;
                     }
                 }
         }
+        for (int e = 0; e < 25; ++e) g5[e] /= 576.0;        // 16 from the two 4 FA, 36 from 6 G x 6 G (= 2 x 6 G x 3 Gc)
         for (int side = 0; side < 2; ++side)
             for (int slot = 0; slot < 2; ++slot) {
                 const int a0 = side == 0 ? 0 : (slot == 0 ? 4 : 3), na = side == 0 ? (slot == 0 ? 2 : 1) : (slot == 0 ? 1 : 2);
                 for (int kb = 0; kb < 5; ++kb) {
                     float *rc = wr + (((size_t)side * 5 + kb) * Cin + i) * 2 * Cout + (size_t)slot * Cout + o;
                     float *cc = wc + (((size_t)side * 5 + kb) * Cin + i) * 2 * Cout + (size_t)slot * Cout + o;
-                    const float r = *rc, c = *cc;
+                    const double r = (double)*rc, c = (double)*cc;
                     *rc = 0.f, *cc = 0.f;
                     for (int e = 0; e < na; ++e) g5[(a0 + e) * 5 + kb] -= r, g5[kb * 5 + (a0 + e)] -= c;
                 }
             }
         float *g = grad + ((size_t)o * Cin + i) * 25;
-        for (int e = 0; e < 25; ++e) g[e] += g5[e];
+        for (int e = 0; e < 25; ++e) g[e] = (float)((double)g[e] + g5[e]);
     }
 }
 

@@ -211,3 +211,188 @@ def test_coherent_row_separates_the_third_term():
     lost = 16 * 57 * 2.0 ** -23
     assert abs(float(st.out[0, 0, 0, 0]) - 16 * cc.COHERENT_V) < 1e-5
     assert lost > 3 * float(st.b_out[0, 0, 0, 0]) and lost < 2e-5 * float(st.out.abs().max())
+
+
+# ================================================================================================ head, folded decoders, UP2X loaders
+import fold_head_cases as fh                        # noqa: E402
+
+
+def _layer(seed, B, H, W, Cin, Cout):
+    g = torch.Generator().manual_seed(seed)
+    x, skip = torch.randn(B, H, W, Cin, generator=g, dtype=F64), torch.randn(B, H, W, Cin, generator=g, dtype=F64)
+    return x, skip, torch.randn(Cout, Cin, 5, 5, generator=g, dtype=F64), torch.randn(Cout, generator=g, dtype=F64)
+
+
+def test_up2x_is_bilinear_align_corners_false():
+    x = torch.randn(2, 5, 7, 3, generator=torch.Generator().manual_seed(3), dtype=F64)
+    close(cr.up2x(x), nhwc(F.interpolate(nchw(x), scale_factor=2, mode="bilinear", align_corners=False)), "up2x")
+    d = types.SimpleNamespace(in_mode=cr.IN_UP2X_SKIP, x0=x, x1=2 * x)
+    close(cr.logical_input(d), 3 * cr.up2x(x), "UP2X_SKIP")
+
+
+@pytest.mark.parametrize("H,W", [(2, 2), (3, 5), (6, 4)])
+def test_fold_with_frame_is_the_layer_on_the_whole_image(H, W):
+    """fold_statement on pad2(x + skip) with the frame operands of border_operands = relu(conv5x5, zero-padded, of up2x(x + skip) + b) on
+    EVERY pixel; without the frame the interior alone agrees; frame operands of zero equal no frame; both families and the pair tiling
+    reproduce the class tap sums with their signed matrices"""
+    B, Cin, Cout = 2, 3, 4
+    x, skip, w, b = _layer(H * 10 + W, B, H, W, Cin, Cout)
+    ref = nhwc(F.conv2d(F.interpolate(nchw(x + skip), scale_factor=2, mode="bilinear", align_corners=False), w, b, 1, 2)).clamp_min(0)
+    e0, e1 = cr.border_operands(x + skip, w)
+    d = types.SimpleNamespace(x0=cr.pad2(x + skip), w5=w, bias=b, epi=cr.EPI_RELU, frame=2, e0=e0, e1=e1, Ho=H, Wo=W, HoF=2 * H, WoF=2 * W, Cout=Cout)
+    for fam in ("fold2x2", "fold2x3"):
+        st = cr.fold_statement(d, fam)
+        close(st.out, ref, fam)
+        assert bool((st.pre_abs >= st.pre.abs() * (1 - 1e-12)).all())
+    bare = types.SimpleNamespace(**dict(vars(d), frame=0, e0=None, e1=None))
+    zero = types.SimpleNamespace(**dict(vars(d), e0=torch.zeros_like(e0), e1=torch.zeros_like(e1)))
+    s0, sz = cr.fold_statement(bare, "fold2x2"), cr.fold_statement(zero, "fold2x2")
+    assert torch.equal(s0.out, sz.out) and torch.equal(s0.pre_abs, sz.pre_abs)
+    if H > 2 and W > 2:
+        close(s0.out[:, 2:-2, 2:-2], ref[:, 2:-2, 2:-2], "interior without the frame")
+        assert float((s0.out - ref).abs().max()) > 1e-3
+    W4 = cr.fold_w4(w)
+    for py in range(2):
+        for px in range(2):
+            Wc = W4[:, :, py, px].permute(2, 3, 1, 0).reshape(16, Cin, Cout)
+            acc, _ = cr.reduction(d.x0, Wc, cr.fold_taps(py, px), 1, H, W)
+            for fam in ("fold2x2", "fold2x3"):
+                for shift in (0, 1) if px == 1 else (0,):
+                    close(cr.fold_wino(d.x0, Wc, py, px, H, W, fam, shift=shift, absolute=False), acc, (fam, py, px, shift))
+
+
+def test_frame_on_the_direct_statement():
+    """the four parity classes as direct sub-grid descriptors with frame = 2 (the folded_direct path) give the same image"""
+    B, H, W, Cin, Cout = 1, 3, 4, 2, 3
+    x, skip, w, b = _layer(11, B, H, W, Cin, Cout)
+    e0, e1 = cr.border_operands(x + skip, w)
+    ref = nhwc(F.conv2d(F.interpolate(nchw(x + skip), scale_factor=2, mode="bilinear", align_corners=False), w, b, 1, 2))
+    W4 = cr.fold_w4(w)
+    out = torch.zeros_like(ref)
+    for py in range(2):
+        for px in range(2):
+            d = types.SimpleNamespace(in_mode=cr.IN_PLAIN, x0=cr.pad2(x + skip), W=W4[:, :, py, px].permute(2, 3, 1, 0).reshape(16, Cin, Cout),
+                                      taps=cr.fold_taps(py, px), stride=1, Ho=H, Wo=W, HoF=2 * H, WoF=2 * W, os=(2, 2, py, px), bias=b, epi=cr.EPI_LINEAR,
+                                      beta=0.0, e0=e0, e1=e1, frame=2, out_old=None, active=None, out_s2d=0, Cout=Cout)
+            st = cr.conv_statement(d)
+            out = out + st.out * st.w_out
+    close(out, ref, "direct classes with frame")
+
+
+def test_parity4_is_the_gradient_of_the_fold():
+    B, H, W, Cin, Cout = 2, 3, 4, 3, 2
+    g = torch.Generator().manual_seed(9)
+    xpad = torch.randn(B, H + 4, W + 4, Cin, generator=g, dtype=F64, requires_grad=True)
+    w, gy = torch.randn(Cout, Cin, 5, 5, generator=g, dtype=F64), torch.randn(B, 2 * H, 2 * W, Cout, generator=g, dtype=F64)
+    W4 = cr.fold_w4(w)
+    out = torch.zeros(B, 2 * H, 2 * W, Cout, dtype=F64)
+    for py in range(2):
+        for px in range(2):
+            out[:, py::2, px::2] = nhwc(F.conv2d(nchw(xpad)[:, :, py:py + H + 3, px:px + W + 3], W4[:, :, py, px]))
+    (out * gy).sum().backward()
+    taps, Wt = cr.parity4_taps_weights(w)
+    d = types.SimpleNamespace(in_mode=cr.IN_PARITY4, x0=gy)
+    acc, _ = cr.reduction(cr.logical_input(d), Wt, taps, 1, H + 4, W + 4)
+    close(acc, xpad.grad, "PARITY4")
+    for fam in ("fold2x2", "fold2x3"):
+        close(cr.parity4_wino(gy, w, fam, absolute=False), acc, fam)
+        assert bool((cr.parity4_wino(gy, w, fam) >= acc.abs() * (1 - 1e-12)).all())
+
+
+def test_fold_backward_weights_against_autograd():
+    """fold_wgrad_statement + fold_unpack_statement = the autograd gradient of the 5x5 weights through the four parity convolutions (mask
+    and bias included); both transformed-domain forms fold back to the same dW4; HEAD and the sub-grid form of DIRECT are wgrad_statement on
+    their tap lists, which test_wgrad_statement_against_autograd anchors"""
+    g = torch.Generator().manual_seed(1)
+    B, H, W, C, N = 2, 3, 5, 3, 2
+    xpad = torch.randn(B, H + 4, W + 4, C, generator=g, dtype=F64)
+    w = torch.zeros(N, C, 5, 5, dtype=F64, requires_grad=True)
+    b = torch.zeros(N, dtype=F64, requires_grad=True)
+    dout, gm = torch.randn(B, 2 * H, 2 * W, N, generator=g, dtype=F64), torch.randn(B, 2 * H, 2 * W, N, generator=g, dtype=F64)
+    W4 = cr.fold_w4(w)
+    out = torch.zeros(B, 2 * H, 2 * W, N, dtype=F64)
+    for py in range(2):
+        for px in range(2):
+            out[:, py::2, px::2] = nhwc(F.conv2d(nchw(xpad)[:, :, py:py + H + 3, px:px + W + 3], W4[:, :, py, px], b))
+    (out * dout * (gm > 0)).sum().backward()
+    d = types.SimpleNamespace(x0=xpad, dout=dout, gmask=gm, Ho=H, Wo=W)
+    st = cr.fold_wgrad_statement(d)
+    old = torch.randn(N, C, 5, 5, generator=g, dtype=F64)
+    w4, wr = torch.randn(4, 16, C, N, generator=g, dtype=F64), torch.randn(2, 5 * C, 2 * N, generator=g, dtype=F64)
+    close(cr.fold_unpack_statement(old, st.dW4, torch.zeros_like(w4), torch.zeros_like(wr), torch.zeros_like(wr)), old + w.grad, "dW5")
+    close(st.dbias, b.grad, "dbias")
+    import torch_restatements as tr
+    ref = tr.fold_unpack_torch(w4.float().reshape(-1), None, wr.float(), (2 * wr).float(), N, C, C)      # (the fp32 restatement of the product path)
+    got = cr.fold_unpack_statement(torch.zeros_like(old), torch.zeros_like(w4), w4, wr, 2 * wr)
+    assert float((got - ref.to(F64)).abs().max()) < 1e-5 * float(got.abs().max()), "direct and border workspaces"
+    for fam in ("fold2x2", "fold2x3"):
+        dU, folded, n = cr.fold_wgrad_wino(d, fam, absolute=False)
+        close(folded, st.dW4, fam)
+        assert bool((cr.fold_wgrad_wino(d, fam)[1] >= st.dW4.abs() * (1 - 1e-12)).all()) and n == B * 2 * -(-W // cr.FOLD_TW[fam])
+
+
+def test_pack_statements_are_the_rounding_of_the_rational():
+    """fold_u through the integer matrices = G W4 Gc^T with the fractions of the header; on the exact rule's weights (9 x integers) it is a
+    multiple of 2^-6 (F(2x2)) / 2^-5 (F(2x3)) with few bits: an fp32 number; the layouts against the header's index formula by hand"""
+    import torch_restatements as tr
+    import test_fold_wino2x3_cpu as t23
+    w = fh.pack_weights(32, 32, "normal")
+    close(cr.fold_u(w, 2).reshape(4, 25, 32, 32), tr.fold_weights_wino(w), "fold_u 2x2")
+    close(cr.fold_u(w, 3).reshape(4, 30, 32, 32), t23.fold_weights_wino2x3(w), "fold_u 2x3")
+    close(cr.fold_w4(w), tr.fold_weights(w), "W4")
+    for Cout, Cin in fh.PACK_SHAPES:
+        wi = fh.pack_weights(Cout, Cin, "int")
+        for tw, k in ((2, 6), (3, 5)):
+            u = cr.fold_u(wi, tw) * 2 ** k
+            assert torch.equal(u, u.round()) and float(u.abs().max()) < 2 ** 24
+            assert bool((cr.fold_u_abs(wi, tw) >= cr.fold_u(wi, tw).abs() * (1 - 1e-12)).all())
+    # one element of each layout by the header's formula, written out
+    w = fh.pack_weights(64, 32, "normal")
+    U = cr.fold_u(w, 2).reshape(4, 25, 32, 64)
+    p = cr.pack_fold_statement(w, 2)
+    cls, pos, k, n, KC, NCQ = 3, 17, 21, 45, 16, 4
+    i = ((((cls * (32 // KC) + k // KC) * (64 // (16 * NCQ)) + n // (16 * NCQ)) * 25 + pos) * NCQ + (n % (16 * NCQ)) // 16) * 16 * KC + (((k % KC) // (KC // 4)) * 16 + n % 16) * (KC // 4) + k % (KC // 4)
+    assert float(p[i]) == float(U[cls, pos, k, n])
+    assert torch.equal(torch.sort(p.abs())[0], torch.sort(U.reshape(-1).abs())[0])          # a permutation
+    w = fh.pack_weights(32, 32, "normal")
+    for pair in (False, True):
+        for tw in (2, 3):
+            p, U = cr.pack_fold_statement(w, tw, pair=pair), cr.fold_u(w, tw)
+            assert torch.equal(torch.sort(p.abs())[0], torch.sort(U.reshape(-1).abs())[0])
+    w = fh.pack_weights(32, 64, "normal")
+    for tw in (2, 3):
+        p, U = cr.pack_fold_dgrad_statement(w, tw), cr.fold_u(w, tw, dgrad=True)
+        assert torch.equal(torch.sort(p.abs())[0], torch.sort(U.reshape(-1).abs())[0])
+    rows, cols, rows_t, cols_t = cr.border_statement(w)
+    r2, c2 = tr.border_matrices(w)
+    assert torch.equal(rows, r2) and torch.equal(cols, c2) and torch.equal(rows_t, rows.transpose(1, 2))
+
+
+@pytest.mark.parametrize("c", fh.FOLD, ids=lambda c: c.name)
+def test_fold_row_can_be_judged(c):
+    d = fh.build_fold(c)
+    for t in (d.x0, d.w5, d.bias, d.e0, d.e1):
+        assert t is None or torch.equal(t, t.float().to(F64))
+    st = cr.fold_statement(d, c.fam, pair=fh.is_pair(c))
+    if c.kind == "int":
+        assert cr.fold_exact_ok(st, c.fam), "%s is not exact in fp32: abs statement x 2^%d = %.3f x 2^24" % (
+            c.name, cr.GRID_BITS[c.fam], float(st.pre_abs.max()) * 2.0 ** (cr.GRID_BITS[c.fam] - 24))
+        u = cr.fold_u(d.w5, cr.FOLD_TW[c.fam])
+        assert torch.equal(u, u.float().to(F64)), "the transformed weights must be fp32 numbers"
+    else:
+        assert bool(torch.isfinite(st.b_out).all()) and int(st.kink.sum()) <= 1e-3 * st.kink.numel(), "more than 0.1 % of the elements on a kink"
+    assert bool((st.pre_abs >= st.pre.abs() * (1 - 1e-12)).all())
+
+
+@pytest.mark.parametrize("c", fh.HEAD + [fh.HEAD_BIG], ids=lambda c: c.name)
+def test_head_row_can_be_judged(c):
+    d = fh.build_head(c)
+    if c is not fh.HEAD_BIG:
+        st = cr.conv_statement(d, "direct")
+        if c.kind == "int":
+            assert cr.exact_ok(st, "direct")
+        else:
+            assert int(st.kink.sum()) <= 1e-3 * st.kink.numel()
+    if c.kind == "int":
+        wg = cr.wgrad_statement(types.SimpleNamespace(**dict(vars(d), taps=[t[:2] for t in d.taps])))
+        assert float(wg.dW_abs.max()) * 16 < 2 ** 24 and float(wg.dbias_abs.max()) * 16 < 2 ** 24

@@ -190,7 +190,10 @@ typedef struct ramnet_wgrad_desc {
                                      * atomic adds; S > 0 = dw is [S][16][Cin][Cout] and dbias [S][Cout] (S >= 1, ramnet_wgrad_wino_slabs()):
                                      * split s owns slab s and joins it by plain read-modify-write — no atomics, and with the launches of
                                      * a layer serialised on one stream the gradient is bit-reproducible; ramnet_reduce_slabs() folds the
-                                     * slabs into slab 0 before ramnet_unpack_wgrad_wino().  Other algorithms ignore it.           */
+                                     * slabs into slab 0 before ramnet_unpack_wgrad_wino().  Every algorithm honours it: S slabs of the
+                                     * algorithm's own workspace layout and dbias [S][Cout], at most ramnet_wgrad_slabs() of them used
+                                     * (RAMNET_ALGO_WINOGRAD24 / _2X3: [S][4][25 | 30][C0][Cout]; RAMNET_ALGO_HEAD: [S][25][C0][Cout];
+                                     * RAMNET_ALGO_DIRECT, parity views included: [S][ntaps][Cin][Cout]); 0 launches the atomic kernels.      */
     int nseg;                       /* 0: one launch over x0 / x1 / xm / dout / gmask above.  1..RAMNET_WGRAD_MAX_SEGMENTS (RAMNET_ALGO_WINOGRAD_2X4
                                      * only — ramnet_wgrad_launch rejects nseg > 0 for every other algorithm): `segs` (HOST memory, copied into the kernel arguments by the launch) lists nseg tensor
                                      * sets of B images each; the launch reduces over all of them (one prologue / one join of the tile splits'
@@ -210,6 +213,8 @@ typedef struct ramnet_wgrad_desc {
  * "pred_si_cap" (256) / "pred_si_bwd_cap" (1024): workgroups per launch, over all segments, of ramnet_pred_sigmoid_si_fwd / _bwd (every
  * workgroup ends on per-segment atomics: tools/bench_pred_si.py has the sweep); ramnet_pred_si_scratch_doubles follows the option, so set it
  * before sizing the scratch.
+ * "ordered_only" (0; 1: ramnet_si_loss_fwd / ramnet_si_log_loss_fwd refuse — RAMNET_E_BADARG, nothing launched — instead of taking their
+ * zero-fill + atomics form when the fixed-order one-launch form has no library scratch: inside a stream capture, after a failed allocation).
  * ramnet_get_option: -1 if unknown.  */
 int ramnet_set_option(const char *name, int value);
 int ramnet_get_option(const char *name);
@@ -236,6 +241,17 @@ int ramnet_gemm2(const float *A, const float *B, float *C, int M, long stride_a,
                  const float *B2, float *C2, int M2, long stride_a2, long stride_b2, long stride_c2, int batch2, int N, int K, int K2, int lda,
                  int ldb, int ldc, int trans_a, int accumulate, void *stream);
 
+/* The accumulating forms (accumulate != 0) with a fixed order of the sums (additions to ABI 27): no atomics; the reduction slices of a launch that
+ * splits leave their products in `partial` (ramnet_gemm_partial_floats() floats, 16-byte aligned, any contents, owned by the launch until it has
+ * run; batch2 = 0 and M2 = K2 = 0 for ramnet_gemm_ordered; 0 floats = the launch does not split and `partial` may be NULL) and a second launch
+ * adds them to C one after the other in slice order, so the same operands give the same bits on every launch.  Everything else as above.  */
+size_t ramnet_gemm_partial_floats(int M, int N, int K, int batch, int M2, int K2, int batch2);
+int ramnet_gemm_ordered(const float *A, const float *B, float *C, int M, int N, int K, int lda, int ldb, int ldc, int trans_a, int batch,
+                        long stride_a, long stride_b, long stride_c, float *partial, void *stream);
+int ramnet_gemm2_ordered(const float *A, const float *B, float *C, int M, long stride_a, long stride_b, long stride_c, int batch, const float *A2,
+                         const float *B2, float *C2, int M2, long stride_a2, long stride_b2, long stride_c2, int batch2, int N, int K, int K2,
+                         int lda, int ldb, int ldc, int trans_a, float *partial, void *stream);
+
 /* ---- layout plumbing -------------------------------------------------------------------------- */
 /* NCHW [B,C,H,W] -> NHWC [B,H,W,Cpad] zero-padded (model inputs: model.py:177,200 `.to(self.gpu)`). */
 int ramnet_nchw_to_nhwc_pad(const float *src, float *dst, int B, int C, int H, int W, int Cpad, void *stream);
@@ -250,6 +266,15 @@ int ramnet_reflect_pad(const float *src, float *dst, int B, int C, int H, int W,
 int ramnet_wgrad_wino_slabs(int Cin, int Cout);
 int ramnet_wgrad_wino2x4_slabs(int Cin, int Cout);      /* the same for RAMNET_ALGO_WINOGRAD_2X4 launches */
 int ramnet_wgrad_dsplit_slabs(int Cin, int Cout);       /* the same for RAMNET_ALGO_DIRECT_SPLIT launches (ABI 23) */
+/* Slab forms of the other backward-weights families (additions to ABI 27).  ramnet_wgrad_slabs: the largest number of splits a launch of this
+ * descriptor's algorithm and shape (B, Ho, Wo, channels, taps, stride, in_mode; no pointer is read) uses when dw_slabs > 0 — what a caller
+ * allocates: >= 1 where the algorithm has a slab form, 0 where it has none (or the shape is not the algorithm's).  Host arithmetic only.
+ * RAMNET_ALGO_WINOGRAD24 / _2X3: the tile splits of the launch (256 workgroups over channel blocks and classes, at most one per batch of 8 | 6
+ * tiles); RAMNET_ALGO_HEAD and RAMNET_ALGO_DIRECT walk their pixel tiles with at most RAMNET_WGRAD_SLAB_CAP workgroups per channel block in
+ * the slab form (512 in the atomic form), one slab each; the 3x3 families answer what their ramnet_wgrad_*_slabs(Cin, Cout) answer.
+ * A launch with 0 < dw_slabs < ramnet_wgrad_slabs() uses dw_slabs splits.                                                              */
+#define RAMNET_WGRAD_SLAB_CAP 64
+int ramnet_wgrad_slabs(const ramnet_wgrad_desc *d);
 /* Floats of ONE slab of the RAMNET_ALGO_DIRECT_SPLIT workspace (ABI 23): blocked [9 taps][ceil(Cin/32)][ceil(Cout/32)][64 lanes][16], element
  * (tap, c, n) where ramnet_wgrad_wino2x4_ws_floats() puts (position, c, n); ramnet_unpack_wgrad_dsplit adds it into the OIHW gradient
  * [Cout][Cin][3][3] of output channels n_off .. n_off + Cout - 1 of a [CinWs][CoutWs] workspace.                                    */
@@ -462,6 +487,17 @@ int ramnet_lstm_bwd_masked(const float *gates, const float *cprev, const float *
                            const int *active, float *dpre, float *dcprev, float *dxh, size_t npix, int hw, int C, void *stream);
 /* db[C] += sum_pixels dy * (mask > 0): bias gradient of the transposed-conv decoder (submodules.py:38-66). */
 int ramnet_bias_grad(const float *dy, const float *mask, float *db, size_t npix, int C, void *stream);
+/* Ordered forms of the joins that end on fp32 atomics (additions to ABI 27): every workgroup leaves its partial sums in its own row of
+ * `partial` (any contents before; ramnet_bias_grad_partial_floats(C) / ramnet_pred_bwd_partial_floats() floats) and a second launch adds the
+ * rows to db / dw one after the other in workgroup order: the same bits on every launch.  Arguments otherwise as ramnet_bias_grad,
+ * ramnet_pred_sigmoid_bwd and ramnet_pred_linear_bwd.                                                                               */
+size_t ramnet_bias_grad_partial_floats(int C);
+int ramnet_bias_grad_ordered(const float *dy, const float *mask, float *db, size_t npix, int C, float *partial, void *stream);
+size_t ramnet_pred_bwd_partial_floats(void);
+int ramnet_pred_sigmoid_bwd_ordered(const float *x, int ldx, int C, const float *w, const float *y, const float *dy, float *dx, int lddx,
+                                    float *dw, float *db, size_t npix, float *partial, void *stream);
+int ramnet_pred_linear_bwd_ordered(const float *x, int ldx, int C, const float *w, const float *dz, float *dx, int lddx, float *dw, float *db,
+                                   size_t npix, float *partial, void *stream);
 /* ---- BatchNorm / InstanceNorm of `norm: "BN" | "IN"` layers: submodules.py:13-24, 29-30, 52-62, 82-94, 188-193, 203-210 ------
  * NHWC tensors [groups][npix][C] (row stride ld* >= C); groups = 1 for BatchNorm (npix = B*H*W), B for InstanceNorm (npix = H*W).
  * ramnet_norm_partial: part[((g * nslab + s) * C + c) * 2 + {0, 1}] = (sum a', sum a'*b) over the pixels p = s (mod nslab) ... of
@@ -568,6 +604,17 @@ int ramnet_voxelize_batch(const double *events, const long long *offsets, int n_
 int ramnet_normalize_nonzero_batch(float *grids, int n_grids, size_t n, double *scratch, void *stream);
 /* The statistics alone: stats[3 g ..] = (sum, sum of squares, nonzero count) of grid g (zeroed here); the grids are not modified.  */
 int ramnet_nonzero_stats_batch(const float *grids, int n_grids, size_t n, double *stats, void *stream);
+
+/* Ordered forms (additions to ABI 27): the workgroups' partial sums go to rows of `scratch` (ramnet_nonzero_stats_scratch_doubles(n_grids, n)
+ * doubles, any contents) and are added in workgroup order into stats [n_grids][3] (every entry written; no zero-fill, no atomics): the same
+ * bits on every launch.  ramnet_normalize_nonzero_ordered = one grid, any n, `grid` 16-byte aligned.                                  */
+int ramnet_voxelize_batch_sorted(const double *events, const long long *offsets, int n_grids, size_t max_events, int bins, int W, int H,
+                                 float *grids, void *stream);      /* ramnet_voxelize_batch on its sorted form ONLY (records sorted by cell, fixed-point
+                                  * accumulation: the same bits on every launch), for n_grids >= 1; RAMNET_E_UNSUPPORTED, nothing launched, where that form cannot run */
+size_t ramnet_nonzero_stats_scratch_doubles(int n_grids, size_t n);
+int ramnet_nonzero_stats_batch_ordered(const float *grids, int n_grids, size_t n, double *stats, double *scratch, void *stream);
+int ramnet_normalize_nonzero_batch_ordered(float *grids, int n_grids, size_t n, double *stats, double *scratch, void *stream);
+int ramnet_normalize_nonzero_ordered(float *grid, size_t n, double *stats, double *scratch, void *stream);
 
 /* ---- training augmentation: utils/data_augmentation.py:52-216 (RandomRotationFlip, then RandomCrop / CenterCrop) -----------------
  * G tensors [C][H][W] -> G windows of th x tw pixels in ONE launch.  src / dst: DEVICE tables of G device pointers (the tensors of a

@@ -200,6 +200,22 @@ _SIGS = {
                                       _fp, _fp, _fp, _fp, _fp]),
     "ramnet_least_squares_scale": (C.c_int, [_fp, _fp, C.c_int, C.c_size_t, C.c_float, C.c_float, _fp, _fp, _fp]),
     "ramnet_render_inputs": (C.c_int, [_fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    # ---- joins in a fixed order (additions to ABI 27): slab forms of the backward-weights families, ordered forms of the atomic joins
+    "ramnet_wgrad_slabs": (C.c_int, [C.POINTER(WgradDesc)]),
+    "ramnet_gemm_partial_floats": (C.c_size_t, [C.c_int] * 7),
+    "ramnet_gemm_ordered": (C.c_int, [_fp, _fp, _fp] + [C.c_int] * 8 + [C.c_long] * 3 + [_fp, _fp]),
+    "ramnet_gemm2_ordered": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int, _fp, _fp, _fp, C.c_int, C.c_long, C.c_long, C.c_long,
+                                       C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "ramnet_bias_grad_partial_floats": (C.c_size_t, [C.c_int]),
+    "ramnet_bias_grad_ordered": (C.c_int, [_fp, _fp, _fp, C.c_size_t, C.c_int, _fp, _fp]),
+    "ramnet_pred_bwd_partial_floats": (C.c_size_t, []),
+    "ramnet_pred_sigmoid_bwd_ordered": (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp, C.c_size_t, _fp, _fp]),
+    "ramnet_pred_linear_bwd_ordered": (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, _fp, _fp, C.c_size_t, _fp, _fp]),
+    "ramnet_voxelize_batch_sorted": (C.c_int, [_fp, _fp, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "ramnet_nonzero_stats_scratch_doubles": (C.c_size_t, [C.c_int, C.c_size_t]),
+    "ramnet_nonzero_stats_batch_ordered": (C.c_int, [_fp, C.c_int, C.c_size_t, _fp, _fp, _fp]),
+    "ramnet_normalize_nonzero_batch_ordered": (C.c_int, [_fp, C.c_int, C.c_size_t, _fp, _fp, _fp]),
+    "ramnet_normalize_nonzero_ordered": (C.c_int, [_fp, C.c_size_t, _fp, _fp, _fp]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -318,7 +318,13 @@ def voxelize_augmented(cat, off, max_count, num_bins, width, height, params, pid
     voxel.events_to_voxel_grids_packed(cat, off, max_count, num_bins, width, height, out=grids, normalize=False)
     if normalize:
         n = num_bins * int(height) * int(width)
-        H.check(H.lib().ramnet_nonzero_stats_batch(_p(grids), G, n, _p(stats), _st()), "ramnet_nonzero_stats_batch")
+        from . import ops
+        if ops.deterministic():         # the statistics joined in workgroup order
+            L = H.lib()
+            part = torch.empty(L.ramnet_nonzero_stats_scratch_doubles(G, n), device=grids.device, dtype=torch.float64)
+            H.check(L.ramnet_nonzero_stats_batch_ordered(_p(grids), G, n, _p(stats), _p(part), _st()), "ramnet_nonzero_stats_batch_ordered")
+        else:
+            H.check(H.lib().ramnet_nonzero_stats_batch(_p(grids), G, n, _p(stats), _st()), "ramnet_nonzero_stats_batch")
     return apply(grids, params, pidx=pidx, out=out, nhwc=nhwc, cpad=cpad, stats=stats if normalize else None)
 
 

@@ -772,8 +772,10 @@ __global__ void nonzero_stats_kernel(const float *__restrict__ g, size_t n, doub
     if (threadIdx.x < 3) atomicAdd(stats + threadIdx.x, red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
 }
 
-// batched forms: blockIdx.y = grid, stats[3*g ..]
-__global__ void nonzero_stats_batch_kernel(const float *__restrict__ grids, size_t n, double *stats) {
+// batched forms: blockIdx.y = grid, stats[3*g ..].  ORD (the *_ordered entry points): the workgroup stores its three sums to row
+// (grid, workgroup) of `stats` = part [n_grids][gridDim.x][3] instead, and nonzero_stats_join_kernel adds the rows in workgroup order.
+template <bool ORD>
+__device__ __forceinline__ void nonzero_stats_batch_body(const float *__restrict__ grids, size_t n, double *stats) {
     const float *g = grids + (size_t)blockIdx.y * n;
     double s1 = 0.0, s2 = 0.0, cnt = 0.0;
     for (size_t i = (blockIdx.x * (size_t)blockDim.x + threadIdx.x) * 4; i < n; i += (size_t)gridDim.x * blockDim.x * 4) {
@@ -792,8 +794,26 @@ __global__ void nonzero_stats_batch_kernel(const float *__restrict__ grids, size
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) red[0][wave] = s1, red[1][wave] = s2, red[2][wave] = cnt;
     __syncthreads();
-    if (threadIdx.x < 3)
-        atomicAdd(stats + 3 * blockIdx.y + threadIdx.x, red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
+    if (threadIdx.x < 3) {
+        const double t = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+        if (ORD) stats[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = t;
+        else atomicAdd(stats + 3 * blockIdx.y + threadIdx.x, t);
+    }
+}
+
+__global__ void nonzero_stats_batch_kernel(const float *__restrict__ grids, size_t n, double *stats) {
+    nonzero_stats_batch_body<false>(grids, n, stats);
+}
+__global__ void nonzero_stats_batch_ordered_kernel(const float *__restrict__ grids, size_t n, double *part) {
+    nonzero_stats_batch_body<true>(grids, n, part);
+}
+// stats[3 g + k] = part[g][0][k] + part[g][1][k] + ... one after the other (one workgroup of 64 threads per grid, threads 0-2 work)
+__global__ void nonzero_stats_join_kernel(const double *__restrict__ part, int rows, double *__restrict__ stats) {
+    if (threadIdx.x >= 3) return;
+    const double *p = part + (size_t)blockIdx.x * rows * 3 + threadIdx.x;
+    double t = 0.0;
+    for (int r = 0; r < rows; ++r) t += p[(size_t)r * 3];
+    stats[3 * blockIdx.x + threadIdx.x] = t;
 }
 
 __global__ void normalize_nonzero_batch_kernel(float *__restrict__ grids, size_t n, const double *__restrict__ stats) {
@@ -846,6 +866,7 @@ extern "C" int ramnet_si_loss_fwd(const float *pred, const float *target, size_t
         RAMNET_LAUNCH_CHECK();
         return 0;
     }
+    RAMNET_CHECK_ARG(!g_opt_ordered_only || !"ramnet_si_loss_fwd: no library scratch for the fixed-order join (stream capture, or no memory) and option ordered_only is set");
     RAMNET_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(double), st));
     hipLaunchKernelGGL(si_stats_kernel<false>, dim3(g), dim3(1024), 0, st, pred, target, n, weight, lambda, stats, loss);
     RAMNET_LAUNCH_CHECK();
@@ -864,6 +885,7 @@ extern "C" int ramnet_si_log_loss_fwd(const float *pred, const float *target, si
         RAMNET_LAUNCH_CHECK();
         return 0;
     }
+    RAMNET_CHECK_ARG(!g_opt_ordered_only || !"ramnet_si_log_loss_fwd: no library scratch for the fixed-order join (stream capture, or no memory) and option ordered_only is set");
     RAMNET_HIP(hipMemsetAsync(stats, 0, 4 * sizeof(double), st));
     hipLaunchKernelGGL(si_stats_kernel<true>, dim3(g), dim3(1024), 0, st, pred, target, n, 1.0f, lambda, stats, loss);
     RAMNET_LAUNCH_CHECK();
@@ -1023,11 +1045,13 @@ static unsigned char *voxel_id_scratch(hipStream_t st, size_t bytes) {
     return b.first;
 }
 
-static int launch_voxel_bands(const double *events, const long long *offsets, long long n_single, int n_grids, size_t max_events,
-                              int bins, int W, int H, float *grids, hipStream_t st) {
-    if (offsets != nullptr && max_events > 0 && max_events < (1u << 30) && W <= 32767 && H <= 32767 && g_opt_voxel_sorted) {      // sorted form
+// The sorted form alone (fixed-point accumulation of sorted records: the same bits whatever the arrival order): 0 = launched, -1 = this
+// shape or stream cannot take it (no room for a band in LDS, no library scratch inside a stream capture)
+static int launch_voxel_sorted(const double *events, const long long *offsets, int n_grids, size_t max_events, int bins, int W, int H,
+                               float *grids, hipStream_t st, int min_grids = 2) {      // (one list is faster on the atomic form: 27 against 33 us)
+    if (offsets != nullptr && max_events > 0 && max_events < (1u << 30) && W <= 32767 && H <= 32767) {
         const int nchunks = (int)((max_events + VS_CH - 1) / VS_CH);
-        const int rows = voxel_band_rows(2 * bins, W, H, n_grids, 2 * nchunks + 16, 2);    // (8-byte cells)
+        const int rows = voxel_band_rows(2 * bins, W, H, n_grids, 2 * nchunks + 16, min_grids);    // (8-byte cells)
         const int nbands = rows > 0 ? cdiv(H, rows) : 0;
         const long long rstride = (long long)nchunks * VS_CH;
         const size_t rec_bytes = (size_t)n_grids * rstride * sizeof(int4), tab_bytes = (size_t)n_grids * nchunks * (nbands + 1) * sizeof(int);
@@ -1044,6 +1068,15 @@ static int launch_voxel_bands(const double *events, const long long *offsets, lo
             RAMNET_LAUNCH_CHECK();
             return 0;
         }
+    }
+    return -1;
+}
+
+static int launch_voxel_bands(const double *events, const long long *offsets, long long n_single, int n_grids, size_t max_events,
+                              int bins, int W, int H, float *grids, hipStream_t st) {
+    if (g_opt_voxel_sorted) {
+        const int rc = launch_voxel_sorted(events, offsets, n_grids, max_events, bins, W, H, grids, st);
+        if (rc >= 0) return rc;
     }
     const long long stride = (long long)((max_events + 15) / 16 * 16);
     const int rows_ids = voxel_band_rows(bins, W, H, n_grids, 8192);
@@ -1103,6 +1136,24 @@ extern "C" int ramnet_voxelize_batch(const double *events, const long long *offs
     return 0;
 }
 
+// ramnet_voxelize_batch on the sorted form ONLY, for any number of lists: RAMNET_E_UNSUPPORTED (nothing launched) where that form cannot run
+extern "C" int ramnet_voxelize_batch_sorted(const double *events, const long long *offsets, int n_grids, size_t max_events, int bins, int W,
+                                            int H, float *grids, void *stream) {
+    RAMNET_CHECK_ARG(grids && offsets && n_grids > 0 && n_grids <= 65535 && bins > 0 && W > 0 && H > 0);
+    hipStream_t st = (hipStream_t)stream;
+    if (max_events == 0) {
+        RAMNET_HIP(hipMemsetAsync(grids, 0, (size_t)n_grids * bins * W * H * sizeof(float), st));
+        return 0;
+    }
+    RAMNET_CHECK_ARG(events != nullptr);
+    const int rc = launch_voxel_sorted(events, offsets, n_grids, max_events, bins, W, H, grids, st, 1);
+    if (rc < 0) {
+        set_error("ramnet_voxelize_batch_sorted: the sorted form cannot take this launch (%d x %d x %d grids, %zu events at most, or a stream capture without library scratch)", bins, H, W, max_events);
+        return RAMNET_E_UNSUPPORTED;
+    }
+    return rc;
+}
+
 extern "C" int ramnet_normalize_nonzero_batch(float *grids, int n_grids, size_t n, double *scratch, void *stream) {
     RAMNET_CHECK_ARG(grids && scratch && n > 0 && n % 4 == 0 && n_grids > 0 && n_grids <= 65535);
     RAMNET_CHECK_ARG(((uintptr_t)grids & 15) == 0);      // 16-byte loads and stores: with n % 4 == 0 every grid then starts aligned
@@ -1115,6 +1166,37 @@ extern "C" int ramnet_normalize_nonzero_batch(float *grids, int n_grids, size_t 
     hipLaunchKernelGGL(normalize_nonzero_batch_kernel, dim3(gx, n_grids), dim3(256), 0, st, grids, n, scratch);
     RAMNET_LAUNCH_CHECK();
     return 0;
+}
+
+// ---- the same with a fixed order of the sums (no atomics): partial rows per workgroup in `scratch`, added in workgroup order ----
+static int nonzero_stats_gx(int n_grids, size_t n) {
+    int gx = (int)((n / 4 + 255) / 256);
+    const int cap = (2048 * 4 + n_grids - 1) / n_grids;
+    if (gx > cap) gx = cap;
+    return gx < 1 ? 1 : gx;
+}
+extern "C" size_t ramnet_nonzero_stats_scratch_doubles(int n_grids, size_t n) {
+    return n_grids > 0 && n > 0 ? (size_t)3 * n_grids * nonzero_stats_gx(n_grids, n) : 0;
+}
+extern "C" int ramnet_nonzero_stats_batch_ordered(const float *grids, int n_grids, size_t n, double *stats, double *scratch, void *stream) {
+    RAMNET_CHECK_ARG(grids && stats && scratch && n > 0 && (n % 4 == 0 || n_grids == 1) && n_grids > 0 && n_grids <= 65535);
+    RAMNET_CHECK_ARG(((uintptr_t)grids & 15) == 0);      // (16-byte loads)
+    hipStream_t st = (hipStream_t)stream;
+    const int gx = nonzero_stats_gx(n_grids, n);
+    hipLaunchKernelGGL(nonzero_stats_batch_ordered_kernel, dim3(gx, n_grids), dim3(256), 0, st, grids, n, scratch);
+    hipLaunchKernelGGL(nonzero_stats_join_kernel, dim3(n_grids), dim3(64), 0, st, scratch, gx, stats);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int ramnet_normalize_nonzero_batch_ordered(float *grids, int n_grids, size_t n, double *stats, double *scratch, void *stream) {
+    const int rc = ramnet_nonzero_stats_batch_ordered(grids, n_grids, n, stats, scratch, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(normalize_nonzero_batch_kernel, dim3(nonzero_stats_gx(n_grids, n), n_grids), dim3(256), 0, (hipStream_t)stream, grids, n, stats);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int ramnet_normalize_nonzero_ordered(float *grid, size_t n, double *stats, double *scratch, void *stream) {
+    return ramnet_normalize_nonzero_batch_ordered(grid, 1, n, stats, scratch, stream);
 }
 
 // The statistics half of ramnet_normalize_nonzero_batch alone: the grids stay as they are, a consumer (ramnet_augment_batch) normalises

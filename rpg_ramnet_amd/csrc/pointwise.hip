@@ -225,6 +225,37 @@ __global__ void bias_grad_kernel(const float *__restrict__ dy, const float *__re
     }
 }
 
+// The same with a fixed order of the sums (ramnet_bias_grad_ordered): the workgroup's row groups meet in LDS in row order and leave
+// part[workgroup][C]; bias_grad_join_kernel adds the rows to db in workgroup order.
+__global__ void bias_grad_ordered_kernel(const float *__restrict__ dy, const float *__restrict__ mask, float *__restrict__ part, size_t npix, int C) {
+    __shared__ float red[256 * 4];
+    const int C4 = C / 4, q = threadIdx.x % C4, rows = blockDim.x / C4, r0 = threadIdx.x / C4;
+    float4 s = f4zero();
+    if (r0 < rows)
+        for (size_t pix = blockIdx.x * (size_t)rows + r0; pix < npix; pix += (size_t)gridDim.x * rows) {
+            float4 g = ld4(dy + pix * C + q * 4);
+            if (mask) {
+                const float4 m = ld4(mask + pix * C + q * 4);
+                g = make_float4(m.x > 0.f ? g.x : 0.f, m.y > 0.f ? g.y : 0.f, m.z > 0.f ? g.z : 0.f, m.w > 0.f ? g.w : 0.f);
+            }
+            s = f4add(s, g);
+        }
+    st4(red + threadIdx.x * 4, s);
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        float t = 0.f;
+        for (int r = 0; r < rows; ++r) t += red[(r * C4 + c / 4) * 4 + (c & 3)];
+        part[(size_t)blockIdx.x * C + c] = t;
+    }
+}
+__global__ void bias_grad_join_kernel(const float *__restrict__ part, int rows, float *__restrict__ db, int C) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    float t = db[c];
+    for (int r = 0; r < rows; ++r) t += part[(size_t)r * C + c];
+    db[c] = t;
+}
+
 // ------------------------------------------------------------------------------------------ prediction head
 // 8 lanes per pixel, each owns channel quads q, q+8, ...; butterfly over the 8 lanes.
 template <bool SIG>
@@ -246,9 +277,13 @@ __global__ void pred_sigmoid_fwd_kernel(const float *__restrict__ x, int ldx, in
     }
 }
 
-__global__ void pred_sigmoid_bwd_kernel(const float *__restrict__ x, int ldx, int C, const float *__restrict__ w,
-                                        const float *__restrict__ y, const float *__restrict__ dy, float *__restrict__ dx,
-                                        int lddx, float *__restrict__ dw, float *__restrict__ db, size_t npix) {
+// ORD (ramnet_pred_sigmoid_bwd_ordered / ramnet_pred_linear_bwd_ordered): dw = part [workgroups][PRED_BWD_LDP], the workgroup stores its C weight
+// sums and, at [128], its bias sum to its own row; pred_bwd_join_kernel adds the rows in workgroup order.
+constexpr int PRED_BWD_LDP = 132, PRED_BWD_WGS = 512;
+template <bool ORD>
+__device__ __forceinline__ void pred_sigmoid_bwd_body(const float *__restrict__ x, int ldx, int C, const float *__restrict__ w,
+                                                      const float *__restrict__ y, const float *__restrict__ dy, float *__restrict__ dx,
+                                                      int lddx, float *__restrict__ dw, float *__restrict__ db, size_t npix) {
     // thread (pixel slot, channel quad q = sub): fixed channel quads per thread -> private dw partials
     __shared__ float red[32 * 4 * 8 + 32];
     const int sub = threadIdx.x & 7, slot = threadIdx.x >> 3;
@@ -297,7 +332,10 @@ __global__ void pred_sigmoid_bwd_kernel(const float *__restrict__ x, int ldx, in
             const int c = k * 32 + threadIdx.x;
             float s = 0.f;
             for (int g = 0; g < 32; ++g) s += red[g * 32 + threadIdx.x];
-            if (c < C) atomicAdd(dw + c, s);
+            if (c < C) {
+                if (ORD) dw[(size_t)blockIdx.x * PRED_BWD_LDP + c] = s;
+                else atomicAdd(dw + c, s);
+            }
         }
     }
     __syncthreads();
@@ -306,8 +344,29 @@ __global__ void pred_sigmoid_bwd_kernel(const float *__restrict__ x, int ldx, in
     if (threadIdx.x == 0) {
         float s = 0.f;
         for (int g = 0; g < 32; ++g) s += red[g];
-        if (db) atomicAdd(db, s);
+        if (ORD) dw[(size_t)blockIdx.x * PRED_BWD_LDP + 128] = s;
+        else if (db) atomicAdd(db, s);
     }
+}
+
+__global__ void pred_sigmoid_bwd_kernel(const float *__restrict__ x, int ldx, int C, const float *__restrict__ w,
+                                        const float *__restrict__ y, const float *__restrict__ dy, float *__restrict__ dx,
+                                        int lddx, float *__restrict__ dw, float *__restrict__ db, size_t npix) {
+    pred_sigmoid_bwd_body<false>(x, ldx, C, w, y, dy, dx, lddx, dw, db, npix);
+}
+__global__ void pred_sigmoid_bwd_ordered_kernel(const float *__restrict__ x, int ldx, int C, const float *__restrict__ w,
+                                                const float *__restrict__ y, const float *__restrict__ dy, float *__restrict__ dx,
+                                                int lddx, float *__restrict__ part, size_t npix) {
+    pred_sigmoid_bwd_body<true>(x, ldx, C, w, y, dy, dx, lddx, part, nullptr, npix);
+}
+// dw[c] += part[0][c] + part[1][c] + ..., db += part[0][128] + ...: one after the other, in workgroup order (one workgroup of 256 threads)
+__global__ void pred_bwd_join_kernel(const float *__restrict__ part, int rows, int C, float *__restrict__ dw, float *__restrict__ db) {
+    const int c = threadIdx.x;
+    float *dst = c < C ? dw + c : (c == 128 && db != nullptr) ? db : nullptr;
+    if (dst == nullptr) return;
+    float t = *dst;
+    for (int r = 0; r < rows; ++r) t += part[(size_t)r * PRED_BWD_LDP + c];
+    *dst = t;
 }
 
 // ------------------------------------------------------------------------------------------ prediction head + scale-invariant loss
@@ -997,7 +1056,7 @@ extern "C" int ramnet_abi_version(void) { return RAMNET_ABI_VERSION; }
 
 // Process-wide A/B options (tests and tuning runs; the environment variables they replace are gone since round 4)
 namespace ramnet {
-int g_opt_voxel_sorted = 1, g_opt_fold_pair = 1, g_opt_wgrad_blocks = 512, g_opt_wgrad_wino_blocks = 384, g_opt_wino_ksplit = 1, g_opt_wgrad_wino_nf = 1, g_opt_pred_si_cap = 256, g_opt_pred_si_bwd_cap = 1024;
+int g_opt_voxel_sorted = 1, g_opt_fold_pair = 1, g_opt_wgrad_blocks = 512, g_opt_wgrad_wino_blocks = 384, g_opt_wino_ksplit = 1, g_opt_wgrad_wino_nf = 1, g_opt_pred_si_cap = 256, g_opt_pred_si_bwd_cap = 1024, g_opt_ordered_only = 0;
 }
 extern "C" int ramnet_set_option(const char *name, int value) {
     RAMNET_CHECK_ARG(name != nullptr);
@@ -1009,6 +1068,7 @@ extern "C" int ramnet_set_option(const char *name, int value) {
     else if (!strcmp(name, "wgrad_wino_blocks")) { RAMNET_CHECK_ARG(value >= 1 && value <= 384); ramnet::g_opt_wgrad_wino_blocks = value; }
     else if (!strcmp(name, "pred_si_bwd_cap")) { RAMNET_CHECK_ARG(value >= 8 && value <= 65536); ramnet::g_opt_pred_si_bwd_cap = value; }
     else if (!strcmp(name, "pred_si_cap")) { RAMNET_CHECK_ARG(value >= 8 && value <= 65536); ramnet::g_opt_pred_si_cap = value; }
+    else if (!strcmp(name, "ordered_only")) ramnet::g_opt_ordered_only = value != 0;
     else RAMNET_CHECK_ARG(!"ramnet_set_option: unknown option");
     return 0;
 }
@@ -1022,6 +1082,7 @@ extern "C" int ramnet_get_option(const char *name) {
     if (!strcmp(name, "wgrad_wino_nf")) return ramnet::g_opt_wgrad_wino_nf;
     if (!strcmp(name, "pred_si_bwd_cap")) return ramnet::g_opt_pred_si_bwd_cap;
     if (!strcmp(name, "pred_si_cap")) return ramnet::g_opt_pred_si_cap;
+    if (!strcmp(name, "ordered_only")) return ramnet::g_opt_ordered_only;
     return -1;
 }
 
@@ -1136,6 +1197,15 @@ extern "C" int ramnet_bias_grad(const float *dy, const float *mask, float *db, s
     return 0;
 }
 
+extern "C" size_t ramnet_bias_grad_partial_floats(int C) { return C > 0 ? (size_t)256 * C : 0; }
+extern "C" int ramnet_bias_grad_ordered(const float *dy, const float *mask, float *db, size_t npix, int C, float *partial, void *stream) {
+    RAMNET_CHECK_ARG(dy && db && partial && C > 0 && C % 4 == 0 && C <= 1024);
+    hipLaunchKernelGGL(bias_grad_ordered_kernel, dim3(256), dim3(256), 0, (hipStream_t)stream, dy, mask, partial, npix, C);
+    hipLaunchKernelGGL(bias_grad_join_kernel, dim3((C + 255) / 256), dim3(256), 0, (hipStream_t)stream, partial, 256, db, C);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int ramnet_concat2(const float *a, int lda, int Ca, const float *b, int ldb, int Cb, float *y, size_t npix, void *stream) {
     RAMNET_CHECK_ARG(a && b && y && Ca > 0 && Cb > 0 && Ca % 4 == 0 && Cb % 4 == 0 && lda % 4 == 0 && ldb % 4 == 0 && lda >= Ca && ldb >= Cb);
     hipLaunchKernelGGL(concat2_kernel, dim3(grid_for(npix * ((Ca + Cb) / 4))), dim3(256), 0, (hipStream_t)stream, a, lda, Ca, b, ldb, Cb, y, npix);
@@ -1178,6 +1248,28 @@ extern "C" int ramnet_pred_sigmoid_bwd(const float *x, int ldx, int C, const flo
                                        int lddx, float *dw, float *db, size_t npix, void *stream) {
     RAMNET_CHECK_ARG(x && w && y && dy && dw && db && C > 0 && C % 4 == 0 && C <= 128 && ldx % 4 == 0);
     return pred_bwd(x, ldx, C, w, y, dy, dx, lddx, dw, db, npix, stream);
+}
+static int pred_bwd_ordered(const float *x, int ldx, int C, const float *w, const float *y, const float *dy, float *dx, int lddx, float *dw, float *db,
+                            size_t npix, float *partial, void *stream) {
+    RAMNET_CHECK_ARG(partial && ldx >= C);
+    if (dx) RAMNET_CHECK_ARG(lddx % 4 == 0 && lddx >= C);
+    int g = grid_for(npix * 8);
+    if (g > PRED_BWD_WGS) g = PRED_BWD_WGS;
+    hipLaunchKernelGGL(pred_sigmoid_bwd_ordered_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, x, ldx, C, w, y, dy, dx, lddx, partial, npix);
+    hipLaunchKernelGGL(pred_bwd_join_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, g, C, dw, db);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" size_t ramnet_pred_bwd_partial_floats(void) { return (size_t)PRED_BWD_WGS * PRED_BWD_LDP; }
+extern "C" int ramnet_pred_sigmoid_bwd_ordered(const float *x, int ldx, int C, const float *w, const float *y, const float *dy, float *dx,
+                                               int lddx, float *dw, float *db, size_t npix, float *partial, void *stream) {
+    RAMNET_CHECK_ARG(x && w && y && dy && dw && db && C > 0 && C % 4 == 0 && C <= 128 && ldx % 4 == 0);
+    return pred_bwd_ordered(x, ldx, C, w, y, dy, dx, lddx, dw, db, npix, partial, stream);
+}
+extern "C" int ramnet_pred_linear_bwd_ordered(const float *x, int ldx, int C, const float *w, const float *dz, float *dx, int lddx, float *dw,
+                                              float *db, size_t npix, float *partial, void *stream) {
+    RAMNET_CHECK_ARG(x && w && dz && dw && C > 0 && C % 4 == 0 && C <= 128 && ldx % 4 == 0);
+    return pred_bwd_ordered(x, ldx, C, w, nullptr, dz, dx, lddx, dw, db, npix, partial, stream);
 }
 static int pred_si_grid(size_t seg_pix, int nseg) {
     // Workgroups per segment: at most "pred_si_cap" (256 = one per CU) over all segments: 1.41 M pixels x 32 channels take 32.2 us with 256 or 512

@@ -546,6 +546,7 @@ class GraphedTrainStep:
 
         # which launches and folds the capture holds follows the parameters' requires_grad flags (partial training): baked in here
         self.flags = tuple(p.requires_grad for p in model.parameters())
+        self.deterministic = ops.deterministic()      # ... and so does the mode: slab launches and ordered joins, or the atomic ones
         _warm(run, warmup)
         torch.cuda.empty_cache()
         ops.invalidate_packs()            # every weight pack is re-run — and therefore recorded — inside the capture
@@ -577,6 +578,9 @@ class GraphedTrainStep:
             changed = [n for (n, p), f in zip(self.model.named_parameters(), self.flags) if p.requires_grad != f]
             raise RuntimeError("GraphedTrainStep: requires_grad of %s changed since the capture; the graph holds the launches of the "
                                "captured flags — build a new GraphedTrainStep" % ", ".join(changed[:4] + (["..."] if len(changed) > 4 else [])))
+        if ops.deterministic() != self.deterministic:
+            raise RuntimeError("GraphedTrainStep: captured with set_deterministic(%s), replayed under set_deterministic(%s); the graph holds "
+                               "the launches of the captured mode — build a new GraphedTrainStep" % (self.deterministic, ops.deterministic()))
         self._attach()
         self.graph.replay()
         return self.total, self.reported

@@ -27,6 +27,8 @@ def depth_metrics(prediction, target, clip_distance, reg_factor, cutoff=float("i
     """prediction / target: normalised log-depth tensors (any shape, same numel).  Pixels with metric target depth
     `nan_to_num(t) < cutoff` form the mask (evaluation.py:367); NaN targets are skipped by the means (metric.py) but stay in
     the denominator of the delta thresholds (`np.mean(ratio <= ...)`, evaluation.py:224-226)."""
+    from . import ops
+    ops.not_deterministic("metrics.depth_metrics (the batched tables, metrics.batch_metrics and EvalTable, are ordered)")
     p = prediction.detach().float().contiguous()
     t = target.detach().to(p.device).float().contiguous()
     assert p.numel() == t.numel()

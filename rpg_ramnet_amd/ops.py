@@ -42,7 +42,41 @@ def set_wgrad_slabs(on):
     """Winograd backward-weights: tile splits join per-split slabs of the workspace by plain read-modify-write (default: no atomics,
     bit-reproducible gradients) or meet in slab 0 by atomic adds (A/B runs)."""
     global _WGRAD_SLABS
+    if not on and _DETERMINISTIC:
+        raise RuntimeError("set_wgrad_slabs(False) has no deterministic form: the atomic join of the backward-weights tile splits "
+                           "contradicts set_deterministic(True)")
     _WGRAD_SLABS = bool(on)
+
+
+# Deterministic mode: every floating-point join of the training step runs in a fixed order — the same loss, gradients and (with a deterministic
+# optimiser) weights, bit for bit, on the same machine, device, world size and library build.  The backward-weights launches of EVERY family
+# then own per-split slabs (ramnet_wgrad_desc.dw_slabs, folded by ramnet_reduce_slabs as the 3x3 families' always were), the border-GEMM,
+# bias and prediction-layer gradients and the normalisation statistics go through the library's *_ordered entry points, the voxeliser is
+# the sorted one; an operation without an ordered form raises RuntimeError naming itself (not_deterministic) instead of running.
+_DETERMINISTIC = False
+
+
+def set_deterministic(on):
+    """Off by default: every launch, its order, its kernel and its descriptor are then what they are without this switch."""
+    global _DETERMINISTIC
+    if on and not _WGRAD_SLABS:
+        raise RuntimeError("set_deterministic(True) needs the slab join of the backward-weights launches: set_wgrad_slabs(True) first")
+    if on and not _GRAD_LOSS_BATCHED:
+        raise RuntimeError("set_deterministic(True) needs the batched multi-scale gradient loss: set_grad_loss_batched(True) first")
+    _DETERMINISTIC = bool(on)
+    # the library refuses, instead of taking, the zero-fill + atomics form of ramnet_si_loss_fwd / ramnet_si_log_loss_fwd when the fixed-order
+    # one-launch form has no scratch (a stream capture, a failed allocation)
+    H.check(H.lib().ramnet_set_option(b"ordered_only", int(_DETERMINISTIC)), "set_option")
+
+
+def deterministic():
+    return _DETERMINISTIC
+
+
+def not_deterministic(what):
+    """Called by an operation that has no ordered form, before it launches anything."""
+    if _DETERMINISTIC:
+        raise RuntimeError("%s has no deterministic form: it joins floating-point partial sums by atomic adds (set_deterministic(True) is on)" % what)
 
 
 
@@ -503,11 +537,46 @@ _FOLD_LAYOUTS = {
 }
 
 
-def _stamp_layout(dw, kind, slabs, head_cin=0):
-    """Write the layout of a pass onto its workspace tensor (the protocol stated at wgrad_launch); ConvParam.grad_ws is the one caller."""
+def _stamp_layout(dw, kind, slabs, head_cin=0, det_slabs=0):
+    """Write the layout of a pass onto its workspace tensor (the protocol stated at wgrad_launch); ConvParam.grad_ws is the one caller.
+    det_slabs (deterministic mode): slabs of a workspace of the direct / head / fold kinds, which have none otherwise."""
     dw.wino, dw.wino6, dw.wg_dsplit = kind == "wino", kind == "wino6", kind == "dsplit"
     dw.slabs, dw.head_cin = slabs, head_cin
+    dw.det_slabs = det_slabs
     return dw
+
+
+def _det_slabs(dw):
+    """Slabs of a direct / head / fold workspace stamped in deterministic mode (0: the one-slab atomic form)."""
+    return getattr(dw, "det_slabs", 0)
+
+
+_DET_SLAB_QUERIES = {}
+
+
+def _det_slab_query(algo, Cin, Cout, k):
+    """Most slabs a backward-weights launch of a layer of this algorithm and these channels uses at any map size: ramnet_wgrad_slabs of a
+    map large enough that the tile count limits nothing (what ConvParam allocates in deterministic mode).  The probe's shape may pick
+    another kernel shape than a real launch does (the direct kernel's 64-channel `wide` form needs 2048 tiles): that is safe only because
+    every launcher clamps its splits to the dw_slabs it is handed — a launch uses what its own shape gives, never more than the stamp.
+    The answer depends on the arguments alone: asked once per (algorithm, channels, taps)."""
+    key = (algo, Cin, Cout, k, H.lib().ramnet_get_option(b"wgrad_blocks"))
+    if key not in _DET_SLAB_QUERIES:
+        _DET_SLAB_QUERIES[key] = _det_slab_query_once(algo, Cin, Cout, k)
+    return _DET_SLAB_QUERIES[key]
+
+
+def _det_slab_query_once(algo, Cin, Cout, k):
+    d = H.WgradDesc()
+    d.algo, d.in_mode, d.stride, d.B, d.C0, d.Cout = algo, H.IN_PLAIN, 1, 64, Cin, Cout
+    if algo in (H.ALGO_WINOGRAD24, H.ALGO_WINOGRAD24_2X3):
+        d.Ho, d.Wo, d.Hin, d.Win, d.HoG, d.WoG, d.ntaps = 256, 256, 260, 260, 512, 512, 16
+    else:
+        d.Ho = d.Wo = d.Hin = d.Win = 512
+        d.ntaps = k * k
+        for t in range(k * k):
+            d.dy[t], d.dx[t] = t // k - k // 2, t % k - k // 2
+    return max(1, H.lib().ramnet_wgrad_slabs(C.byref(d)))
 
 
 def _layout_of(dw):
@@ -534,6 +603,8 @@ def _wgrad_desc_build(x0, taps, dout, dw, Cout, stride, x1, xm, xm_off, in_mode,
     kind, slabs = _layout_of(dw)
     d.algo = _LAYOUTS[kind][3]
     d.dw_slabs = slabs if (kind != "direct" and _WGRAD_SLABS) else 0     # per-split slabs (read-modify-write joins)
+    if _det_slabs(dw) and _WGRAD_SLABS and (kind == "direct" or wino24):    # deterministic mode: the direct, head and fold kinds as well
+        d.dw_slabs = _det_slabs(dw)
     if wino24:          # folded upsample-conv in the Winograd F(2x2,4x4) domain: dw = [4][25][C0][Cout]; "2x3": F(2x3,4x4), dw = [4][30][C0][Cout]
         d.algo = H.ALGO_WINOGRAD24_2X3 if wino24 == "2x3" else H.ALGO_WINOGRAD24
     hc = getattr(dw, "head_cin", 0)
@@ -553,7 +624,7 @@ def wgrad_launch(x0, taps, dout, dw, Cout, *, stride=1, x1=None, xm=None, xm_off
     # ConvParam.grad_ws is the one writer in the package (_stamp_layout) and _layout_of the one reader of the first four; bench.py reads
     # them for its FLOP / byte accounting, tests and tools stamp them on plain tensors to pick an algorithm: the names and defaults stay.
     # (descriptor cache as for _conv_desc: the template holds everything but the six pointers)
-    key = (id(taps), id(dw), _layout_of(dw), getattr(dw, "head_cin", 0), Cout, stride,
+    key = (id(taps), id(dw), _layout_of(dw), _det_slabs(dw), getattr(dw, "head_cin", 0), Cout, stride,
            in_mode, C0, C1, Hin, Win, Ho, Wo, gview, dw_off, wino24, xm_off, tuple(x0.shape), x0.stride(2), _sd(x1), _sd(xm), dout.shape[1],
            dout.shape[2], dout.stride(2), _sd(gmask), _WGRAD_SLABS, _HEAD, x0.device.index)
     tmpl = _WDESC_CACHE.get(key) if _DESC_CACHE_ON else None
@@ -957,6 +1028,8 @@ class ConvParam:
         self._ws = self._bws = self._slabs = None
         self._ws_fold = None             # (dW4 [64][CinWs][Cout], dWrows, dWcols) of the folded upsample-conv backward-weights
         self._ws_fold24 = self._ws_fold23 = None
+        self._ws_fold_det = None         # deterministic mode: the direct parity launches' slabs [4 classes][S][16][CinWs][Cout]
+        self._part = {}                  # deterministic mode: partial buffers of the ordered joins, by name
         self._fold_used = self._fold24_used = self._fold23_used = self._ws_used = False
         self._dirty = False
         self._defer = []                 # queued backward-weights launches of a recurrent cell (_wgrad_cell)
@@ -1086,6 +1159,21 @@ class ConvParam:
             self._bias, self._vbias = torch.cat([b.detach() for b in self.biases]).contiguous(), v
         return self._bias
 
+    def det_partial(self, name, n, dtype=torch.float32):
+        """A buffer of at least n elements for the partial sums of an ordered join of this layer (deterministic mode); its launches are
+        ordered on one stream, as the layer's gradient workspaces'."""
+        buf = self._part.get(name)
+        if buf is None or buf.numel() < n:
+            buf = self._part[name] = torch.empty(max(n, 1), device=self.weights[0].device, dtype=dtype)
+        return buf
+
+    def _bias_slabs(self, ns):
+        """The bias workspace with room for ns slabs [ns][Cout] (zero between passes: grown by reallocation)."""
+        if self._bws is None or self._bws.numel() < ns * self.Cout:
+            self._bws = torch.zeros(ns * self.Cout, device=self.weights[0].device)
+        self._bws_slabs = max(getattr(self, "_bws_slabs", 1), ns)
+        return self._bws
+
     def _slab_floats(self, kind):
         f = _LAYOUTS[kind][0]
         return getattr(H.lib(), f)(self.CinWs, self.Cout) if isinstance(f, str) else (f or self.k * self.k) * self.CinWs * self.Cout
@@ -1122,13 +1210,18 @@ class ConvParam:
         if not self._dirty:     # every launch of the pass accumulates into the same layout
             kind, ns = self._choose_layout(wino_ok)
             n = ns * self._slab_floats(kind) if kind == "dsplit" else 0
+            det = 0
+            if _DETERMINISTIC and kind == "direct":         # the direct (and head) launches own slabs as well: [S][k x k][CinWs][Cout]
+                det = _det_slab_query(H.ALGO_DIRECT, self.CinWs, self.Cout, self.k)
+                n, ns = det * self._slab_floats(kind), det
             if self._ws.numel() < n or (n and self._bws.numel() < ns * self.Cout):
                 dev = self._ws.device                       # (between passes the workspaces hold zeros: grow them)
                 self._ws = torch.zeros(max(n, self._ws.numel()), device=dev)
                 self._bws = torch.zeros(max(ns, self._slabs) * self.Cout, device=dev)
             # head layers: the launch may run the head kernel (same [tap][CinWs][Cout] layout as the direct kernel)
-            _stamp_layout(self._ws, kind, ns, self.Cin if (self.k == 5 and self.gates == 1 and len(self.weights) == 1
-                                                          and H.lib().ramnet_head_supported(self.Cin, self.Cout)) else 0)
+            _stamp_layout(self._ws, kind, self._choose_layout(wino_ok)[1] if det else ns,
+                          self.Cin if (self.k == 5 and self.gates == 1 and len(self.weights) == 1
+                                       and H.lib().ramnet_head_supported(self.Cin, self.Cout)) else 0, det_slabs=det)
         _Engine.mark(self)
         self._ws_used = True
         return self._ws, self._bws
@@ -1140,6 +1233,8 @@ class ConvParam:
         dev = self.weights[0].device
         if self._bws is None:
             self._bws = torch.zeros(self.Cout, device=dev)
+        if _DETERMINISTIC:              # room for the slabs of whichever backward-weights form the launch takes
+            self._bias_slabs(max(_det_slab_query(H.ALGO_DIRECT, self.CinWs, self.Cout, 4), self._fold_det_slabs()))
         if self._ws_fold is None:
             self._ws_fold = (torch.zeros(64 * self.CinWs * self.Cout, device=dev),
                              torch.zeros(2, 5 * self.Cin, 2 * self.Cout, device=dev),
@@ -1148,13 +1243,32 @@ class ConvParam:
         self._fold_used = True
         return self._ws_fold + (self._bws,)
 
+    def _fold_det_slabs(self):
+        ok = self.Cin == self.CinWs and ((self.Cin % 32 == 0 and self.Cout % 64 == 0) or (self.Cin % 64 == 0 and self.Cout % 32 == 0))
+        return _det_slab_query(H.ALGO_WINOGRAD24, self.Cin, self.Cout, 4) if ok else 1
+
+    def grad_ws_fold_det(self):
+        """Deterministic mode, direct parity launches: [4 classes][S][16 taps][CinWs][Cout] — class (py, px) launches into its own S slabs
+        at offset class * S * 16 * CinWs * Cout; _finalize_fold joins them and copies slab 0 of every class into the [64][CinWs][Cout]
+        workspace the fold reads."""
+        S = _det_slab_query(H.ALGO_DIRECT, self.CinWs, self.Cout, 4)
+        n = 4 * S * 16 * self.CinWs * self.Cout
+        if self._ws_fold_det is None or self._ws_fold_det.numel() < n:
+            self._ws_fold_det = torch.zeros(n, device=self.weights[0].device)
+        _stamp_layout(self._ws_fold_det, "direct", 1, 0, det_slabs=S)
+        self._fold_det_used = True
+        return self._ws_fold_det, S
+
     def grad_ws_fold24(self, kind="fold24"):
         """dU [4 parity classes][25 positions][Cin][Cout]: Winograd-domain gradient of the four 4x4 parity filters — or, kind "fold23", the
         [4][30][Cin][Cout] of the F(2x3,4x4) launches (_FOLD_LAYOUTS): the workspace of the variant the launch takes."""
         f23 = kind == "fold23"
         ws = self._ws_fold23 if f23 else self._ws_fold24
-        if ws is None:
-            ws = torch.zeros(4 * _FOLD_LAYOUTS[kind][0] * self.CinWs * self.Cout, device=self.weights[0].device)
+        det = self._fold_det_slabs() if _DETERMINISTIC else 0         # deterministic mode: one slab per tile split [S][4][positions][CinWs][Cout]
+        one = 4 * _FOLD_LAYOUTS[kind][0] * self.CinWs * self.Cout
+        if ws is None or ws.numel() < max(det, 1) * one:
+            ws = torch.zeros(max(det, 1) * one, device=self.weights[0].device)
+        ws.det_slabs = det
         if f23:
             self._ws_fold23, self._fold23_used = ws, True
         else:
@@ -1168,6 +1282,20 @@ class ConvParam:
         w4, wr, wc = self._ws_fold
         dU = self._ws_fold24 if self._fold24_used else None
         dU3 = self._ws_fold23 if self._fold23_used else None       # F(2x3,4x4) launches of the pass: + G^T dU3 Gc
+        L = H.lib()
+        for t, kind in ((dU, "fold24"), (dU3, "fold23")):           # deterministic mode: the tile splits' slabs -> slab 0, in slab order
+            if t is not None and _det_slabs(t) > 1:
+                H.check(L.ramnet_reduce_slabs(_p(t), _det_slabs(t), 4 * _FOLD_LAYOUTS[kind][0] * self.CinWs * self.Cout, _st()), "ramnet_reduce_slabs")
+        if getattr(self, "_fold_det_used", False):                  # ... and the direct parity launches' slabs, class by class, into w4
+            wd, S = self._ws_fold_det, _det_slabs(self._ws_fold_det)
+            one = 16 * self.CinWs * self.Cout
+            for cls in range(4):
+                H.check(L.ramnet_reduce_slabs(_p(wd, cls * S * one), S, one, _st()), "ramnet_reduce_slabs")
+            w4.view(4, one).copy_(wd.view(4, S, one)[:, 0])
+            for cls in range(4):            # (slab 0 of every class: ramnet_reduce_slabs left slabs 1.. at zero)
+                _zero_later(wd[cls * S * one:cls * S * one + one])
+            self._fold_det_used = False
+        self._join_bias()
         if self.weights[0].requires_grad:
             g = ensure_grad(self.weights[0])
             if dU3 is not None:
@@ -1179,15 +1307,17 @@ class ConvParam:
         else:       # frozen weight beside a trainable bias (they share the launches): nothing to fold, the workspaces start the next pass at zero
             for t in (w4, dU, dU3, wr, wc):
                 if t is not None:
-                    _zero_later(t)
+                    _zero_later(t[:t.numel() // max(_det_slabs(t), 1)] if _det_slabs(t) > 1 else t)      # (joined: slabs 1.. are zero)
         self._fold24_used = self._fold23_used = False
         self._fold_used = False
 
     def discard(self):
         """Zero every gradient workspace without folding it (aborted backward pass)."""
-        for t in (self._ws, self._bws, self._ws_fold24, self._ws_fold23) + tuple(self._ws_fold or ()):
+        for t in (self._ws, self._bws, self._ws_fold24, self._ws_fold23, self._ws_fold_det) + tuple(self._ws_fold or ()):
             if t is not None:
                 t.zero_()
+        self._fold_det_used = False
+        self._bws_slabs = 1
         self._dirty = self._ws_used = self._fold_used = self._fold24_used = self._fold23_used = False
 
     def _join_slabs(self):
@@ -1196,12 +1326,23 @@ class ConvParam:
         if ns > 1 and kind != "direct":
             H.check(H.lib().ramnet_reduce_slabs(_p(self._ws), ns, self._slab_floats(kind), _st()), "ramnet_reduce_slabs")
             H.check(H.lib().ramnet_reduce_slabs(_p(self._bws), ns, self.Cout, _st()), "ramnet_reduce_slabs")
+        elif kind == "direct" and _det_slabs(self._ws) > 1:         # deterministic mode: the direct / head launches' slabs, the same way
+            ns = _det_slabs(self._ws)
+            H.check(H.lib().ramnet_reduce_slabs(_p(self._ws), ns, self._slab_floats(kind), _st()), "ramnet_reduce_slabs")
+            H.check(H.lib().ramnet_reduce_slabs(_p(self._bws), ns, self.Cout, _st()), "ramnet_reduce_slabs")
+
+    def _join_bias(self):
+        """Deterministic mode, folded decoders: the bias slabs [S][Cout] of the pass -> slab 0 (the bias workspace has one slab otherwise)."""
+        ns = getattr(self, "_bws_slabs", 1)
+        if ns > 1 and self._bws is not None:
+            H.check(H.lib().ramnet_reduce_slabs(_p(self._bws), ns, self.Cout, _st()), "ramnet_reduce_slabs")
+        self._bws_slabs = 1
 
     def _zero_ws(self):
         """Zero what the pass used of the gradient workspace for the next one: slab 0 only where the slabs were joined
         (ramnet_reduce_slabs leaves slabs 1.. zeroed), not the whole buffer sized for the largest layout."""
         kind, ns = _layout_of(self._ws)
-        n, ns = self._slab_floats(kind), (1 if kind == "direct" else max(ns, 1))
+        n, ns = self._slab_floats(kind), (max(_det_slabs(self._ws), 1) if kind == "direct" else max(ns, 1))
         joined = ns > 1
         _zero_later(self._ws[:n if joined else min(self._ws.numel(), n * ns)])
         _zero_later(self._bws[:self.Cout if joined else self._bws.numel()])
@@ -1368,17 +1509,30 @@ class CropParameters:
         return y[..., self.iy0:self.iy1, self.ix0:self.ix1]
 
 
-def gemm(a, b, out, trans_a=False, accumulate=False):
+def _gemm_partial(n, device, owner):
+    """Partial buffer of an ordered accumulating GEMM: the owner layer's (its launches are ordered on one stream), else a fresh one."""
+    if n == 0:
+        return None
+    return owner.det_partial("gemm", n) if owner is not None else torch.empty(n, device=device)
+
+
+def gemm(a, b, out, trans_a=False, accumulate=False, owner=None):
     """out[i] (=, +=) a[i] @ b[i]  (trans_a: a[i]^T @ b[i]) for the entries i of a batch, in ONE launch of the library's own MFMA
     kernel (ramnet_gemm); a, b, out: [batch][rows][cols] row-major.  Plain products are bit-reproducible (one wave per 32 x 32
-    block, no atomics); accumulate=True splits the reduction and joins by atomics (backward pass)."""
+    block, no atomics); accumulate=True splits the reduction and joins by atomics (backward pass) — in deterministic mode through
+    ramnet_gemm_ordered and a partial buffer (owner: the ConvParam that keeps it), in slice order."""
     nb, M, N = out.shape
     K = a.shape[1] if trans_a else a.shape[2]
+    if accumulate and _DETERMINISTIC:
+        part = _gemm_partial(H.lib().ramnet_gemm_partial_floats(M, N, K, nb, 0, 0, 0), out.device, owner)
+        H.check(H.lib().ramnet_gemm_ordered(_p(a), _p(b), _p(out), M, N, K, a.stride(1), b.stride(1), out.stride(1), int(trans_a),
+                                            nb, a.stride(0), b.stride(0), out.stride(0), _p(part), _st()), "ramnet_gemm_ordered")
+        return
     H.check(H.lib().ramnet_gemm(_p(a), _p(b), _p(out), M, N, K, a.stride(1), b.stride(1), out.stride(1), int(trans_a), int(accumulate),
                                 nb, a.stride(0), b.stride(0), out.stride(0), _st()), "ramnet_gemm")
 
 
-def gemm2(a1, b1, out1, a2, b2, out2, trans_a=False, accumulate=False):
+def gemm2(a1, b1, out1, a2, b2, out2, trans_a=False, accumulate=False, owner=None):
     """gemm(a1, b1, out1) and gemm(a2, b2, out2) in ONE launch (ramnet_gemm2): the row and the column border of a decoder layer — same
     N, leading dimensions and mode; the two problems differ in M (forward, backward-data) or in the reduction length (weight gradient)."""
     nb1, M1, N = out1.shape
@@ -1386,6 +1540,12 @@ def gemm2(a1, b1, out1, a2, b2, out2, trans_a=False, accumulate=False):
     K1 = a1.shape[1] if trans_a else a1.shape[2]
     K2 = a2.shape[1] if trans_a else a2.shape[2]
     assert N == N2 and a1.stride(1) == a2.stride(1) and b1.stride(1) == b2.stride(1) and out1.stride(1) == out2.stride(1)
+    if accumulate and _DETERMINISTIC:
+        part = _gemm_partial(H.lib().ramnet_gemm_partial_floats(M1, N, K1, nb1, M2, K2, nb2), out1.device, owner)
+        H.check(H.lib().ramnet_gemm2_ordered(_p(a1), _p(b1), _p(out1), M1, a1.stride(0), b1.stride(0), out1.stride(0), nb1, _p(a2), _p(b2), _p(out2),
+                                             M2, a2.stride(0), b2.stride(0), out2.stride(0), nb2, N, K1, K2, a1.stride(1), b1.stride(1),
+                                             out1.stride(1), int(trans_a), _p(part), _st()), "ramnet_gemm2_ordered")
+        return
     H.check(H.lib().ramnet_gemm2(_p(a1), _p(b1), _p(out1), M1, a1.stride(0), b1.stride(0), out1.stride(0), nb1, _p(a2), _p(b2), _p(out2), M2,
                                  a2.stride(0), b2.stride(0), out2.stride(0), nb2, N, K1, K2, a1.stride(1), b1.stride(1), out1.stride(1),
                                  int(trans_a), int(accumulate), _st()), "ramnet_gemm2")
@@ -1527,14 +1687,16 @@ def _folded_upsample_wgrad(x, skip, dy, y, cp, xpad=None):
             wgrad_launch(xpad, Taps.get("fold", 4, 0, 0, 0), dy, cp.grad_ws_fold24(kind), cp.Cout, gmask=y, dbias=bws, Ho=Hh, Wo=W,
                          gview=(0, 0, 0, 0, H2, W2), wino24=_FOLD_LAYOUTS[kind][1])
         else:
+            wd, S = cp.grad_ws_fold_det() if _DETERMINISTIC else (w4, 1)      # deterministic mode: every class launches into its own S slabs
             for py in range(2):
                 for px in range(2):
-                    wgrad_launch(xpad, Taps.get("fold", 4, 0, py, px), dy, w4, cp.Cout, gmask=y, dbias=bws, Ho=Hh, Wo=W,
-                                 gview=(2, 2, py, px, H2, W2), dw_off=(py * 2 + px) * 16 * cp.CinWs * cp.Cout)
+                    wgrad_launch(xpad, Taps.get("fold", 4, 0, py, px), dy, wd, cp.Cout, gmask=y, dbias=bws, Ho=Hh, Wo=W,
+                                 gview=(2, 2, py, px, H2, W2), dw_off=(py * 2 + px) * S * 16 * cp.CinWs * cp.Cout)
         g_rows = torch.empty(2, B * W2, 2 * cp.Cout, device=dev)
         g_cols = torch.empty(2, B * H2, 2 * cp.Cout, device=dev)
         H.check(L.ramnet_frame_gather(_p(dy), _p(y), _p(g_rows), _p(g_cols), B, H2, W2, cp.Cout, _st()), "ramnet_frame_gather")
-        gemm2(a_rows, g_rows, wr, a_cols, g_cols, wc, trans_a=True, accumulate=True)      # w[s] += a[s]^T g[s]: the border GEMMs' weight gradient
+        # w[s] += a[s]^T g[s]: the border GEMMs' weight gradient (deterministic mode: the reduction slices joined in slice order through a buffer of the layer)
+        gemm2(a_rows, g_rows, wr, a_cols, g_cols, wc, trans_a=True, accumulate=True, owner=cp)
 
 
 # Backward-data of the folded upsample-conv: the adjoint of (four parity convolutions of the replicate-padded input + border GEMMs),
@@ -1737,7 +1899,12 @@ class TConvAct(Function):
             wgrad_launch(dy, taps, x, ws, Cx, stride=2, xm=mask, in_mode=mode)
         if cp.biases[0] is not None and ctx.needs_input_grad[2]:
             dyc = dy.contiguous()
-            H.check(H.lib().ramnet_bias_grad(_p(dyc), _p(mask), _p(ensure_grad(cp.biases[0])), B * 4 * Hh * W, cp.Cin, _st()), "bias_grad")
+            if _DETERMINISTIC:          # the workgroups' partial rows joined in workgroup order
+                part = cp.det_partial("bias", H.lib().ramnet_bias_grad_partial_floats(cp.Cin))
+                H.check(H.lib().ramnet_bias_grad_ordered(_p(dyc), _p(mask), _p(ensure_grad(cp.biases[0])), B * 4 * Hh * W, cp.Cin, _p(part), _st()),
+                        "bias_grad_ordered")
+            else:
+                H.check(H.lib().ramnet_bias_grad(_p(dyc), _p(mask), _p(ensure_grad(cp.biases[0])), B * 4 * Hh * W, cp.Cin, _st()), "bias_grad")
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(B, Hh, W, Cx, device=ctx.xmeta.device)
@@ -2227,6 +2394,12 @@ def _pred_grads(ctx, w, b):
     return dw, db
 
 
+def _pred_partial(device):
+    """Partial rows of an ordered prediction-layer backward (deterministic mode): a buffer per launch — the layer has no ConvParam, and a
+    buffer of its own cannot meet a launch of the same layer on another stream."""
+    return torch.empty(H.lib().ramnet_pred_bwd_partial_floats(), device=device)
+
+
 class PredSigmoid(Function):
     """pred = sigmoid(conv1x1(x) + b) (statenet.py:116-117, 313); returns NCHW [B,1,H,W]."""
 
@@ -2251,6 +2424,10 @@ class PredSigmoid(Function):
                 H.check(H.lib().ramnet_pred_sigmoid_dgrad(Cc, _p(w.detach()), _p(y), _p(dy), _p(dx), Cc, B * Hh * W, _st()), "pred_dgrad")
             return dx, None, None
         dw, db = _pred_grads(ctx, w, b)
+        if _DETERMINISTIC:
+            H.check(H.lib().ramnet_pred_sigmoid_bwd_ordered(_p(x), ld(x), Cc, _p(w.detach()), _p(y), _p(dy), _p(dx), Cc, _p(dw), _p(db), B * Hh * W,
+                                                            _p(_pred_partial(ctx.xmeta.device)), _st()), "pred_bwd_ordered")
+            return dx, None, None
         H.check(H.lib().ramnet_pred_sigmoid_bwd(_p(x), ld(x), Cc, _p(w.detach()), _p(y), _p(dy), _p(dx), Cc,
                                                 _p(dw), _p(db), B * Hh * W, _st()), "pred_bwd")
         return dx, None, None
@@ -2324,6 +2501,8 @@ class PredSigmoidSI(Function):
         # the fixed-order join of the weight / bias partial sums runs through the forward's scratch; its layout follows the library options
         # ("pred_si_cap" / "pred_si_bwd_cap"): had they changed since the forward pass, fall back to the atomic form instead of a wrong layout
         join = scratch.numel() == H.lib().ramnet_pred_si_scratch_doubles(seg_pix, n)
+        if not join:
+            not_deterministic("PredSigmoidSI.backward after a change of the library options pred_si_cap / pred_si_bwd_cap (its atomic fall-back)")
         H.check(H.lib().ramnet_pred_sigmoid_si_bwd(_p(x), ld(x), Cc, _p(w.detach()), _p(y), _p(dy), seg_pix, n, arr, _p(stats), _p(gs), weight,
                                                    n_lambda, _p(dx), Cc, _p(dw), _p(db), _p(scratch) if join else None, int(mask_x), _st()), "pred_si_bwd")
         return (dx, None, None, None, None, None) + (None,) * n
@@ -2355,9 +2534,21 @@ class PredLinear(Function):
                 H.check(H.lib().ramnet_pred_linear_dgrad(Cc, _p(w.detach()), _p(dz), _p(dx), Cc, B * Hh * W, _st()), "pred_linear_dgrad")
             return dx, None, None
         dw, db = _pred_grads(ctx, w, b)
+        if _DETERMINISTIC:
+            H.check(H.lib().ramnet_pred_linear_bwd_ordered(_p(x), ld(x), Cc, _p(w.detach()), _p(dz), _p(dx), Cc, _p(dw), _p(db), B * Hh * W,
+                                                           _p(_pred_partial(ctx.xmeta.device)), _st()), "pred_linear_bwd_ordered")
+            return dx, None, None
         H.check(H.lib().ramnet_pred_linear_bwd(_p(x), ld(x), Cc, _p(w.detach()), _p(dz), _p(dx), Cc, _p(dw),
                                                _p(db), B * Hh * W, _st()), "pred_linear_bwd")
         return dx, None, None
+
+
+def _si_capture_check(what):
+    """The stand-alone SI / SI-log statistics are joined in a fixed order by their one-launch form (the library's scratch of the stream);
+    inside a stream capture that form may be unavailable and the launch would zero-fill and add atomically: refused in deterministic mode."""
+    if _DETERMINISTIC and torch.cuda.is_current_stream_capturing():
+        not_deterministic("%s inside a stream capture (its one-launch join needs library scratch a capture cannot take; the fused "
+                          "PredSigmoidSI is ordered)" % what)
 
 
 class SILoss(Function):
@@ -2365,6 +2556,7 @@ class SILoss(Function):
 
     @staticmethod
     def forward(ctx, pred, target, weight, n_lambda):
+        _si_capture_check("scale_invariant_loss")
         pred, target = pred.contiguous(), target.contiguous()
         stats = torch.empty(4, device=pred.device, dtype=torch.float64)      # sums + the reduction's arrival ticket
         loss = torch.empty((), device=pred.device)
@@ -2385,6 +2577,7 @@ class SILoss(Function):
 def si_local_stats(pred, target, out_row):
     """(sum d, sum d^2, n) of ONE supervised map into out_row (4 doubles of a caller-owned table; [3] is the reduction's scratch):
     the per-rank half of the exact data-parallel SI loss.  Not differentiated — SILossFromStats carries the gradient."""
+    _si_capture_check("si_local_stats")
     pred, target = pred.contiguous(), target.contiguous()
     dummy = torch.empty((), device=pred.device)
     H.check(H.lib().ramnet_si_loss_fwd(_p(pred), _p(target), pred.numel(), 1.0, 1.0, _p(out_row), _p(dummy), _st()), "si_fwd")
@@ -2418,6 +2611,7 @@ class SILogLoss(Function):
 
     @staticmethod
     def forward(ctx, pred, target, n_lambda):
+        _si_capture_check("scale_invariant_log_loss")
         pred, target = pred.contiguous(), target.contiguous()
         stats = torch.empty(4, device=pred.device, dtype=torch.float64)
         loss = torch.empty((), device=pred.device)
@@ -2441,6 +2635,7 @@ class MSELoss(Function):
 
     @staticmethod
     def forward(ctx, pred, target, half):
+        not_deterministic("mse_loss")
         pred, target = pred.contiguous(), target.contiguous()
         assert pred.dim() == 4 and pred.shape[1] == 1 and pred.shape == target.shape, "mse_loss: [B, 1, H, W] maps"
         B, _, Hh, W = pred.shape
@@ -2481,6 +2676,7 @@ class MSGLoss(Function):
 
     @staticmethod
     def forward(ctx, pred, target, num_scales):
+        not_deterministic("multi_scale_grad_loss (the unbatched form; multi_scale_grad_loss_batch is ordered)")
         pred, target = pred.contiguous(), target.contiguous()
         B, _, Hh, W = pred.shape
         L = H.lib()
@@ -2520,6 +2716,9 @@ def set_grad_loss_batched(on):
     forward loop (multi_scale_grad_loss_batch: deterministic, no saved pyramid) — on by default; off: one multi_scale_grad_loss per
     map, as before (A/B runs and the per-pair path's tests)."""
     global _GRAD_LOSS_BATCHED
+    if not on and _DETERMINISTIC:
+        raise RuntimeError("set_grad_loss_batched(False) has no deterministic form: the unbatched multi-scale gradient loss joins by "
+                           "atomic adds (set_deterministic(True) is on)")
     _GRAD_LOSS_BATCHED = bool(on)
 
 

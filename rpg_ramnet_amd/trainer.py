@@ -64,6 +64,15 @@ LOSS_SEMANTICS = {
 }
 
 
+def apply_deterministic_config(config):
+    """The optional key config['trainer']['deterministic'] (default false; not in the reference): true switches the deterministic mode on
+    (ops.set_deterministic) for the process — bit-reproducible steps per rank on the same machine, device, world size and library build;
+    the order in which a collective sums the ranks' gradients is the communication library's.  Absent or false leaves the switch alone."""
+    if config.get('trainer', {}).get('deterministic', False):
+        ops.set_deterministic(True)
+    return ops.deterministic()
+
+
 LOSS_TYPES = ("scale_invariant_loss", "scale_invariant_log_loss", "mse_loss")      # config['loss']['type'] (train.py:192 getattr(module_loss, ...))
 
 
@@ -266,6 +275,7 @@ class EpochTrainer:
         import os
         from . import checkpoint as ck
         self.model, self.config, self.train_epoch, self.reducer = model, config, train_epoch, reducer
+        apply_deterministic_config(config)
         self.epochs = config['trainer']['epochs']
         self.save_freq = config['trainer']['save_freq']
         # optional partial training (config['trainer']['freeze' | 'train_only']) BEFORE the optimizer exists; the optimizer still gets
@@ -356,6 +366,7 @@ class SequenceTrainer:
         self.config, self.model, self.optimizer, self.reducer, self.group = config, model, optimizer, reducer, process_group
         self.data_loader, self.valid_data_loader = data_loader, valid_data_loader
         tr = config['trainer']
+        apply_deterministic_config(config)
         self.frozen = apply_freeze_config(model, config)       # optional tr['freeze'] / tr['train_only'] (before epoch_trainer() builds the optimizer)
         self.num_previews, self.num_val_previews = tr['num_previews'], tr['num_val_previews']
         self.loss_composition, self.loss_weights = tr['loss_composition'], tr['loss_weights']

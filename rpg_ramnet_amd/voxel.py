@@ -8,7 +8,31 @@ import numpy as np
 import torch
 
 from . import _hip as H
+from . import ops
 from .ops import _p, _st
+
+
+def _voxelize_batch(L, cat, off, G, max_count, num_bins, width, height, grids):
+    """ramnet_voxelize_batch; in deterministic mode its sorted form alone (fixed-point accumulation: the same bits on every launch) — the
+    other forms, asked for through the library option "voxel_sorted" = 0 or needed by a launch the sorted form cannot take, are refused."""
+    if ops.deterministic():
+        if not L.ramnet_get_option(b"voxel_sorted"):
+            ops.not_deterministic("the unsorted voxeliser (library option voxel_sorted = 0)")
+        H.check(L.ramnet_voxelize_batch_sorted(_p(cat), _p(off), G, int(max_count), num_bins, int(width), int(height), _p(grids), _st()),
+                "ramnet_voxelize_batch_sorted")
+        return
+    H.check(L.ramnet_voxelize_batch(_p(cat), _p(off), G, int(max_count), num_bins, int(width), int(height), _p(grids), _st()),
+            "ramnet_voxelize_batch")
+
+
+def _normalize_batch(L, grids, G, n, scratch):
+    """ramnet_normalize_nonzero_batch; in deterministic mode its ordered form (statistics joined in workgroup order; buffers of its own)."""
+    if ops.deterministic():
+        stats = torch.empty(3 * G, device=grids.device, dtype=torch.float64)
+        part = torch.empty(L.ramnet_nonzero_stats_scratch_doubles(G, n), device=grids.device, dtype=torch.float64)
+        H.check(L.ramnet_normalize_nonzero_batch_ordered(_p(grids), G, n, _p(stats), _p(part), _st()), "ramnet_normalize_nonzero_batch_ordered")
+        return
+    H.check(L.ramnet_normalize_nonzero_batch(_p(grids), G, n, _p(scratch), _st()), "ramnet_normalize_nonzero_batch")
 
 
 def _events(events, device):
@@ -24,6 +48,10 @@ def events_to_voxel_grid(events, num_bins, width, height, device=None):
     device = torch.device(device) if device is not None else (events.device if torch.is_tensor(events) else torch.device("cuda:0"))
     ev = _events(events, device)
     grid = torch.empty(num_bins, int(height), int(width), device=device, dtype=torch.float32)
+    if ops.deterministic():         # the single-list entry point scatters with global atomics: one list through the sorted batch form
+        off = torch.tensor([0, ev.shape[0]], dtype=torch.int64).to(device)
+        _voxelize_batch(H.lib(), ev if ev.numel() else None, off, 1, ev.shape[0], num_bins, width, height, grid)
+        return grid
     H.check(H.lib().ramnet_voxelize(_p(ev) if ev.numel() else None, ev.shape[0], num_bins, int(width), int(height),
                                     _p(grid), _st()), "ramnet_voxelize")
     return grid
@@ -43,6 +71,11 @@ def normalize_nonzero(grid):
     """Zero mean / unit std over the non-zero entries; zeros stay zero.  Returns a new tensor."""
     out = grid.detach().clone().float().contiguous()
     scratch = torch.empty(3, device=out.device, dtype=torch.float64)
+    if ops.deterministic():
+        L = H.lib()
+        part = torch.empty(L.ramnet_nonzero_stats_scratch_doubles(1, out.numel()), device=out.device, dtype=torch.float64)
+        H.check(L.ramnet_normalize_nonzero_ordered(_p(out), out.numel(), _p(scratch), _p(part), _st()), "ramnet_normalize_nonzero_ordered")
+        return out
     H.check(H.lib().ramnet_normalize_nonzero(_p(out), out.numel(), _p(scratch), _st()), "ramnet_normalize_nonzero")
     return out
 
@@ -67,13 +100,12 @@ def events_to_voxel_grids_packed(cat, off, max_count, num_bins, width, height, o
     grids = out if out is not None else torch.empty(G, num_bins, int(height), int(width), device=device, dtype=torch.float32)
     assert tuple(grids.shape) == (G, num_bins, int(height), int(width)) and grids.is_contiguous() and grids.dtype == torch.float32
     L = H.lib()
-    H.check(L.ramnet_voxelize_batch(_p(cat), _p(off), G, int(max_count), num_bins, int(width), int(height), _p(grids), _st()),
-            "ramnet_voxelize_batch")
+    _voxelize_batch(L, cat, off, G, max_count, num_bins, width, height, grids)
     if normalize:
         assert n % 4 == 0, "batched normalisation: bins * height * width must be a multiple of 4"
         if scratch is None:
             scratch = torch.empty(3 * G, device=device, dtype=torch.float64)
-        H.check(L.ramnet_normalize_nonzero_batch(_p(grids), G, n, _p(scratch), _st()), "ramnet_normalize_nonzero_batch")
+        _normalize_batch(L, grids, G, n, scratch)
     return grids
 
 
@@ -91,11 +123,10 @@ def events_to_voxel_grids(event_lists, num_bins, width, height, device=None, nor
     G, n = len(evs), num_bins * int(height) * int(width)
     grids = torch.empty(G, num_bins, int(height), int(width), device=device, dtype=torch.float32)
     L = H.lib()
-    H.check(L.ramnet_voxelize_batch(_p(cat), _p(off), G, max(counts), num_bins, int(width), int(height), _p(grids), _st()),
-            "ramnet_voxelize_batch")
+    _voxelize_batch(L, cat, off, G, max(counts), num_bins, width, height, grids)
     if normalize:
         if n % 4:
             return torch.stack([normalize_nonzero(g) for g in grids])
         scratch = torch.empty(3 * G, device=device, dtype=torch.float64)
-        H.check(L.ramnet_normalize_nonzero_batch(_p(grids), G, n, _p(scratch), _st()), "ramnet_normalize_nonzero_batch")
+        _normalize_batch(L, grids, G, n, scratch)
     return grids

@@ -597,8 +597,19 @@ int ramnet_normalize_nonzero(float *grid, size_t n, double *scratch, void *strea
 /* Batched forms (one launch for the B x K grids of a batch of packages): event lists concatenated in `events`, list g =
  * rows offsets[g] .. offsets[g+1] (device int64 [n_grids+1]; each list sorted by t, normalised by ITS first / last stamp),
  * max_events = longest list; grids [n_grids][bins][H][W] (zeroed here).  normalize: n = bins*H*W (multiple of 4) per grid, `grids`
- * 16-byte aligned (also for ramnet_nonzero_stats_batch), scratch = 3*n_grids doubles.  Same arithmetic per grid as the single-grid entry points.  Launches of >= 16 grids resolve the
- * votes in LDS row bands (no global atomics, no zero-fill pass); smaller ones scatter with global fp32 atomics.             */
+ * 16-byte aligned (also for ramnet_nonzero_stats_batch), scratch = 3*n_grids doubles.  Same arithmetic per grid as the single-grid entry points.
+ * EVERY list must hold at most max_events events (the forms below size their record and band-id regions from max_events; a longer list would
+ * be stored past them; a larger max_events only costs empty chunks); max_events = 0 (all lists empty) takes events = NULL.  An event lies in
+ * the image where -1 < x < W and -1 < y < H on the double (the integer conversion truncates towards zero); NaN, +-inf and values no integer
+ * holds cast no vote, in every form.  Polarities must be finite (0 counts as -1).  Which form takes a ramnet_voxelize_batch launch
+ * (ramnet_last_kernel() names it, with the rows of a band):
+ *   - from 2 lists, option "voxel_sorted" = 1 (the default), 0 < max_events < 2^30, W and H <= 32767, outside a stream capture, and at least
+ *     one row of 8-byte cells of all bins fits into 160 KB of LDS beside a table of 2 * ceil(max_events / 8192) + 16 ints with at most 254
+ *     bands: the SORTED form (records sorted by row band in library scratch, votes added as 2^-40 fixed-point integers in LDS: the same bits
+ *     on every launch, one rounding per cell; no zero-fill pass, no global atomics);
+ *   - else from 16 lists, where a row of 4-byte cells fits beside a queue of 8192 (4096) ints: LDS row bands with fp32 atomics, walking
+ *     one band id per event (library scratch) or, inside a stream capture and for max_events = 0, the lists themselves;
+ *   - else a zero-fill and a scatter with global fp32 atomics.                                                                           */
 int ramnet_voxelize_batch(const double *events, const long long *offsets, int n_grids, size_t max_events, int bins, int W, int H,
                           float *grids, void *stream);
 int ramnet_normalize_nonzero_batch(float *grids, int n_grids, size_t n, double *scratch, void *stream);

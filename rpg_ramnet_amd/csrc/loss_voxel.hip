@@ -385,10 +385,15 @@ static int msg_args(int B, int H, int W, int ns, MsgArgs &a, size_t &total) {
 // (xs, ys, pol) of an event and whether it lies inside the image; then the two votes of (t, xs, ys, pol) — split so that the sorted form
 // can carry the integer coordinates between its two passes; voxel_vote() is the composition, operation for operation as before.
 __device__ __forceinline__ bool voxel_coord(double x, double y, double p, int W, int H, long long &xs, long long &ys, float &pol) {
-    xs = (long long)x, ys = (long long)y;
+    // The image test runs on the doubles, as in voxel_band_ids_kernel, in_band and voxel_sort_chunks_kernel: the conversion truncates towards
+    // zero, so 0 <= (long long)v < N  <=>  -1 < v < N for every v that a long long holds; for the others (NaN, +-inf, 1e300) the conversion is
+    // undefined, and what the hardware's sequence returned for a NaN was 0: an event with x = NaN voted in column 0 of the atomic and row-band
+    // forms and in no cell of the sorted one.  Only in-range values are converted.
+    const bool inside = x > -1.0 && x < (double)W && y > -1.0 && y < (double)H;        // the reference would raise on an OOB index
+    xs = (long long)(inside ? x : 0.0), ys = (long long)(inside ? y : 0.0);
     pol = (float)p;
     if (pol == 0.f) pol = -1.f;
-    return xs >= 0 && xs < W && ys >= 0 && ys < H;        // the reference would raise on an OOB index
+    return inside;
 }
 
 __device__ __forceinline__ void voxel_vote_t(double t, long long xs, long long ys, float pol, bool inside, double t0, double t1, int bins, int W,
@@ -1066,6 +1071,7 @@ static int launch_voxel_sorted(const double *events, const long long *offsets, i
             hipLaunchKernelGGL(voxelize_sorted_kernel, dim3(8 * cdiv(n_grids, 8) * nbands), dim3(1024), lds, st, events, offsets, n_grids, bins, W, H,
                                rows, grids, rec, rstride, tab, nchunks);
             RAMNET_LAUNCH_CHECK();
+            note_kernel("voxel_sort_chunks_kernel + voxelize_sorted_kernel<rows=%d>", rows);
             return 0;
         }
     }
@@ -1091,6 +1097,7 @@ static int launch_voxel_bands(const double *events, const long long *offsets, lo
         hipLaunchKernelGGL(voxelize_bands_kernel<true>, dim3(8 * cdiv(n_grids, 8) * cdiv(H, rows_ids)), dim3(1024), lds, st, events, offsets,
                            n_single, n_grids, bins, W, H, rows_ids, grids, ids, stride);
         RAMNET_LAUNCH_CHECK();
+        note_kernel("voxel_band_ids_kernel + voxelize_bands_kernel<true,rows=%d>", rows_ids);
         return 0;
     }
     const int rows = voxel_band_rows(bins, W, H, n_grids, 4096);
@@ -1100,17 +1107,20 @@ static int launch_voxel_bands(const double *events, const long long *offsets, lo
     hipLaunchKernelGGL(voxelize_bands_kernel<false>, dim3(8 * cdiv(n_grids, 8) * cdiv(H, rows)), dim3(1024), lds, st, events, offsets, n_single,
                        n_grids, bins, W, H, rows, grids, nullptr, 0);
     RAMNET_LAUNCH_CHECK();
+    note_kernel("voxelize_bands_kernel<false,rows=%d>", rows);
     return 0;
 }
 
 extern "C" int ramnet_voxelize(const double *events, size_t n_events, int bins, int W, int H, float *grid, void *stream) {
     RAMNET_CHECK_ARG(grid && bins > 0 && W > 0 && H > 0);
     hipStream_t st = (hipStream_t)stream;
+    RAMNET_CHECK_ARG(events != nullptr || n_events == 0);       // (refused before anything is enqueued)
     RAMNET_HIP(hipMemsetAsync(grid, 0, (size_t)bins * W * H * sizeof(float), st));
+    note_kernel("zero_fill");
     if (n_events == 0) return 0;
-    RAMNET_CHECK_ARG(events != nullptr);
     hipLaunchKernelGGL(voxelize_kernel, dim3(grid_for(n_events)), dim3(256), 0, st, events, n_events, bins, W, H, grid);
     RAMNET_LAUNCH_CHECK();
+    note_kernel("voxelize_kernel");
     return 0;
 }
 
@@ -1124,15 +1134,17 @@ extern "C" int ramnet_voxelize_batch(const double *events, const long long *offs
         const int rc = launch_voxel_bands(events, offsets, 0, n_grids, max_events, bins, W, H, grids, st);
         if (rc >= 0) return rc;
     }
+    RAMNET_CHECK_ARG(events != nullptr || max_events == 0);     // (refused before anything is enqueued)
     RAMNET_HIP(hipMemsetAsync(grids, 0, (size_t)n_grids * bins * W * H * sizeof(float), st));
+    note_kernel("zero_fill");
     if (max_events == 0) return 0;
-    RAMNET_CHECK_ARG(events != nullptr);
     int gx = (int)((max_events + 255) / 256);
     const int cap = (2048 * 4 + n_grids - 1) / n_grids;       // ~32 workgroups per CU over the whole launch
     if (gx > cap) gx = cap;
     if (gx < 1) gx = 1;
     hipLaunchKernelGGL(voxelize_batch_kernel, dim3(gx, n_grids), dim3(256), 0, st, events, offsets, bins, W, H, grids);
     RAMNET_LAUNCH_CHECK();
+    note_kernel("voxelize_batch_kernel");
     return 0;
 }
 
@@ -1143,6 +1155,7 @@ extern "C" int ramnet_voxelize_batch_sorted(const double *events, const long lon
     hipStream_t st = (hipStream_t)stream;
     if (max_events == 0) {
         RAMNET_HIP(hipMemsetAsync(grids, 0, (size_t)n_grids * bins * W * H * sizeof(float), st));
+        note_kernel("zero_fill");
         return 0;
     }
     RAMNET_CHECK_ARG(events != nullptr);

@@ -1,4 +1,4 @@
-"""The guarded call of the direct kernel tests (tests/test_hip_pointwise.py, tests/test_hip_reductions.py, tests/test_hip_conv_launch.py): device buffers between
+"""The guarded call of the direct kernel tests (tests/test_hip_pointwise.py, tests/test_hip_reductions.py, tests/test_hip_conv_launch.py, tests/test_hip_voxel_launch.py): device buffers between
 sentinel / NaN guards, the one way to an entry point of the C ABI, and the comparison rules of profiles/pointwise_tests_notes.md §1.
 
 `dtype`: float32 (default), float64 (`stats`, `part`, `mean`, `rstd`) or int64 (`num_batches_tracked`), guards and gaps in that dtype.

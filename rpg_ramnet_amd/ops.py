@@ -537,18 +537,67 @@ _FOLD_LAYOUTS = {
 }
 
 
+class _GradWs:
+    """One weight-gradient workspace of a layer through its passes: [groups][count slabs][one floats], zero between passes.  The launches
+    of a pass own `count` slabs per group (1: none, they meet in the one slab); join() folds them into slab 0 in slab order."""
+    __slots__ = ("t", "one", "count", "groups", "used")
+
+    def __init__(self):
+        self.t, self.one, self.count, self.groups, self.used = None, 0, 1, 1, False
+
+    def reserve(self, device, *shape, anew=False):
+        """At least prod(shape) zeros (between passes the workspace holds zeros: grown by reallocation; anew: reallocated whatever it holds)."""
+        if anew or self.t is None or self.t.numel() < torch.Size(shape).numel():
+            self.t = torch.zeros(*shape, device=device)
+        return self.t
+
+    def begin(self, one, count=1, groups=1):
+        """The pass writes `count` slabs of `one` floats per group; the largest count where several paths of a pass share the workspace."""
+        self.count = max(count, self.count if self.used else 1)
+        self.one, self.groups, self.used = one, groups, True
+
+    def join(self):
+        if self.used and self.count > 1:
+            for g in range(self.groups):
+                H.check(H.lib().ramnet_reduce_slabs(_p(self.t, g * self.count * self.one), self.count, self.one, _st()), "ramnet_reduce_slabs")
+
+    def zero(self, whole=False, kernel=False):
+        """Zero what the pass used for the next one: slab 0 of every group (where the slabs were joined, ramnet_reduce_slabs left slabs 1..
+        zeroed) — not the whole buffer sized for the largest layout unless `whole`; kernel: the fold's unpack launch has done it."""
+        if self.used and not kernel:
+            n, flat = self.count * self.one, self.t.view(-1)
+            for g in range(0 if whole else self.groups):
+                _zero_later(flat[g * n:g * n + self.one])
+            if whole:
+                _zero_later(flat)
+        self.used, self.count = False, 1
+
+    def discard(self):
+        """Zero everything without folding it (aborted backward pass)."""
+        if self.t is not None:
+            self.t.zero_()
+        self.used, self.count = False, 1
+
+
 def _stamp_layout(dw, kind, slabs, head_cin=0, det_slabs=0):
-    """Write the layout of a pass onto its workspace tensor (the protocol stated at wgrad_launch); ConvParam.grad_ws is the one caller.
-    det_slabs (deterministic mode): slabs of a workspace of the direct / head / fold kinds, which have none otherwise."""
+    """Write the layout of a pass onto its workspace tensor (the protocol stated at wgrad_launch): the one writer in the package, for the layer
+    and the fold workspaces alike.  det_slabs (deterministic mode): slabs of a workspace of the direct / head / fold kinds, which have none otherwise."""
     dw.wino, dw.wino6, dw.wg_dsplit = kind == "wino", kind == "wino6", kind == "dsplit"
-    dw.slabs, dw.head_cin = slabs, head_cin
-    dw.det_slabs = det_slabs
+    dw.slabs, dw.head_cin, dw.det_slabs = slabs, head_cin, det_slabs
     return dw
 
 
 def _det_slabs(dw):
     """Slabs of a direct / head / fold workspace stamped in deterministic mode (0: the one-slab atomic form)."""
     return getattr(dw, "det_slabs", 0)
+
+
+def _launch_slabs(dw, wino24):
+    """ramnet_wgrad_desc.dw_slabs of a launch into the stamped workspace dw: the per-split slabs of the 3x3 families (read-modify-write
+    joins), in deterministic mode those of the direct, head and fold kinds as well; 0 = the launch's splits meet in slab 0 by atomic adds."""
+    kind, slabs = _layout_of(dw)
+    det = _det_slabs(dw) if (kind == "direct" or wino24) else 0
+    return 0 if not _WGRAD_SLABS else det or (slabs if kind != "direct" else 0)
 
 
 _DET_SLAB_QUERIES = {}
@@ -600,12 +649,9 @@ def _wgrad_desc_build(x0, taps, dout, dw, Cout, stride, x1, xm, xm_off, in_mode,
     d.dw, d.dbias = _p(dw, dw_off), _p(dbias)
     if gview is not None:      # dout / gmask addressed as (oy*gsy + goy, ox*gsx + gox) of [B, HoG, WoG]
         d.gsy, d.gsx, d.goy, d.gox, d.HoG, d.WoG = gview
-    kind, slabs = _layout_of(dw)
-    d.algo = _LAYOUTS[kind][3]
-    d.dw_slabs = slabs if (kind != "direct" and _WGRAD_SLABS) else 0     # per-split slabs (read-modify-write joins)
-    if _det_slabs(dw) and _WGRAD_SLABS and (kind == "direct" or wino24):    # deterministic mode: the direct, head and fold kinds as well
-        d.dw_slabs = _det_slabs(dw)
-    if wino24:          # folded upsample-conv in the Winograd F(2x2,4x4) domain: dw = [4][25][C0][Cout]; "2x3": F(2x3,4x4), dw = [4][30][C0][Cout]
+    d.algo = _LAYOUTS[_layout_of(dw)[0]][3]
+    d.dw_slabs = _launch_slabs(dw, wino24)
+    if wino24:         # folded upsample-conv in the Winograd F(2x2,4x4) domain: dw = [4][25][C0][Cout]; "2x3": F(2x3,4x4), dw = [4][30][C0][Cout]
         d.algo = H.ALGO_WINOGRAD24_2X3 if wino24 == "2x3" else H.ALGO_WINOGRAD24
     hc = getattr(dw, "head_cin", 0)
     if hc and _HEAD and taps.head and stride == 1 and in_mode == H.IN_PLAIN and gview is None and dw_off == 0:
@@ -621,7 +667,7 @@ def wgrad_launch(x0, taps, dout, dw, Cout, *, stride=1, x1=None, xm=None, xm_off
     in one launch (deferred ConvGRU cell updates, _wgrad_cell); x0 ... gmask then describe the first segment."""
     # The layout of `dw` travels as plain attributes of the tensor: wino / wino6 / wg_dsplit (bool, absent = False; wg_dsplit wins over
     # wino6 over wino, none = direct), slabs (int, absent = 0: no per-split slabs) and head_cin (int, absent = 0: not a head layer).
-    # ConvParam.grad_ws is the one writer in the package (_stamp_layout) and _layout_of the one reader of the first four; bench.py reads
+    # _stamp_layout is the one writer in the package (ConvParam.grad_ws*) and _layout_of the one reader of the first four; bench.py reads
     # them for its FLOP / byte accounting, tests and tools stamp them on plain tensors to pick an algorithm: the names and defaults stay.
     # (descriptor cache as for _conv_desc: the template holds everything but the six pointers)
     key = (id(taps), id(dw), _layout_of(dw), _det_slabs(dw), getattr(dw, "head_cin", 0), Cout, stride,
@@ -1024,13 +1070,14 @@ class ConvParam:
         self._bias = self._vbias = None
         self._packs = {}                 # pack key -> (_versions at pack time, packed tensor(s))
         self._splitk = {}                # floats -> split-reduction workspace (splitk_ws)
-        self._state_half = self._s2d = None
-        self._ws = self._bws = self._slabs = None
-        self._ws_fold = None             # (dW4 [64][CinWs][Cout], dWrows, dWcols) of the folded upsample-conv backward-weights
-        self._ws_fold24 = self._ws_fold23 = None
-        self._ws_fold_det = None         # deterministic mode: the direct parity launches' slabs [4 classes][S][16][CinWs][Cout]
+        self._state_half = self._s2d = self._slabs = None
+        # every gradient workspace of the layer, in the order finalize() joins them: the layer's own [slabs][tap][CinWs][Cout]; the folded
+        # upsample-conv's Winograd-domain dU [S][4][25 | 30][CinWs][Cout] and (deterministic mode) direct parity slabs [4][S][16][CinWs][Cout];
+        # the bias [slabs][Cout] of both paths; the fold's dW4 [64 = (py,px,ty,tx)][CinWs][Cout] and the two border-GEMM weight gradients
+        self._main, self._fold24, self._fold23, self._fold_direct, self._bias_ws, self._w4, self._rows, self._cols = (_GradWs() for _ in range(8))
+        self._gws = (("main", self._main), ("fold24", self._fold24), ("fold23", self._fold23), ("fold_direct", self._fold_direct),
+                     ("bias", self._bias_ws), ("w4", self._w4), ("rows", self._rows), ("cols", self._cols))
         self._part = {}                  # deterministic mode: partial buffers of the ordered joins, by name
-        self._fold_used = self._fold24_used = self._fold23_used = self._ws_used = False
         self._dirty = False
         self._defer = []                 # queued backward-weights launches of a recurrent cell (_wgrad_cell)
 
@@ -1167,16 +1214,18 @@ class ConvParam:
             buf = self._part[name] = torch.empty(max(n, 1), device=self.weights[0].device, dtype=dtype)
         return buf
 
-    def _bias_slabs(self, ns):
-        """The bias workspace with room for ns slabs [ns][Cout] (zero between passes: grown by reallocation)."""
-        if self._bws is None or self._bws.numel() < ns * self.Cout:
-            self._bws = torch.zeros(ns * self.Cout, device=self.weights[0].device)
-        self._bws_slabs = max(getattr(self, "_bws_slabs", 1), ns)
-        return self._bws
+    def workspaces(self):
+        """(name, _GradWs) of every gradient workspace of the layer; a record's tensor `t` is None until a pass has asked for it."""
+        return iter(self._gws)
 
     def _slab_floats(self, kind):
         f = _LAYOUTS[kind][0]
         return getattr(H.lib(), f)(self.CinWs, self.Cout) if isinstance(f, str) else (f or self.k * self.k) * self.CinWs * self.Cout
+
+    def _fold_slab_floats(self, kind=None):
+        """One slab of a workspace of the folded upsample-conv: [4 classes][positions][CinWs][Cout] of a Winograd-domain kind
+        (_FOLD_LAYOUTS), the [16 taps][CinWs][Cout] of ONE parity class of the direct launches without one."""
+        return (4 * _FOLD_LAYOUTS[kind][0] if kind else 16) * self.CinWs * self.Cout
 
     def _choose_layout(self, wino_ok):
         """(kind, slabs) of the weight-gradient workspace for the pass that starts: one algorithm per layer and pass."""
@@ -1195,7 +1244,8 @@ class ConvParam:
         """([tap][CinWs][Cout] weight-gradient workspace, [Cout] bias-gradient workspace), zero at pass start.
         wino_ok: the caller's launch is a plain 3x3 stride-1 convolution (no upsampling loader), i.e. eligible for the
         Winograd backward-weights kernel, whose workspace holds the transformed-domain gradient [16][CinWs][Cout]."""
-        if self._ws is None:
+        m, b = self._main, self._bias_ws
+        if m.t is None:
             dev = self.weights[0].device
             slots = 24 if self.k == 3 else self.k * self.k       # 3x3: room for the Winograd-domain gradient dU (F(2x4): 24, F(2x2): 16 positions)
             # 3x3 layers: one slab per tile split of the Winograd backward-weights launch (joined by plain read-modify-write: no atomics,
@@ -1204,166 +1254,118 @@ class ConvParam:
             # (F(2x4): blocked layout padded to 32 x 32-channel blocks, half as many slabs as F(2x2): never larger than the dense 24-slot slabs
             # of F(2x2)'s count unless the channel counts are ragged — take the maximum)
             n6 = self._slab_floats("wino6") * getattr(H.lib(), _LAYOUTS["wino6"][1])(self.CinWs, self.Cout) if self.k == 3 else 0
-            self._ws = torch.zeros(max(self._slabs * slots * self.CinWs * self.Cout, n6), device=dev)
-            self._bws = torch.zeros(self._slabs * self.Cout, device=dev)
+            m.reserve(dev, max(self._slabs * slots * self.CinWs * self.Cout, n6))
+            b.reserve(dev, self._slabs * self.Cout)
         _Engine.enter()         # (a new pass after an aborted one resets _dirty first)
         if not self._dirty:     # every launch of the pass accumulates into the same layout
-            kind, ns = self._choose_layout(wino_ok)
-            n = ns * self._slab_floats(kind) if kind == "dsplit" else 0
-            det = 0
-            if _DETERMINISTIC and kind == "direct":         # the direct (and head) launches own slabs as well: [S][k x k][CinWs][Cout]
-                det = _det_slab_query(H.ALGO_DIRECT, self.CinWs, self.Cout, self.k)
-                n, ns = det * self._slab_floats(kind), det
-            if self._ws.numel() < n or (n and self._bws.numel() < ns * self.Cout):
-                dev = self._ws.device                       # (between passes the workspaces hold zeros: grow them)
-                self._ws = torch.zeros(max(n, self._ws.numel()), device=dev)
-                self._bws = torch.zeros(max(ns, self._slabs) * self.Cout, device=dev)
+            kind, ns = self._choose_layout(wino_ok)         # (deterministic mode: the direct / head launches own slabs as well, [S][k x k][CinWs][Cout])
+            det = _det_slab_query(H.ALGO_DIRECT, self.CinWs, self.Cout, self.k) if (_DETERMINISTIC and kind == "direct") else 0
+            one, count = self._slab_floats(kind), (det if kind == "direct" else ns)      # `count` slabs for finalize() to join
+            n = count * one if (det or kind == "dsplit") else 0         # (every other layout fits the first allocation)
+            if m.t.numel() < n or (n and b.t.numel() < count * self.Cout):      # the two grow together, whichever was short
+                m.reserve(m.t.device, max(n, m.t.numel()), anew=True)
+                b.reserve(m.t.device, max(count, self._slabs) * self.Cout, anew=True)
             # head layers: the launch may run the head kernel (same [tap][CinWs][Cout] layout as the direct kernel)
-            _stamp_layout(self._ws, kind, self._choose_layout(wino_ok)[1] if det else ns,
-                          self.Cin if (self.k == 5 and self.gates == 1 and len(self.weights) == 1
-                                       and H.lib().ramnet_head_supported(self.Cin, self.Cout)) else 0, det_slabs=det)
+            _stamp_layout(m.t, kind, ns, self.Cin if (self.k == 5 and self.gates == 1 and len(self.weights) == 1
+                                                      and H.lib().ramnet_head_supported(self.Cin, self.Cout)) else 0, det_slabs=det)
+            m.begin(one, count)
+            b.begin(self.Cout, count)
         _Engine.mark(self)
-        self._ws_used = True
-        return self._ws, self._bws
+        m.used = True
+        return m.t, b.t
 
     def grad_ws_fold(self):
         """Workspaces of the folded upsample-conv backward-weights: dW4 [64 = (py,px,ty,tx)][CinWs][Cout] of the four parity
         convolutions, the gradients of the two border-GEMM weight stacks, and the shared bias workspace."""
         assert len(self.weights) == 1 and self.k == 5
-        dev = self.weights[0].device
-        if self._bws is None:
-            self._bws = torch.zeros(self.Cout, device=dev)
-        if _DETERMINISTIC:              # room for the slabs of whichever backward-weights form the launch takes
-            self._bias_slabs(max(_det_slab_query(H.ALGO_DIRECT, self.CinWs, self.Cout, 4), self._fold_det_slabs()))
-        if self._ws_fold is None:
-            self._ws_fold = (torch.zeros(64 * self.CinWs * self.Cout, device=dev),
-                             torch.zeros(2, 5 * self.Cin, 2 * self.Cout, device=dev),
-                             torch.zeros(2, 5 * self.Cin, 2 * self.Cout, device=dev))
+        dev = self.weights[0].device        # (deterministic mode: bias slabs for whichever backward-weights form the launch takes)
+        ns = max(_det_slab_query(H.ALGO_DIRECT, self.CinWs, self.Cout, 4), self._fold_det_slabs()) if _DETERMINISTIC else 1
+        self._bias_ws.reserve(dev, ns * self.Cout)
+        self._bias_ws.begin(self.Cout, ns)
+        for r, shape in ((self._w4, (4 * self._fold_slab_floats(),)), (self._rows, (2, 5 * self.Cin, 2 * self.Cout)),
+                         (self._cols, (2, 5 * self.Cin, 2 * self.Cout))):
+            r.begin(r.reserve(dev, *shape).numel())
         _Engine.mark(self)
-        self._fold_used = True
-        return self._ws_fold + (self._bws,)
+        return self._w4.t, self._rows.t, self._cols.t, self._bias_ws.t
+
+    def _fold_one_launch(self):         # the channel rule of the one-launch Winograd-domain backward-weights kernel of the folded upsample-conv
+        return self.Cin == self.CinWs and ((self.Cin % 32 == 0 and self.Cout % 64 == 0) or (self.Cin % 64 == 0 and self.Cout % 32 == 0))
 
     def _fold_det_slabs(self):
-        ok = self.Cin == self.CinWs and ((self.Cin % 32 == 0 and self.Cout % 64 == 0) or (self.Cin % 64 == 0 and self.Cout % 32 == 0))
-        return _det_slab_query(H.ALGO_WINOGRAD24, self.Cin, self.Cout, 4) if ok else 1
+        return _det_slab_query(H.ALGO_WINOGRAD24, self.Cin, self.Cout, 4) if self._fold_one_launch() else 1
 
     def grad_ws_fold_det(self):
-        """Deterministic mode, direct parity launches: [4 classes][S][16 taps][CinWs][Cout] — class (py, px) launches into its own S slabs
-        at offset class * S * 16 * CinWs * Cout; _finalize_fold joins them and copies slab 0 of every class into the [64][CinWs][Cout]
-        workspace the fold reads."""
+        """Deterministic mode, direct parity launches: [4 classes][S][16 taps][CinWs][Cout] — class (py, px) launches into its own S slabs at
+        offset class * S * _fold_slab_floats(); finalize() joins them, _finalize_fold copies every class's slab 0 into the [64][CinWs][Cout] one."""
         S = _det_slab_query(H.ALGO_DIRECT, self.CinWs, self.Cout, 4)
-        n = 4 * S * 16 * self.CinWs * self.Cout
-        if self._ws_fold_det is None or self._ws_fold_det.numel() < n:
-            self._ws_fold_det = torch.zeros(n, device=self.weights[0].device)
-        _stamp_layout(self._ws_fold_det, "direct", 1, 0, det_slabs=S)
-        self._fold_det_used = True
-        return self._ws_fold_det, S
+        r, one = self._fold_direct, self._fold_slab_floats()
+        _stamp_layout(r.reserve(self.weights[0].device, 4 * S * one), "direct", 1, 0, det_slabs=S)
+        r.begin(one, S, groups=4)
+        return r.t, S
 
     def grad_ws_fold24(self, kind="fold24"):
         """dU [4 parity classes][25 positions][Cin][Cout]: Winograd-domain gradient of the four 4x4 parity filters — or, kind "fold23", the
         [4][30][Cin][Cout] of the F(2x3,4x4) launches (_FOLD_LAYOUTS): the workspace of the variant the launch takes."""
-        f23 = kind == "fold23"
-        ws = self._ws_fold23 if f23 else self._ws_fold24
-        det = self._fold_det_slabs() if _DETERMINISTIC else 0         # deterministic mode: one slab per tile split [S][4][positions][CinWs][Cout]
-        one = 4 * _FOLD_LAYOUTS[kind][0] * self.CinWs * self.Cout
-        if ws is None or ws.numel() < max(det, 1) * one:
-            ws = torch.zeros(max(det, 1) * one, device=self.weights[0].device)
-        ws.det_slabs = det
-        if f23:
-            self._ws_fold23, self._fold23_used = ws, True
-        else:
-            self._ws_fold24, self._fold24_used = ws, True
-        return ws
+        r = self._fold23 if kind == "fold23" else self._fold24
+        # deterministic mode: one slab per tile split [S][4][positions][CinWs][Cout]
+        det, one = (self._fold_det_slabs() if _DETERMINISTIC else 0), self._fold_slab_floats(kind)
+        _stamp_layout(r.reserve(self.weights[0].device, max(det, 1) * one), "direct", 0, 0, det_slabs=det)
+        r.begin(one, det)
+        return r.t
 
     def _finalize_fold(self):
         """dW5 += sum_parities A_py^T dW4 A_px  -  (border GEMM gradients routed back to the taps they summed), dW4 = the direct parity
         launches' workspace + G^T dU G of the Winograd-domain launches: one launch (ramnet_fold_unpack_wgrad), which also zeroes the
         workspaces for the next pass."""
-        w4, wr, wc = self._ws_fold
-        dU = self._ws_fold24 if self._fold24_used else None
-        dU3 = self._ws_fold23 if self._fold23_used else None       # F(2x3,4x4) launches of the pass: + G^T dU3 Gc
-        L = H.lib()
-        for t, kind in ((dU, "fold24"), (dU3, "fold23")):           # deterministic mode: the tile splits' slabs -> slab 0, in slab order
-            if t is not None and _det_slabs(t) > 1:
-                H.check(L.ramnet_reduce_slabs(_p(t), _det_slabs(t), 4 * _FOLD_LAYOUTS[kind][0] * self.CinWs * self.Cout, _st()), "ramnet_reduce_slabs")
-        if getattr(self, "_fold_det_used", False):                  # ... and the direct parity launches' slabs, class by class, into w4
-            wd, S = self._ws_fold_det, _det_slabs(self._ws_fold_det)
-            one = 16 * self.CinWs * self.Cout
-            for cls in range(4):
-                H.check(L.ramnet_reduce_slabs(_p(wd, cls * S * one), S, one, _st()), "ramnet_reduce_slabs")
-            w4.view(4, one).copy_(wd.view(4, S, one)[:, 0])
-            for cls in range(4):            # (slab 0 of every class: ramnet_reduce_slabs left slabs 1.. at zero)
-                _zero_later(wd[cls * S * one:cls * S * one + one])
-            self._fold_det_used = False
-        self._join_bias()
-        if self.weights[0].requires_grad:
+        w4, wr, wc, wd = self._w4, self._rows, self._cols, self._fold_direct
+        dU, dU3 = (r.t if r.used else None for r in (self._fold24, self._fold23))      # (F(2x3,4x4) launches of the pass: + G^T dU3 Gc)
+        if wd.used:                 # deterministic mode: the direct parity launches' joined slabs, class by class, into w4
+            w4.t.view(4, wd.one).copy_(wd.t.view(4, wd.count, wd.one)[:, 0])
+        trains = self.weights[0].requires_grad
+        if trains:
             g = ensure_grad(self.weights[0])
             if dU3 is not None:
-                H.check(H.lib().ramnet_fold_unpack_wgrad2x3(_p(w4), _p(dU), _p(dU3), _p(wr), _p(wc), _p(g), self.Cout, self.Cin, self.CinWs, _st()),
+                H.check(H.lib().ramnet_fold_unpack_wgrad2x3(_p(w4.t), _p(dU), _p(dU3), _p(wr.t), _p(wc.t), _p(g), self.Cout, self.Cin, self.CinWs, _st()),
                         "ramnet_fold_unpack_wgrad2x3")
             else:
-                H.check(H.lib().ramnet_fold_unpack_wgrad(_p(w4), _p(dU), _p(wr), _p(wc), _p(g), self.Cout, self.Cin, self.CinWs, _st()),
+                H.check(H.lib().ramnet_fold_unpack_wgrad(_p(w4.t), _p(dU), _p(wr.t), _p(wc.t), _p(g), self.Cout, self.Cin, self.CinWs, _st()),
                         "ramnet_fold_unpack_wgrad")
-        else:       # frozen weight beside a trainable bias (they share the launches): nothing to fold, the workspaces start the next pass at zero
-            for t in (w4, dU, dU3, wr, wc):
-                if t is not None:
-                    _zero_later(t[:t.numel() // max(_det_slabs(t), 1)] if _det_slabs(t) > 1 else t)      # (joined: slabs 1.. are zero)
-        self._fold24_used = self._fold23_used = False
-        self._fold_used = False
+        # (frozen weight beside a trainable bias — they share the launches —: nothing to fold, the workspaces start the next pass at zero)
+        for r in (w4, self._fold24, self._fold23, wr, wc):
+            r.zero(kernel=trains)
 
     def discard(self):
         """Zero every gradient workspace without folding it (aborted backward pass)."""
-        for t in (self._ws, self._bws, self._ws_fold24, self._ws_fold23, self._ws_fold_det) + tuple(self._ws_fold or ()):
-            if t is not None:
-                t.zero_()
-        self._fold_det_used = False
-        self._bws_slabs = 1
-        self._dirty = self._ws_used = self._fold_used = self._fold24_used = self._fold23_used = False
+        for _, r in self._gws:
+            r.discard()
+        self._dirty = False
 
     def _join_slabs(self):
-        """Winograd backward-weights slabs -> slab 0 (fixed order), weights and bias."""
-        kind, ns = _layout_of(self._ws)
-        if ns > 1 and kind != "direct":
-            H.check(H.lib().ramnet_reduce_slabs(_p(self._ws), ns, self._slab_floats(kind), _st()), "ramnet_reduce_slabs")
-            H.check(H.lib().ramnet_reduce_slabs(_p(self._bws), ns, self.Cout, _st()), "ramnet_reduce_slabs")
-        elif kind == "direct" and _det_slabs(self._ws) > 1:         # deterministic mode: the direct / head launches' slabs, the same way
-            ns = _det_slabs(self._ws)
-            H.check(H.lib().ramnet_reduce_slabs(_p(self._ws), ns, self._slab_floats(kind), _st()), "ramnet_reduce_slabs")
-            H.check(H.lib().ramnet_reduce_slabs(_p(self._bws), ns, self.Cout, _st()), "ramnet_reduce_slabs")
-
-    def _join_bias(self):
-        """Deterministic mode, folded decoders: the bias slabs [S][Cout] of the pass -> slab 0 (the bias workspace has one slab otherwise)."""
-        ns = getattr(self, "_bws_slabs", 1)
-        if ns > 1 and self._bws is not None:
-            H.check(H.lib().ramnet_reduce_slabs(_p(self._bws), ns, self.Cout, _st()), "ramnet_reduce_slabs")
-        self._bws_slabs = 1
+        """The slabs of every workspace of the pass -> its slab 0 (fixed order)."""
+        for _, r in self._gws:
+            r.join()
 
     def _zero_ws(self):
-        """Zero what the pass used of the gradient workspace for the next one: slab 0 only where the slabs were joined
-        (ramnet_reduce_slabs leaves slabs 1.. zeroed), not the whole buffer sized for the largest layout."""
-        kind, ns = _layout_of(self._ws)
-        n, ns = self._slab_floats(kind), (max(_det_slabs(self._ws), 1) if kind == "direct" else max(ns, 1))
-        joined = ns > 1
-        _zero_later(self._ws[:n if joined else min(self._ws.numel(), n * ns)])
-        _zero_later(self._bws[:self.Cout if joined else self._bws.numel()])
+        """Zero what the pass used for the next one (_GradWs.zero); the bias workspace whole unless the layer's own launches' slabs were joined."""
+        whole = not (self._main.used and self._main.count > 1)
+        for _, r in self._gws:
+            r.zero(whole=whole and r is self._bias_ws)
+        self._dirty = False
 
     def _unpack(self, g, n, off):
         """Output channels off .. off + n of the (joined) workspace -> the OIHW gradient g, += (the layout's own unpack launch)."""
-        kind = _layout_of(self._ws)[0]
+        kind = _layout_of(self._main.t)[0]
         taps = (self.k, self.k) if kind == "direct" else ()
-        H.check(getattr(H.lib(), _LAYOUTS[kind][2])(_p(self._ws), _p(g), n, self.Cin, self.CinWs, self.Cout, off, *taps, _st()), _LAYOUTS[kind][2])
+        H.check(getattr(H.lib(), _LAYOUTS[kind][2])(_p(self._main.t), _p(g), n, self.Cin, self.CinWs, self.Cout, off, *taps, _st()), _LAYOUTS[kind][2])
 
     def finalize(self):
-        if self._fold_used:
+        self._join_slabs()
+        if self._w4.used:
             self._finalize_fold()
-        if self._ws_used:
-            self._join_slabs()
-        if not self._ws_used:
+        if not self._main.used:
             if self.biases[0] is not None and self.biases[0].shape[0] == self.Cout and self.biases[0].requires_grad:
-                ensure_grad(self.biases[0]).add_(self._bws[:self.Cout])
-            _zero_later(self._bws)
-            self._dirty = False
-            return
+                ensure_grad(self.biases[0]).add_(self._bias_ws.t[:self.Cout])
+            return self._zero_ws()
         off = 0
         for w, b in zip(self.weights, self.biases):
             n = w.shape[0]
@@ -1372,10 +1374,9 @@ class ConvParam:
             if w.requires_grad:
                 self._unpack(ensure_grad(w), n, off)
             if b is not None and b.shape[0] == n and b.requires_grad:      # (transposed conv: bias has Cout_t entries, handled by its op)
-                ensure_grad(b).add_(self._bws[off:off + n])
+                ensure_grad(b).add_(self._bias_ws.t[off:off + n])
             off += n
         self._zero_ws()
-        self._dirty = self._ws_used = False
 
 
 class S2DConvParam(ConvParam):
@@ -1402,9 +1403,8 @@ class S2DConvParam(ConvParam):
             self._unpack(g3, self.Cout, 0)
             ensure_grad(w).add_(s2d_weights_adjoint(g3, self.parent.Cin))
         if b is not None and b.requires_grad:
-            ensure_grad(b).add_(self._bws[:self.Cout])
+            ensure_grad(b).add_(self._bias_ws.t[:self.Cout])
         self._zero_ws()
-        self._dirty = self._ws_used = False
 
 
 class StateHalfConvParam(ConvParam):
@@ -1680,8 +1680,7 @@ def _folded_upsample_wgrad(x, skip, dy, y, cp, xpad=None):
             H.check(L.ramnet_pad2_sum_im2col(_p(x), _p(skip), _p(xpad), _p(a_rows), _p(a_cols), B, Hh, W, Cc, _st()), "ramnet_pad2_sum_im2col")
         else:
             H.check(L.ramnet_up2x_border_im2col(_p(x), _p(skip), _p(a_rows), _p(a_cols), B, Hh, W, Cc, _st()), "ramnet_up2x_border_im2col")
-        if _FOLD_WINO_WGRAD and Cc == cp.CinWs and ((Cc % 32 == 0 and cp.Cout % 64 == 0) or
-                                                                                 (Cc % 64 == 0 and cp.Cout % 32 == 0)):
+        if _FOLD_WINO_WGRAD and cp._fold_one_launch():
             # one launch, all four parities, in the Winograd F(2x2,4x4) or F(2x3,4x4) domain (csrc/conv_wgrad_wino24.hip)
             kind = "fold23" if _fold_wgrad_2x3(B, Hh, W, Cc, cp.Cout) else "fold24"
             wgrad_launch(xpad, Taps.get("fold", 4, 0, 0, 0), dy, cp.grad_ws_fold24(kind), cp.Cout, gmask=y, dbias=bws, Ho=Hh, Wo=W,
@@ -1691,7 +1690,7 @@ def _folded_upsample_wgrad(x, skip, dy, y, cp, xpad=None):
             for py in range(2):
                 for px in range(2):
                     wgrad_launch(xpad, Taps.get("fold", 4, 0, py, px), dy, wd, cp.Cout, gmask=y, dbias=bws, Ho=Hh, Wo=W,
-                                 gview=(2, 2, py, px, H2, W2), dw_off=(py * 2 + px) * S * 16 * cp.CinWs * cp.Cout)
+                                 gview=(2, 2, py, px, H2, W2), dw_off=(py * 2 + px) * S * cp._fold_slab_floats())
         g_rows = torch.empty(2, B * W2, 2 * cp.Cout, device=dev)
         g_cols = torch.empty(2, B * H2, 2 * cp.Cout, device=dev)
         H.check(L.ramnet_frame_gather(_p(dy), _p(y), _p(g_rows), _p(g_cols), B, H2, W2, cp.Cout, _st()), "ramnet_frame_gather")

@@ -23,7 +23,15 @@ SETTINGS = {
     "split_operands": _FORCE + [("set_split_operands", True, "_SPLIT_OPERANDS"), ("set_split_wgrad", True, "_SPLIT_WGRAD")],
     "winograd_off": [("set_winograd", False, "_WINOGRAD")],
     "frozen_weight": [],
+    # deterministic mode gives slabs to the direct, head and fold launches as well: with the decoders' one-launch form (F(2x2,4x4); at
+    # these map sizes F(2x3,4x4) only when forced) and as four direct parity launches.  set_deterministic goes last in, first out: the
+    # other switches refuse to change under it or it under them (ops.set_wgrad_slabs)
+    "deterministic": [("set_deterministic", True, "_DETERMINISTIC")],
+    "deterministic_fold_direct": [("set_fold_winograd_wgrad", False, "_FOLD_WINO_WGRAD"), ("set_deterministic", True, "_DETERMINISTIC")],
+    "deterministic_fold_2x3": [("set_fold_winograd_wgrad_2x3", "force", "_FOLD_WGRAD_2X3"), ("set_deterministic", True, "_DETERMINISTIC")],
+    "wgrad_atomic": [("set_wgrad_slabs", False, "_WGRAD_SLABS")],        # the tile splits meet in slab 0 by atomic adds; the joins still run
 }
+DETERMINISTIC = ("deterministic", "deterministic_fold_direct", "deterministic_fold_2x3")
 NETS = ("gru", "lstm", "unet")
 CASES = [(net, s) for s in SETTINGS for net in NETS if s != "frozen_weight" or net == "gru"]
 FROZEN = "resblocks.0.conv1.weight"          # a plain 3x3 layer: its bias still trains, the two share every launch
@@ -128,7 +136,7 @@ def run_case(net, setting, after_first_backward=None):
                             p.add_(p.grad, alpha=-1e-3)
     finally:
         _hip.set_tracer(None)
-        for (setter, _, _), value in zip(todo, prev):
+        for (setter, _, _), value in reversed(list(zip(todo, prev))):
             getattr(ops, setter)(value)
     return passes
 
@@ -144,6 +152,11 @@ def pack_kind(record):
 def wgrad_algo(record):
     name, args = record.split("|")
     return int(args.split("/")[0][5:]) if name == "ramnet_wgrad_launch" else None
+
+
+def wgrad_slabs(record):
+    name, args = record.split("|")
+    return int(args.split("/")[2][6:]) if name == "ramnet_wgrad_launch" else None
 
 
 def encode(traces):

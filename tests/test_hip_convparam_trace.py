@@ -42,6 +42,10 @@ def test_the_workload_reaches_every_pack_and_layout(golden):
     algos = {cases.wgrad_algo(r) for r in flat}
     for kind, algo in cases.LAYOUT_ALGOS.items():
         assert algo in algos, kind
+    # deterministic mode: the direct (0), head (2) and both fold launches (3: F(2x2,4x4), 7: F(2x3,4x4)) own slabs as well
+    det = [r for s in cases.DETERMINISTIC for net in cases.NETS for p in golden["%s/%s" % (net, s)] for r in p]
+    for algo in (0, 2, 3, 7):
+        assert any(cases.wgrad_algo(r) == algo and cases.wgrad_slabs(r) > 0 for r in det), algo
     # the frozen weight's unpack launch is gone from the fold, nothing else changes in the first pass
     frozen, trained = Counter(golden["gru/frozen_weight"][0]), Counter(golden["gru/defaults"][0])
     gone = list((trained - frozen).elements())

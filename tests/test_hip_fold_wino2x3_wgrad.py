@@ -101,11 +101,12 @@ def test_two_passes_accumulate(wgrad2x3):
     g = torch.randn(y.shape, device=dev())
     dw, db = _reference_grads(m, x, s, g)
     _one_pass(m, x, s, g)
-    ws = m._cp._ws_fold23
-    assert ws is not None and float(ws.abs().max()) == 0.0 and m._cp._ws_fold24 is None
+    recs = dict(m._cp.workspaces())
+    ws = recs["fold23"].t
+    assert ws is not None and float(ws.abs().max()) == 0.0 and recs["fold24"].t is None
     assert_close(m.conv2d.weight.grad.cpu().numpy(), dw.cpu().numpy(), TOL, "dW, one pass")
     _one_pass(m, x, s, g)
-    assert m._cp._ws_fold23 is ws
+    assert recs["fold23"].t is ws
     assert_close(m.conv2d.weight.grad.cpu().numpy(), 2 * dw.cpu().numpy(), TOL, "dW, two passes")
     assert_close(m.conv2d.bias.grad.cpu().numpy(), 2 * db.cpu().numpy(), TOL, "db, two passes")
     assert _ran_2x3(wgrad2x3)

@@ -39,16 +39,17 @@ def det_buffers():
     direct / head slabs beyond the default workspace, the bias slabs beyond one row, the partial buffers"""
     out = {"fold_slabs": 0, "fold_direct_slabs": 0, "direct_head_slabs": 0, "bias_slabs": 0, "partials": 0}
     for cp in [o for o in gc.get_objects() if isinstance(o, ops.ConvParam)]:
-        for t in (cp._ws_fold24, cp._ws_fold23):
-            if t is not None and ops._det_slabs(t) > 1:
-                out["fold_slabs"] += t.numel() * 4 * (ops._det_slabs(t) - 1) // ops._det_slabs(t)
-        if cp._ws_fold_det is not None:
-            out["fold_direct_slabs"] += cp._ws_fold_det.numel() * 4
-        if cp._ws is not None and ops._det_slabs(cp._ws) > 1:
-            out["direct_head_slabs"] += (ops._det_slabs(cp._ws) - 1) * cp._slab_floats("direct") * 4
-        if cp._bws is not None and cp._bws.numel() > cp.Cout and ops._det_slabs(cp._ws) + (cp._ws_fold_det is not None) + sum(
-                ops._det_slabs(t) for t in (cp._ws_fold24, cp._ws_fold23) if t is not None) > 0:
-            out["bias_slabs"] += (cp._bws.numel() - cp.Cout) * 4
+        ws = {name: r.t for name, r in cp.workspaces()}
+        det = {name: ops._det_slabs(t) for name, t in ws.items()}       # (the stamp of the last pass; 0 on a workspace never asked for)
+        for name in ("fold24", "fold23"):
+            if det[name] > 1:
+                out["fold_slabs"] += ws[name].numel() * 4 * (det[name] - 1) // det[name]
+        if ws["fold_direct"] is not None:
+            out["fold_direct_slabs"] += ws["fold_direct"].numel() * 4
+        if det["main"] > 1:
+            out["direct_head_slabs"] += (det["main"] - 1) * cp._slab_floats("direct") * 4
+        if ws["bias"] is not None and ws["bias"].numel() > cp.Cout and (ws["fold_direct"] is not None or det["main"] + det["fold24"] + det["fold23"] > 0):
+            out["bias_slabs"] += (ws["bias"].numel() - cp.Cout) * 4
         out["partials"] += sum(b.numel() * b.element_size() for b in cp._part.values())
     out["total"] = sum(out.values())
     return out

@@ -533,7 +533,8 @@ int ramnet_concat2(const float *a, int lda, int Ca, const float *b, int ldb, int
  * when base != NULL: the gradient of a feature that went through a layer chain at batch n x B and was consumed slice by slice (the n
  * state updates of a package) and, as a whole, by the next layer of the chain (ABI 19; `parts` = host array of n <= 8 device pointers). */
 int ramnet_cat_batch_add(const float *const *parts, int n, size_t npix, int C, int ld, const float *base, float *out, void *stream);
-/* The same with the ReLU mask of the feature itself applied to the sum (ABI 24): out = (cat(parts) [+ base]) * (mask > 0), mask [n * npix][C] dense = the
+/* The same with the ReLU mask of the feature itself applied to the sum (ABI 24): out = mask > 0 ? cat(parts) [+ base] : +0 (a SELECT, not a product:
+ * under a non-positive or NaN mask the output is +0 even where the sum is NaN or infinite), mask [n * npix][C] dense = the
  * feature (the output of a ConvLayer with ReLU, submodules.py:26-35).  The layer's backward-data / backward-weights launches then read the gradient as
  * ONE plain operand instead of (gradient, output) pairs through RAMNET_IN_RELUMASK / gmask: the same values, so bit-identical gradients. */
 int ramnet_cat_batch_add_masked(const float *const *parts, int n, size_t npix, int C, int ld, const float *base, const float *mask, float *out,
@@ -637,7 +638,8 @@ int ramnet_normalize_nonzero_ordered(float *grid, size_t n, double *stats, doubl
  *   exact == 0: affine_grid + grid_sample (bilinear, zeros, align_corners=False) in fp32 with the normalised coordinates bx [W] and
  *               by [H] (device; torch's linspace(-1, 1, n) * (n - 1) / n); taps outside the image are skipped.
  * stats (optional, [G][3] doubles of the entry above): a source value v is read as v != 0 ? (v - mean) / std : 0 — the nonzero
- * normalisation of the FULL grid, fused in front of the transform; degenerate statistics leave values unchanged.
+ * normalisation of the FULL grid, fused in front of the transform; degenerate statistics (no nonzero value, or a single distinct one: the fp32
+ * variance, formed unfused as by ramnet_normalize_nonzero_batch, is not positive) leave values unchanged.
  * nhwc = 0: dst [C][th][tw]; nhwc = 1: [th][tw][Cpad], channels zero-padded (the model's input layout; Cpad % 4 == 0).
  * win_host (optional): a HOST copy of win; when given, every window is checked against the image before anything is launched.  The
  * kernel itself clamps top / left into the image.  G = 0 is a no-op.                                                              */
@@ -744,7 +746,8 @@ int ramnet_resize_metric_target(const float *const *target, int G, int H, int W,
  *   (up[g] + *up_sum) * w_g * gain * sum_s (Bg * 2 / C_s / num_scales) / 4^s * dP_s[Y >> s, X >> s]: a gather — every workgroup re-stages
  *   its tile with a 16-pixel halo, rebuilds the pyramid and the signs of the Sobel components in LDS and applies the transposed stencil
  *   (replicate padding: a clamped tap lands on the edge cell) in integer arithmetic.  up (device [G]) / up_sum (device scalar): upstream
- *   gradients of loss[g] / of wsum, either may be NULL.  A scale with C_s = 0 contributes nothing; pixels under a NaN target get 0.
+ *   gradients of loss[g] / of wsum, either may be NULL.  A scale with C_s = 0 contributes nothing; pixels under a NaN target, and
+ *   cropped rows / columns that no scale reaches, get +0 whatever the sign of the upstream gradient.
  * The pointer-table entry writes n pointers of a HOST array to a device table by kernel argument (no host buffer has to outlive the
  * call: usable inside a stream capture).                                                                                             */
 int ramnet_fill_pointer_table(const void **table, const void *const *host_ptrs, int n, void *stream);

@@ -29,7 +29,11 @@ struct aug_norm {
     float mean, sd;
 };
 
+// The variance is formed as in normalize_nonzero_batch_kernel, product and difference each rounded: a fused ms - mean * mean leaves the
+// rounding error of mean^2 behind as the "variance" of a grid with a single distinct nonzero value (0.2f: positive), and such a grid
+// would be normalised to zeros here while the stand-alone kernel leaves it unchanged.
 __device__ __forceinline__ aug_norm aug_norm_of(const double *stats, int g) {
+#pragma clang fp contract(off)
     aug_norm n = {0, 0.f, 1.f};
     if (stats == nullptr) return n;
     const double cnt = stats[3 * g + 2];

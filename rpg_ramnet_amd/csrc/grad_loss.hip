@@ -278,7 +278,7 @@ __global__ void __launch_bounds__(GL_NT) gl_bwd_kernel(const float *const *__res
             d += D[DOFF[1] + (ly >> 1) * 32 + (x >> 1)];
             d += D[DOFF[2] + (ly >> 2) * 16 + (x >> 2)];
             d += D[DOFF[3] + (ly >> 3) * 8 + (x >> 3)];
-            r[j] = d;
+            r[j] = d + 0.f;           // a negative coefficient times 0 is -0 at every scale: a pixel that nothing reaches gets +0 whatever the sign of `up`
         }
         float *o = out + (size_t)Y * W + X;
         if (vout) {

@@ -1,4 +1,4 @@
-"""The guarded call of the direct kernel tests (tests/test_hip_pointwise.py, tests/test_hip_reductions.py, tests/test_hip_conv_launch.py, tests/test_hip_voxel_launch.py): device buffers between
+"""The guarded call of the direct kernel tests (tests/test_hip_pointwise.py, tests/test_hip_reductions.py, tests/test_hip_conv_launch.py, tests/test_hip_voxel_launch.py, tests/test_hip_grad_loss_launch.py, tests/test_hip_augment_launch.py): device buffers between
 sentinel / NaN guards, the one way to an entry point of the C ABI, and the comparison rules of profiles/pointwise_tests_notes.md §1.
 
 `dtype`: float32 (default), float64 (`stats`, `part`, `mean`, `rstd`) or int64 (`num_batches_tracked`), guards and gaps in that dtype.
@@ -90,6 +90,22 @@ class Out:
             keep[:, self.col0:self.col0 + self.cols] = False
         assert torch.equal(got[off:off + n].view(self.rows, self.ld)[keep], ref[off:off + n].view(self.rows, self.ld)[keep]), \
             "%s wrote into the gap of a pitched output" % what if not untouched and not self.frozen else "%s changed a frozen buffer" % what if not untouched else "%s launched although it refused its arguments" % what
+
+
+def pointer_table(bufs, through_kernel=False, tail=0):
+    """A device table of device pointers (`bufs`: In / Out objects or raw addresses) as a frozen int64 Out between sentinel guards: every
+    later launch through `call` must leave it, its `tail` spare entries and its guards as they are.  Written by a host copy, or
+    (through_kernel) by ramnet_fill_pointer_table."""
+    ptrs = [b.ptr if isinstance(b, (In, Out)) else int(b) for b in bufs]
+    if through_kernel:
+        tab = Out(1, len(ptrs) + tail, dtype=torch.int64)
+        call("ramnet_fill_pointer_table", tab, (C.c_void_p * max(len(ptrs), 1))(*ptrs), len(ptrs))
+        got = tab.value().view(-1)
+        assert got[:len(ptrs)].tolist() == ptrs and bool((got[len(ptrs):] == SENT_INT).all()), "ramnet_fill_pointer_table: the table is not the host array"
+        return tab.freeze()
+    pre = torch.full((len(ptrs) + tail,), SENT_INT, dtype=torch.int64)
+    pre[:len(ptrs)] = torch.tensor(ptrs, dtype=torch.int64)
+    return Out(1, len(ptrs) + tail, dtype=torch.int64, prefill=pre).freeze()
 
 
 def call(name, *args, rc=0, stream=None, defer=False):

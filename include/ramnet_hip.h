@@ -215,6 +215,9 @@ typedef struct ramnet_wgrad_desc {
  * before sizing the scratch.
  * "ordered_only" (0; 1: ramnet_si_loss_fwd / ramnet_si_log_loss_fwd refuse — RAMNET_E_BADARG, nothing launched — instead of taking their
  * zero-fill + atomics form when the fixed-order one-launch form has no library scratch: inside a stream capture, after a failed allocation).
+ * "fold_half_wg" (2 = auto: RAMNET_ALGO_WINOGRAD24_2X3 launches as half workgroups — 4 waves, 16 tiles, two per CU, same outputs bit for
+ * bit — where ramnet_fold_halfwg_variant's rule picks them: batch >= 2 and more than 512 half workgroups; 0: never, 1: every such launch;
+ * the measurements behind the default are in profiles/fold23_halfwg_notes.md).
  * ramnet_get_option: -1 if unknown.  */
 int ramnet_set_option(const char *name, int value);
 int ramnet_get_option(const char *name);
@@ -343,6 +346,14 @@ int ramnet_pack_border_weights(const float *w_oihw, float *rows, float *cols, fl
  * (6 G)(4 FA) w (4 FA)^T (6 G | 3 Gc)^T with integer matrices (sums in double) and divide once by 576 | 288; ramnet_fold_unpack_wgrad[2x3] folds
  * the same way (double, one division by 576).                                                                                           */
 int ramnet_fold_wino_variant(const ramnet_conv_desc *d, int force);
+/* Half-workgroup form of the RAMNET_ALGO_WINOGRAD24_2X3 launches (addition to ABI 27; csrc/conv_wino24.hip, HALF): one 16-tile group on four
+ * waves and 61 KB of LDS, two workgroups per CU, bit-identical outputs.  ramnet_fold_halfwg_variant: will the launch of d (algo =
+ * RAMNET_ALGO_WINOGRAD24_2X3) run that form?  0 for every other algorithm, for 32-column workgroups and with a split workspace; force != 0:
+ * every structurally eligible launch, else what ramnet_set_option("fold_half_wg") selects.  Quiet (ramnet_last_error untouched).
+ * ramnet_fold_halfwg_grid: outputs per tile block (rows x columns) and workgroups of the launch of an eligible d as 16-tile (half != 0) or
+ * 32-tile blocks.                                                                                                                         */
+int ramnet_fold_halfwg_variant(const ramnet_conv_desc *d, int force);
+int ramnet_fold_halfwg_grid(const ramnet_conv_desc *d, int half, int *block_rows, int *block_cols, long *workgroups);
 size_t ramnet_packed_weight_elems_fold_wino2x3(int Cout, int Cin);
 int ramnet_pack_weight_fold_wino2x3(const float *w_oihw, float *wp, int Cout, int Cin, void *stream);
 int ramnet_pack_weight_fold_wino2x3_dgrad(const float *w_oihw, float *wp, int Cout, int Cin, void *stream);

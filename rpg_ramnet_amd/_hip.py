@@ -109,6 +109,8 @@ _SIGS = {
     "ramnet_pack_weight_fold_wino": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp]),
     "ramnet_pack_weight_fold_wino_dgrad": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp]),
     "ramnet_fold_wino_variant": (C.c_int, [C.POINTER(ConvDesc), C.c_int]),
+    "ramnet_fold_halfwg_variant": (C.c_int, [C.POINTER(ConvDesc), C.c_int]),
+    "ramnet_fold_halfwg_grid": (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_long)]),
     "ramnet_packed_weight_elems_fold_wino2x3": (C.c_size_t, [C.c_int, C.c_int]),
     "ramnet_pack_weight_fold_wino2x3": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp]),
     "ramnet_pack_weight_fold_wino2x3_dgrad": (C.c_int, [_fp, _fp, C.c_int, C.c_int, _fp]),

@@ -10,7 +10,7 @@
 // input channels every thread loads the 5x5 window of ONE (tile, channel) straight from global memory (the padded input needs
 // no bounds logic), transforms it in registers and writes the 25 values to V[25][32 tiles][16] in LDS (double-buffered, one
 // barrier per chunk).  Wave (tile half, channel quarter) accumulates all 25 positions of its 16 tiles x 16 channels on
-// v_mfma_f32_16x16x4_f32 (100 accumulator VGPRs): A = one 16-byte LDS read per position (swizzled, conflict-free), B = one
+// v_mfma_f32_16x16x4_f32 (100 accumulator VGPRs): A = one 16-byte LDS read per position (swizzled: 2-way, tools/check_fold23_lds_swizzle.py), B = one
 // 16-byte global (L2) read per position from weights packed in exactly that lane order.  Loads and the transform of chunk
 // i+1 are issued between the MFMAs of chunk i.  The output transform is register-local; bias / ReLU and the border
 // corrections of the folded layer (ramnet_conv_desc.frame) are applied by the shared epilogue.
@@ -19,6 +19,7 @@
 // transform, columns take the 6-point F(3,4) one (points 0, 1, -1, 1/2, -1/2, inf): a 5 x 6 window, 30 positions (15 pairs,
 // 120 accumulator VGPRs), 5.0 multiplies per output instead of 6.25 — 20 % fewer MFMAs and window loads per output.  V holds 30
 // positions (2 x 61.4 KB).  Training-batch launches only (ramnet_fold_wino_variant): no split reduction.
+// HALF: the F(2x3) launches as workgroups of ONE 16-tile group (4 waves, 2 x 30.7 KB, two per CU; ramnet_fold_halfwg_variant).
 #include <stdlib.h>
 #include "common.hpp"
 #include "conv_plan.hpp"
@@ -75,22 +76,28 @@ struct Wino24Params {
 // the workgroup's 64 columns are (px, 32 channels): the input transform (25 loads + ~160 VALU per tile and channel, the cost that
 // bounds this kernel at 32 output channels: 35 % MFMA-busy) feeds twice the MFMAs.  NCQ = 4 geometry, chunks of 16.
 // TW = output columns per tile: 2 = F(2x2, 4x4), 3 = F(2x3, 4x4) (NCQ = 4 only; window 5 x (TW + 3), NP = 5 (TW + 3) positions).
-template <int NCQ, bool DG, int TXW, bool PAIR = false, int TW = 2>
-__global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_desc p, const Wino24Params q) {
+// HALF (F(2x3) only): ONE 16-tile group per workgroup — 4 waves (one per channel quarter) on 256 threads, V planes of 256 floats per position
+// (2 x 30.7 KB), two workgroups per CU.  Per wave the instruction stream is the 8-wave kernel's: the same tiles' arithmetic, chunk order and
+// MFMA order (bit-identical outputs); a 61 KB workgroup can share a CU with a workgroup of another kernel where the 123 KB one holds it alone.
+template <int NCQ, bool DG, int TXW, bool PAIR = false, int TW = 2, bool HALF = false>
+__global__ void __launch_bounds__(HALF ? 256 : 512, HALF ? 2 : 1) conv_wino24_kernel(const ramnet_conv_desc p, const Wino24Params q) {
     static_assert(!PAIR || (NCQ == 4 && !DG), "pair mode: forward, 64-column workgroups");
     static_assert(TW == 2 || (TW == 3 && NCQ == 4), "F(2x3): 64-column workgroups");
+    static_assert(!HALF || TW == 3, "half workgroups: F(2x3) only");
+    constexpr int NTG = HALF ? 1 : 2;                 // 16-tile groups per workgroup (NCQ = 4)
+    constexpr int PS = HALF ? W24_PS / 2 : W24_PS;    // floats per position in V
     constexpr int WC = TW + 3, NP = 5 * WC;           // window columns, Winograd positions
-    constexpr int VSZ = NP * W24_PS;                  // floats per V buffer
+    constexpr int VSZ = NP * PS;                      // floats per V buffer
     constexpr int W24_K = NCQ == 4 ? 16 : 8;          // input channels per chunk
-    constexpr int W24_TX = TXW, W24_TY = (NCQ == 4 ? 32 : 64) / TXW;      // tile columns / rows per workgroup
+    constexpr int W24_TX = TXW, W24_TY = (NCQ == 4 ? 16 * NTG : 64) / TXW;      // tile columns / rows per workgroup
     constexpr int VEC = W24_K / 4;                    // floats per lane and operand read (k = VEC*ks + j)
     constexpr int W24_U = NP * NCQ * 64 * VEC;        // packed weights of one (class, chunk, channel block)
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float *V = smem;                               // [2][NP][32][16]
+    float *V = smem;                               // [2][NP][32 (HALF: 16)][16]
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, ks = lane >> 4;
-    const int th = NCQ == 4 ? wave & 1 : wave & 3, cq = NCQ == 4 ? wave >> 1 : wave >> 2;       // 16-tile group, 16-channel group
+    const int th = HALF ? 0 : NCQ == 4 ? wave & 1 : wave & 3, cq = HALF ? wave : NCQ == 4 ? wave >> 1 : wave >> 2;       // 16-tile group, 16-channel group
 
     // blockIdx.x = ((tile block * nblk + channel block) * 4 + class): the four parities of a tile block read the same input
     int bid = blockIdx.x;
@@ -177,24 +184,24 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
     };
     // F(2x3): vbuf = the lane's first element of the buffer (V + vdst or V + dbuf1 below)
     auto tr_row = [&](float *vbuf, int i) {
-        float *dst = TW == 2 ? vbuf + (i * WC) * W24_PS + vdst : vbuf + (i * WC) * W24_PS;
+        float *dst = TW == 2 ? vbuf + (i * WC) * PS + vdst : vbuf + (i * WC) * PS;
         if constexpr (TW == 2) {
             const float d0 = raw[i * 5], d1 = raw[i * 5 + 1], d2 = raw[i * 5 + 2], d3 = raw[i * 5 + 3], d4 = raw[i * 5 + 4];
-            dst[0 * W24_PS] = 2.f * (d0 - d2) - d1 + d3;
-            dst[1 * W24_PS] = d3 - d2 - 2.f * d1;
-            dst[2 * W24_PS] = 2.f * d1 - 3.f * d2 + d3;
-            dst[3 * W24_PS] = d3 - d1;
-            dst[4 * W24_PS] = 2.f * (d1 - d3) - d2 + d4;
+            dst[0 * PS] = 2.f * (d0 - d2) - d1 + d3;
+            dst[1 * PS] = d3 - d2 - 2.f * d1;
+            dst[2 * PS] = 2.f * d1 - 3.f * d2 + d3;
+            dst[3 * PS] = d3 - d1;
+            dst[4 * PS] = 2.f * (d1 - d3) - d2 + d4;
         } else {
             // F(3,4) columns, B^T = [1/4 0 -5/4 0 1 0; 0 -1/4 -1/4 1 1 0; 0 1/4 -1/4 -1 1 0; 0 -1/2 -1 1/2 1 0; 0 1/2 -1 -1/2 1 0; 0 1/4 0 -5/4 0 1]
             const float d0 = raw[i * 6], d1 = raw[i * 6 + 1], d2 = raw[i * 6 + 2], d3 = raw[i * 6 + 3], d4 = raw[i * 6 + 4], d5 = raw[i * 6 + 5];
             const float u = d3 - d1, v = d4 - d2;
-            dst[0 * W24_PS] = fmaf(-1.25f, d2, fmaf(0.25f, d0, d4));
-            dst[1 * W24_PS] = fmaf(-0.25f, d1 + d2, d3 + d4);
-            dst[2 * W24_PS] = fmaf(0.25f, d1 - d2, d4 - d3);
-            dst[3 * W24_PS] = fmaf(0.5f, u, v);
-            dst[4 * W24_PS] = fmaf(-0.5f, u, v);
-            dst[5 * W24_PS] = fmaf(-1.25f, d3, fmaf(0.25f, d1, d5));
+            dst[0 * PS] = fmaf(-1.25f, d2, fmaf(0.25f, d0, d4));
+            dst[1 * PS] = fmaf(-0.25f, d1 + d2, d3 + d4);
+            dst[2 * PS] = fmaf(0.25f, d1 - d2, d4 - d3);
+            dst[3 * PS] = fmaf(0.5f, u, v);
+            dst[4 * PS] = fmaf(-0.5f, u, v);
+            dst[5 * PS] = fmaf(-1.25f, d3, fmaf(0.25f, d1, d5));
         }
     };
 
@@ -256,8 +263,8 @@ __global__ void __launch_bounds__(512, 1) conv_wino24_kernel(const ramnet_conv_d
             const float *vb = V + half * VSZ;
             float *vn = TW == 2 ? V + (half ^ 1) * VSZ : V + (half ? vdst : dbuf1);
             auto lda = [&](int pos) {
-                if constexpr (TW == 2) return ldv(vb + pos * W24_PS + aoff);
-                else return ldv(V + (half ? abuf1 : aoff) + pos * W24_PS);
+                if constexpr (TW == 2) return ldv(vb + pos * PS + aoff);
+                else return ldv(V + (half ? abuf1 : aoff) + pos * PS);
             };
             // The window of chunk+1 is already in registers (loaded at the end of the previous phase: a weight load issued
             // after it can only be consumed once it has landed, and there it has a barrier and four position pairs to do so);
@@ -506,15 +513,75 @@ static long wino23_tile(int Ho, int Wt, int &tx) {
     return best;
 }
 
-template <bool DG, bool PAIR>
+// The same for the half-workgroup form (conv_wino24_kernel<.., HALF = true>): 16 tiles as 8 x 12 (TX 4), 16 x 6 (TX 2), 4 x 24 (TX 8) or
+// 2 x 48 (TX 16) outputs.  Every 32-tile block above is two of these side by side or on top of each other, so the padded area is never
+// larger than wino23_tile's on the same map.
+static long wino23_tile_half(int Ho, int Wt, int &tx) {
+    const int shapes[4] = {4, 2, 8, 16};
+    long best = -1;
+    for (int s = 0; s < 4; ++s) {
+        const int t = shapes[s], th = 2 * (16 / t), tw = 3 * t;
+        const long a = (long)cdiv(Ho, th) * th * cdiv(Wt, tw) * tw;
+        if (best < 0 || a < best) best = a, tx = t;
+    }
+    return best;
+}
+
+// Does this RAMNET_ALGO_WINOGRAD24_2X3 launch run as half workgroups (4 waves, 16 tiles, two per CU)?  Structurally: every launch the
+// F(2x3) launcher accepts (64-column workgroups — NCQ = 4, the pair form included —, no split reduction).  force = 0 follows
+// ramnet_set_option("fold_half_wg"): 0 = never, 1 = every eligible launch, 2 = auto (fold_halfwg_auto below).
+static bool fold_halfwg_auto(const ramnet_conv_desc &d);
+static int fold_halfwg_variant(const ramnet_conv_desc &d, int force) {
+    if (d.algo != RAMNET_ALGO_WINOGRAD24_2X3 || d.stride != 1 || d.splitk_ws != nullptr) return 0;
+    if (d.in_mode == RAMNET_IN_PARITY4) {
+        if (d.C0 % 16 != 0 || d.Cout % 64 != 0) return 0;
+    } else if (d.in_mode == RAMNET_IN_PLAIN) {
+        const bool wide = fold_wino_pair(d.Cout, d.C0) || (d.Cout % 64 == 0 && d.C0 % 16 == 0);
+        if (!wide || d.C0 % 32 != 0 || d.Ho < 2 || d.Wo < 2) return 0;
+    } else {
+        return 0;
+    }
+    const int mode = force ? 1 : g_opt_fold_half_wg;
+    return mode == 1 ? 1 : mode == 2 ? (int)fold_halfwg_auto(d) : 0;
+}
+
+// Tile block and grid of an F(2x3) launch (the launchers below and ramnet_fold_halfwg_grid): tx = tile columns of a block, 16 or 32 tiles
+struct Wino23Grid {
+    int tx, rows, cols, tiles_x, tiles_y;           // block = rows x cols outputs; blocks over the (Ho, Wt) map
+    long wgs;                                       // workgroups = blocks x batch x 64-column channel blocks x parity classes
+};
+static Wino23Grid wino23_grid(const ramnet_conv_desc &d, bool half) {
+    const bool dg = d.in_mode == RAMNET_IN_PARITY4, pair = !dg && fold_wino_pair(d.Cout, d.C0);
+    // pair: column parity 1 is tiled with its origins one column to the left, so the tiles cover Wo + 1 columns
+    const int Wt = pair ? d.Wo + 1 : d.Wo, ntiles = half ? 16 : 32;
+    Wino23Grid g;
+    if (half) wino23_tile_half(d.Ho, Wt, g.tx);
+    else wino23_tile(d.Ho, Wt, g.tx);
+    g.rows = 2 * (ntiles / g.tx), g.cols = 3 * g.tx;
+    g.tiles_x = cdiv(Wt, g.cols), g.tiles_y = cdiv(d.Ho, g.rows);
+    g.wgs = (long)g.tiles_x * g.tiles_y * d.B * (pair ? 1 : d.Cout / 64) * (dg ? 1 : pair ? 2 : 4);
+    return g;
+}
+
+// auto: batch >= 2 and more half workgroups than the 512 that are resident at once (two on each of 256 CUs).  Isolated sweep of the three
+// decoder layers, forward / pair / backward-data, batch 1-32 (tools/bench_fold23_halfwg.py, profiles/fold23_halfwg_sweep.jsonl): every such
+// launch measured as fast or faster (forward 1.00-1.11, backward-data 1.04-1.46); the five launches that measured slower (0.97-0.995) all have
+// 257-512 half workgroups — one resident round either way, the CUs' MFMA pipes shared by two workgroups instead of held by one.  Launches of
+// at most 256 half workgroups measured 1.5-1.8 x faster (twice the CUs busy); they are batch 1-2 launches, which the callers run on F(2x2)
+// with a split reduction, and stay on the 8-wave kernels.
+static bool fold_halfwg_auto(const ramnet_conv_desc &d) { return d.B >= 2 && wino23_grid(d, true).wgs > 512; }
+
+template <bool DG, bool PAIR, bool HALF = false>
 static int launch_wino23(int tx, dim3 grid, size_t lds, const ramnet_conv_desc &d, const Wino24Params &q, hipStream_t st) {
 #define W23_GO(T)                                                                                                         \
     if (tx == T) {                                                                                                        \
-        RAMNET_FULL_LDS((conv_wino24_kernel<4, DG, T, PAIR, 3>));                                                           \
-        note_kernel("conv_wino24_kernel<4,%d,%d,%d,3>", (int)DG, T, (int)PAIR);                                            \
-        hipLaunchKernelGGL((conv_wino24_kernel<4, DG, T, PAIR, 3>), grid, dim3(512), lds, st, d, q);                        \
+        RAMNET_FULL_LDS((conv_wino24_kernel<4, DG, T, PAIR, 3, HALF>));                                                     \
+        if (HALF) note_kernel("conv_wino24_kernel<4,%d,%d,%d,3,1>", (int)DG, T, (int)PAIR);                                \
+        else note_kernel("conv_wino24_kernel<4,%d,%d,%d,3>", (int)DG, T, (int)PAIR);                                       \
+        hipLaunchKernelGGL((conv_wino24_kernel<4, DG, T, PAIR, 3, HALF>), grid, dim3(HALF ? 256 : 512), lds, st, d, q);     \
     }
     W23_GO(2) W23_GO(4) W23_GO(16)
+    if constexpr (HALF) W23_GO(8)
 #undef W23_GO
     RAMNET_LAUNCH_CHECK();
     return 0;
@@ -534,10 +601,11 @@ static int launch_wino24_dgrad(const ramnet_conv_desc &d, hipStream_t st) {
     RAMNET_CHECK_ARG(xb < 0x40000000ull && wb < 0x7fffffffull);          // invalid window elements use offsets >= 2^30
     q.xbytes = (unsigned)xb, q.wbytes = (unsigned)wb;
     if (w23) {
-        int tx;
-        wino23_tile(d.Ho, d.Wo, tx);
-        q.tiles_x = cdiv(d.Wo, 3 * tx), q.tiles_y = cdiv(d.Ho, 64 / tx);
-        return launch_wino23<true, false>(tx, dim3((unsigned)(q.tiles_x * q.tiles_y * d.B * q.nblk)), (size_t)2 * W23_V * sizeof(float), d, q, st);
+        const bool half = fold_halfwg_variant(d, 0);
+        const Wino23Grid g = wino23_grid(d, half);
+        q.tiles_x = g.tiles_x, q.tiles_y = g.tiles_y;
+        if (half) return launch_wino23<true, false, true>(g.tx, dim3((unsigned)g.wgs), (size_t)W23_V * sizeof(float), d, q, st);
+        return launch_wino23<true, false>(g.tx, dim3((unsigned)g.wgs), (size_t)2 * W23_V * sizeof(float), d, q, st);
     }
     // 16 x 8 or 8 x 16 output pixels per workgroup: whichever covers the grid with fewer workgroups
     const bool flat = cdiv(d.Wo, 16) * cdiv(d.Ho, 8) < cdiv(d.Wo, 8) * cdiv(d.Ho, 16);
@@ -639,14 +707,17 @@ int launch_wino24(const ramnet_conv_desc &d, hipStream_t st) {
     RAMNET_CHECK_ARG(xb < 0xffffffffull && wb < 0x7fffffffull);
     q.xbytes = (unsigned)xb, q.wbytes = (unsigned)wb;
     if (w23) {
-        // pair: column parity 1 is tiled with its origins one column to the left, so the tiles cover Wo + 1 columns
-        int tx;
-        wino23_tile(d.Ho, pair ? d.Wo + 1 : d.Wo, tx);
-        q.tiles_x = cdiv(pair ? d.Wo + 1 : d.Wo, 3 * tx), q.tiles_y = cdiv(d.Ho, 64 / tx);
         q.ksplit = 1, q.ws = nullptr, q.cnt = nullptr;
-        const dim3 grid((unsigned)(q.tiles_x * q.tiles_y * d.B * q.nblk * (pair ? 2 : 4)));
+        const bool half = fold_halfwg_variant(d, 0);
+        const Wino23Grid g = wino23_grid(d, half);
+        q.tiles_x = g.tiles_x, q.tiles_y = g.tiles_y;
+        const dim3 grid((unsigned)g.wgs);
+        if (half) {
+            const size_t lds = (size_t)W23_V * sizeof(float);
+            return pair ? launch_wino23<false, true, true>(g.tx, grid, lds, d, q, st) : launch_wino23<false, false, true>(g.tx, grid, lds, d, q, st);
+        }
         const size_t lds = (size_t)2 * W23_V * sizeof(float);
-        return pair ? launch_wino23<false, true>(tx, grid, lds, d, q, st) : launch_wino23<false, false>(tx, grid, lds, d, q, st);
+        return pair ? launch_wino23<false, true>(g.tx, grid, lds, d, q, st) : launch_wino23<false, false>(g.tx, grid, lds, d, q, st);
     }
     const int Wt = pair ? d.Wo + 2 : d.Wo;                     // pair: one more tile column (the shifted tiling of column parity 1)
     const bool flat = wide && cdiv(Wt, 16) * cdiv(d.Ho, 8) < cdiv(Wt, 8) * cdiv(d.Ho, 16);      // 8 x 16 instead of 16 x 8 pixels
@@ -841,6 +912,15 @@ extern "C" int ramnet_pack_weight_fold_wino2x3_dgrad(const float *w, float *wp, 
 }
 
 extern "C" int ramnet_fold_wino_variant(const ramnet_conv_desc *d, int force) { return d ? fold_wino_variant(*d, force) : 0; }
+
+extern "C" int ramnet_fold_halfwg_variant(const ramnet_conv_desc *d, int force) { return d ? fold_halfwg_variant(*d, force) : 0; }
+
+extern "C" int ramnet_fold_halfwg_grid(const ramnet_conv_desc *d, int half, int *block_rows, int *block_cols, long *workgroups) {
+    RAMNET_CHECK_ARG(d && block_rows && block_cols && workgroups && fold_halfwg_variant(*d, 1));
+    const Wino23Grid g = wino23_grid(*d, half != 0);
+    *block_rows = g.rows, *block_cols = g.cols, *workgroups = g.wgs;
+    return 0;
+}
 
 extern "C" int ramnet_pack_border_weights(const float *w, float *rows, float *cols, float *rows_t, float *cols_t, int Cout, int Cin, void *stream) {
     RAMNET_CHECK_ARG(w && rows && cols && rows_t && cols_t && Cout > 0 && Cin > 0);

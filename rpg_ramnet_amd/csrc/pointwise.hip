@@ -1056,7 +1056,7 @@ extern "C" int ramnet_abi_version(void) { return RAMNET_ABI_VERSION; }
 
 // Process-wide A/B options (tests and tuning runs; the environment variables they replace are gone since round 4)
 namespace ramnet {
-int g_opt_voxel_sorted = 1, g_opt_fold_pair = 1, g_opt_wgrad_blocks = 512, g_opt_wgrad_wino_blocks = 384, g_opt_wino_ksplit = 1, g_opt_wgrad_wino_nf = 1, g_opt_pred_si_cap = 256, g_opt_pred_si_bwd_cap = 1024, g_opt_ordered_only = 0;
+int g_opt_voxel_sorted = 1, g_opt_fold_pair = 1, g_opt_wgrad_blocks = 512, g_opt_wgrad_wino_blocks = 384, g_opt_wino_ksplit = 1, g_opt_wgrad_wino_nf = 1, g_opt_pred_si_cap = 256, g_opt_pred_si_bwd_cap = 1024, g_opt_ordered_only = 0, g_opt_fold_half_wg = 2;
 }
 extern "C" int ramnet_set_option(const char *name, int value) {
     RAMNET_CHECK_ARG(name != nullptr);
@@ -1069,6 +1069,7 @@ extern "C" int ramnet_set_option(const char *name, int value) {
     else if (!strcmp(name, "pred_si_bwd_cap")) { RAMNET_CHECK_ARG(value >= 8 && value <= 65536); ramnet::g_opt_pred_si_bwd_cap = value; }
     else if (!strcmp(name, "pred_si_cap")) { RAMNET_CHECK_ARG(value >= 8 && value <= 65536); ramnet::g_opt_pred_si_cap = value; }
     else if (!strcmp(name, "ordered_only")) ramnet::g_opt_ordered_only = value != 0;
+    else if (!strcmp(name, "fold_half_wg")) { RAMNET_CHECK_ARG(value >= 0 && value <= 2); ramnet::g_opt_fold_half_wg = value; }
     else RAMNET_CHECK_ARG(!"ramnet_set_option: unknown option");
     return 0;
 }
@@ -1083,6 +1084,7 @@ extern "C" int ramnet_get_option(const char *name) {
     if (!strcmp(name, "pred_si_bwd_cap")) return ramnet::g_opt_pred_si_bwd_cap;
     if (!strcmp(name, "pred_si_cap")) return ramnet::g_opt_pred_si_cap;
     if (!strcmp(name, "ordered_only")) return ramnet::g_opt_ordered_only;
+    if (!strcmp(name, "fold_half_wg")) return ramnet::g_opt_fold_half_wg;
     return -1;
 }
 

@@ -226,6 +226,13 @@ def set_fold_winograd_2x3(mode):
     _FOLD_2X3 = mode
 
 
+def set_fold_half_wg(mode):
+    """F(2x3,4x4) forward / backward-data launches of the folded decoders as half workgroups (conv_wino24_kernel<.., HALF>: 4 waves,
+    16 tiles, two workgroups per CU; same outputs bit for bit): "auto" (default) = where the library's rule picks it
+    (ramnet_fold_halfwg_variant: the training-batch launches), "off" = the 8-wave workgroups everywhere, "force" = every such launch.  The library decides per launch; graphs captured before the call keep what they captured."""
+    H.check(H.lib().ramnet_set_option(b"fold_half_wg", {"off": 0, "force": 1, "auto": 2}[mode]), "set_option")
+
+
 _FOLD_WGRAD_2X3 = "auto"
 _FOLD_WGRAD_VARIANT = {}
 

@@ -6,6 +6,7 @@ kernel into per-layer [tap][Cin][Cout] workspaces over ALL time steps of a BPTT 
 ``param.grad`` (OIHW) once, by a callback queued on the autograd engine (the reference gets the same sums from
 autograd's per-use accumulation, lstm_trainer.py:450).
 """
+import collections
 import contextlib
 import ctypes as C
 import os as _os
@@ -16,183 +17,334 @@ from torch.autograd import Function
 from . import _hip as H
 
 _NULL = None
-_ABL_SKIP_WGRAD = _os.environ.get("RAMNET_ABL_SKIP_WGRAD") == "1"
-if _ABL_SKIP_WGRAD:
-    import warnings as _warnings
-    _warnings.warn("RAMNET_ABL_SKIP_WGRAD=1: backward-weights launches are SKIPPED — every weight gradient of this process is zero "
-                   "(tuning runs only; unset the variable for anything else)", RuntimeWarning)
 
-# 3x3 stride-1 layers (ConvGRU gates / candidate, residual blocks) run Winograd F(2x2,3x3) in fp32 — 2.25x fewer
-# multiplies, rounding error ~1e-6 relative (tests/test_hip_ops.py) — unless switched off (RAMNET_WINOGRAD=0).
-_WINOGRAD = True
-_WINO_MIN_CIN = 32        # smallest reduction depth that uses the Winograd kernels
+# ------------------------------------------------------------------------------------------------ switches
+# Every kernel-selection and schedule switch of this module is one row of _SWITCHES, name -> _Switch:
+#   var          the module global that holds the value — the hot path reads it as a plain global (ops._WINOGRAD, ...); None: the library
+#                holds the value (ramnet_get_option)
+#   default      the value without the environment
+#   domain       bool | int | range(...) | tuple of mode strings; set through bool() / int() / an assertion
+#   doc          what the switch selects and the measurements behind its default; the docstring of its set_<name>
+#   env          environment variable that supplies the initial value (tuning runs only): "0" switches a default-on row off, "1" a
+#                default-off row on, anything else leaves the default
+#   key          the value is part of the launch-descriptor keys (_SWITCH_KEY: _conv_desc, wgrad_launch) — a row that changes what a
+#                descriptor holds has key=True or invalidates, or a cached descriptor launches the old kernel
+#   invalidates  functions of this module called after a change (invalidate_packs / invalidate_descs)
+#   lib          (ramnet_set_option name, {value: option value} or None for the value itself) that follows every change
+#   guards       ((refused bool(value), other row, value of the other row, RuntimeError text), ...) checked in order before a change
+#   setter       set_<name>(value) is generated below (False: a second argument of a hand-written setter, or set by env / switches() alone)
+_Switch = collections.namedtuple("_Switch", "var default domain doc env key invalidates lib guards setter",
+                                 defaults=(None, False, (), None, (), True))
+_MODES = ("auto", "off", "force")
+_ON_OFF = {False: 0, True: 1}
+_SWITCHES = {
+    "abl_skip_wgrad": _Switch("_ABL_SKIP_WGRAD", False, bool, """Backward-weights launches are SKIPPED (wgrad_launch returns before the
+    library call): how much of the step they cost.  Every weight gradient of the process is then zero — tuning runs only.""",
+                              env="RAMNET_ABL_SKIP_WGRAD", setter=False),
+    "winograd": _Switch("_WINOGRAD", True, bool, """3x3 stride-1 layers (ConvGRU gates / candidate, residual blocks) run Winograd F(2x2,3x3)
+    in fp32 — 2.25x fewer multiplies, rounding error ~1e-6 relative (tests/test_hip_ops.py) — unless switched off.""", key=True),
+    "wgrad_slabs": _Switch("_WGRAD_SLABS", True, bool, """Winograd backward-weights: tile splits join per-split slabs of the workspace by
+    plain read-modify-write (default: no atomics, bit-reproducible gradients) or meet in slab 0 by atomic adds (A/B runs).""", key=True,
+                           guards=((False, "deterministic", True, "set_wgrad_slabs(False) has no deterministic form: the atomic join of the "
+                                    "backward-weights tile splits contradicts set_deterministic(True)"),)),
+    "winograd_2x4": _Switch("_WINO_2X4", "auto", _MODES, """F(2x4,3x3) variant of the Winograd forward / backward-data launches
+    (csrc/conv_wino6.hip): "auto" = where the library's size heuristics pick it (large maps: the two fine scales at the training batch),
+    "off" = F(2x2,3x3) everywhere, "force" = every structurally eligible launch (tests).  The ConvLSTM cell launch (hidden size a multiple
+    of 16; gate-interleaved pack "2x4g") and its backward-data launch are governed like every other launch.  min_wgs of the setter:
+    launch-size threshold of "auto" (library default when None).  It goes to ramnet_wino2x4_config, which has no getter: it is no row of
+    this table, and switches() neither sets nor restores it.""", key=True, setter=False),
+    "wgrad_winograd_2x4": _Switch("_WGRAD_2X4", "auto", _MODES, """F(2x4,3x3) backward-weights (csrc/conv_wgrad_wino6.hip) for the plain 3x3
+    layers (ConvGRU / ConvLSTM / residual layers of >= 64 reduction channels): "auto" (default) = when the backward-weights launches are
+    co-scheduled with the backward-data chain (set_wgrad_overlap(True): training step +1.1 % same-box; in stream order the 32 x 32-channel
+    F(2x2) workgroups are faster: 200.4 vs 196.5 samples/s), "force" = always (tests), "off" = F(2x2,3x3) everywhere.  Takes effect at the
+    next backward pass (a pass uses one workspace layout per layer)."""),
+    "fold_upsample": _Switch("_FOLD_UP", True, bool, """UpsampleConvLayer forward as four 4x4 parity convolutions of the low-resolution input
+    (16 instead of 25 MACs per output, no interpolation in the loader) plus small border-correction GEMMs (DESIGN 3.1c).  Off: the direct
+    5x5 kernel with the bilinear loader."""),
+    "fold_winograd": _Switch("_FOLD_WINO", True, bool, """Folded upsample-conv forward on the Winograd F(2x2,4x4) kernel (shapes:
+    _fold_wino_ok) or the direct one."""),
+    "fold_winograd_wgrad": _Switch("_FOLD_WINO_WGRAD", True, bool, """Folded upsample-conv backward-weights in the Winograd F(2x2,4x4)
+    domain (32 x 64 or 64 x 32 channel workgroups) or as four direct 16-tap parity launches."""),
+    "fold_pair": _Switch(None, True, bool, """32-channel folded decoders in the pair form (default) or as 64 tiles x 32 channels; the library
+    option and the packs follow.""", invalidates=("invalidate_packs", "invalidate_descs"), lib=(b"fold_pair", _ON_OFF)),
+    "fold_winograd_2x3": _Switch("_FOLD_2X3", "auto", _MODES, """F(2x3,4x4) variant of the folded decoders' Winograd forward / backward-data
+    launches (conv_wino24_kernel<.., 3>): "auto" = where the library's size heuristics pick it (ramnet_fold_wino_variant: the
+    training-batch launches), "off" = F(2x2,4x4) everywhere, "force" = every structurally eligible launch (tests).""", key=True),
+    "fold_half_wg": _Switch(None, "auto", _MODES, """F(2x3,4x4) forward / backward-data launches of the folded decoders as half workgroups
+    (conv_wino24_kernel<.., HALF>: 4 waves, 16 tiles, two workgroups per CU; same outputs bit for bit): "auto" (default) = where the
+    library's rule picks it (ramnet_fold_halfwg_variant: the training-batch launches), "off" = the 8-wave workgroups everywhere, "force" =
+    every such launch.  The library decides per launch; graphs captured before the call keep what they captured.""",
+                            lib=(b"fold_half_wg", {"off": 0, "force": 1, "auto": 2})),
+    "fold_winograd_wgrad_2x3": _Switch("_FOLD_WGRAD_2X3", "auto", _MODES, """Backward-weights of the folded upsample-conv on 2 x 3 gradient
+    tiles (F(2x3,4x4), csrc/conv_wgrad_wino24.hip): "auto" = where the library's size rule picks it (ramnet_fold_wgrad_variant), "off" =
+    F(2x2,4x4) everywhere, "force" = every launch the kernel takes."""),
+    "fold_dgrad": _Switch("_FOLD_DGRAD", True, bool, """Backward-data of the folded upsample-conv: the adjoint of (four parity convolutions of
+    the replicate-padded input + border GEMMs), i.e. conv_wino24_kernel over the parity sub-grids of dy * mask with the flipped filters ->
+    gradient of the padded tensor -> replicate-padding adjoint, plus the border GEMMs' adjoint scattered through the bilinear taps (DESIGN
+    3.1g).  Off: direct 5x5 kernel on the full-resolution grid + bilinear adjoint."""),
+    "gru_bwd_fused": _Switch("_GRU_BWD_FUSED", True, bool, """Stage B of the ConvGRU backward (ramnet_gru_bwd_b) in the epilogue of the
+    candidate convolution's backward-data launch (RAMNET_EPI_GRU_BWD; hidden sizes that are multiples of 64): on by default, off for A/B
+    runs and the unfused path's tests."""),
+    "gru_materialize_hr": _Switch("_GRU_HR", True, bool, """The ConvGRU gates launch also writes h.r (RAMNET_EPI_SIGMOID_HR): the candidate
+    convolution and its backward-weights launch then read the plain concatenation [x | h.r] instead of forming the product in their
+    loaders (one more state-sized tensor per update, saved for the backward; the same single-rounded products either way).  On by default;
+    off for A/B runs and the loader path's tests.""", env="RAMNET_GRU_HR"),
+    "split_operands": _Switch("_SPLIT_OPERANDS", False, bool, """F(2x4,3x3) forward / backward-data launches with three-term bf16 splits of
+    both operands on the bf16 matrix pipe (RAMNET_ALGO_WINOGRAD_2X4_SPLIT, csrc/conv_wino6s.hip: six of the nine partial products, fp32
+    accumulation — fp32-level accuracy, the parity suites run it at unchanged tolerances) instead of the exact-fp32 MFMA.  Off by default:
+    the headline arithmetic is exact fp32.""", key=True, invalidates=("invalidate_descs",)),
+    "split_wgrad": _Switch("_SPLIT_WGRAD", False, bool, """With split operands on (set_split_operands): the backward-weights launches of the
+    layers that would run F(2x4,3x3) run the DIRECT 3x3 form on the bf16 matrix pipe instead (RAMNET_ALGO_DIRECT_SPLIT,
+    csrc/conv_wgrad_dsplit.hip: operands split once per element when a strip is staged, no Winograd transform in the loop).  OFF by default
+    — measured (profiles/r06_dsplit_notes.md): the six backward-weights launches of a ConvGRU update 1.19 ms against 1.20 ms for the
+    exact-fp32 F(2x4) kernel on their own, and the co-scheduled training step LOSES 7 % (237 against 255 samples/s with split forward /
+    backward-data launches): kept as a correct, tested algorithm and a record of why its loop does not reach the matrix pipe's rate.  Takes
+    effect at the next backward pass.""", env="RAMNET_SPLIT_WGRAD"),
+    "winograd_split": _Switch(None, 1, int, """Split channel reduction of latency-bound F(2x2,3x3) launches (batch-1 streaming on the coarse
+    scales; csrc/conv_wino.hip): on by default, off for A/B runs (2..16: that many splits, tuning runs).  Descriptors are built per
+    launch, graphs captured before the call keep what they captured.""", invalidates=("invalidate_descs",), lib=(b"wino_ksplit", None)),
+    "head_kernel": _Switch("_HEAD", True, bool, """The two 5x5 head layers (1 / 5 real input channels -> 32 maps at full resolution) on
+    their own kernel (DESIGN 3.1e): dense (tap, channel) reduction with the weights in registers.  Off: the generic kernel.""", key=True),
+    "space_to_depth": _Switch("_S2D", True, bool, """Stride-2 5x5 layers (the encoders) as 3x3 stride-1 convolutions of the space-to-depth
+    input on the Winograd kernels (DESIGN 3.1d).  Off: the direct stride-2 kernels."""),
+    "space_to_depth_fused": _Switch("_S2D_FUSED", True, bool, """The space-to-depth view is read / written in place by the Winograd kernels
+    (RAMNET_IN_S2D loader, out_s2d epilogue) when the channel count is a power of two >= 32; off: materialised with
+    ramnet_space_to_depth2 instead."""),
+    "space_to_depth_2x4": _Switch("_S2D_2X4", True, bool, """The space-to-depth view on the F(2x4,3x3) kernel (dense) where the library's
+    size heuristics select it (the training batch).  (environment: A/B runs of bench.py)""", env="RAMNET_S2D_2X4", key=True),
+    "cell_state_half": _Switch("_STATE_HALF", "auto", _MODES, """Backward-data of a recurrent cell whose x needs no gradient: the launches
+    form dh alone from the state half of the transposed weights (half the output channels, written into dxh[..., C:] at ld 2C).  The
+    ConvGRU then runs stage B as its own launch (RAMNET_EPI_GRU_BWD tells the halves apart by Cout = 2C).  "auto": where it pays (launches
+    of at least min_pix pixels; profiles/partial_training_notes.md has the table), "off": full-width launches everywhere, "force": every
+    cell (tests).""", setter=False),
+    "cell_state_half_min_pix": _Switch("_STATE_HALF_MIN_PIX", 0, int, """min_pix of set_cell_state_half.""", setter=False),
+    "wgrad_overlap": _Switch("_USE_SIDE", False, bool, """Run backward-weights kernels on a side stream, co-scheduled with the backward-data
+    chain (+4-6 % step rate on MI355X; per-kernel timings then include co-scheduled time, so profiling runs keep it off).  The library
+    option gives the Winograd backward-weights kernel the shape that suits the schedule: 32 x 64-channel workgroups (two per CU) share the
+    CUs with the backward-data chain of the other stream; 32 x 32-channel workgroups (168 registers: three per CU) are 13-20 % faster on
+    their own and 3 % slower in the co-scheduled step, where three of them leave a CU no room for a backward-data workgroup.""",
+                             lib=(b"wgrad_wino_nf", {False: 1, True: 2})),
+    "decoder_overlap": _Switch("_USE_DECODE", False, bool, """The decoder of update k (prediction for that measurement) and the state update
+    k+1 both depend only on the state after update k: when on, the model runs its decoders on a second stream, in forward and — because
+    autograd runs a node's backward on its forward stream — in backward, so the two kernel chains fill each other's tails."""),
+    "branch_overlap": _Switch("_USE_BRANCH", False, bool, """Inference, asynchronous RAM-Net: the state update of scale i depends on the
+    encoder feature x_i and the state h_i only (statenet.py:215-237 — x chains through the encoders, the states do not), so the three
+    ConvGRU / ConvLSTM updates of one measurement are independent of each other and of the next encoder.  When on, every scale but the
+    last runs on a stream of its own (forked behind its encoder, joined at the end of the update): at batch 1 a launch fills a fraction of
+    the chip, and the critical path of an update shrinks from head + 3 encoders + 6 state launches to head + 3 encoders + 2."""),
+    "wgrad_defer": _Switch("_WGRAD_DEFER", 0, range(H.WGRAD_MAX_SEGMENTS + 1), """Cell updates per deferred multi-segment backward-weights
+    launch of a ConvGRU layer (0 / 1: every update launches its own; <= 48).  The queued tensors (x, h, [u|r], the gate gradients: ~0.24
+    GB per update at the bench shape) stay alive until the launch."""),
+    "time_batching": _Switch("_TIME_BATCH", True, bool, """ERGB2DepthRecurrent.forward batches over TIME what does not depend on the order of
+    the state updates (the event encoders of a package as ONE chain at batch K x B, the decodes of a package in groups: model/model.py) —
+    on by default, off for A/B runs and the pass-by-pass path's tests.  max_decodes: split a decode group into chains of at most that many
+    measurements (0 = no split).""", setter=False),
+    "time_batch_max_decodes": _Switch("_TIME_BATCH_MAX_DECODES", 0, int, """max_decodes of set_time_batching: decodes per chain of the
+    time-batched forward (0: a whole group).""", setter=False),
+    "relu_premask": _Switch("_RELU_PREMASK", True, bool, """A time-batched feature that is a ReLU output gets its ReLU mask where its gradient
+    is summed (TimeSplit / TimeFan backward: one more operand in an HBM-bound launch) instead of in the loaders of its layer's
+    backward-data and backward-weights launches (two operands per staged slot on the matrix kernels: RAMNET_IN_RELUMASK / gmask).  The same
+    values reach the same products: bit-identical gradients."""),
+    "si_fusion": _Switch("_SI_FUSION", True, bool, """Scale-invariant loss of the supervised predictions inside the prediction layer's
+    launches (PredSigmoidSI; trainer.sequence_loss asks the model for it): on by default, off for A/B runs and the separate-launch path's
+    tests."""),
+    "grad_loss_batched": _Switch("_GRAD_LOSS_BATCHED", True, bool, """trainer.sequence_loss forms the multi-scale gradient loss of all
+    supervised maps of a sequence in ONE batched call after the forward loop (multi_scale_grad_loss_batch: deterministic, no saved
+    pyramid) — on by default; off: one multi_scale_grad_loss per map, as before (A/B runs and the per-pair path's tests).""",
+                                 guards=((False, "deterministic", True, "set_grad_loss_batched(False) has no deterministic form: the unbatched "
+                                          "multi-scale gradient loss joins by atomic adds (set_deterministic(True) is on)"),)),
+    "desc_cache": _Switch("_DESC_CACHE_ON", True, bool, """Launch descriptors are cached per call site (_conv_desc, wgrad_launch); off: every
+    launch builds its descriptor from scratch (tuning runs).""", env="RAMNET_DESC_CACHE", setter=False),
+    # Deterministic mode: every floating-point join of the training step runs in a fixed order — the same loss, gradients and (with a
+    # deterministic optimiser) weights, bit for bit, on the same machine, device, world size and library build.  The backward-weights
+    # launches of EVERY family then own per-split slabs (ramnet_wgrad_desc.dw_slabs, folded by ramnet_reduce_slabs as the 3x3 families'
+    # always were), the border-GEMM, bias and prediction-layer gradients and the normalisation statistics go through the library's
+    # *_ordered entry points, the voxeliser is the sorted one; an operation without an ordered form raises RuntimeError naming itself
+    # (not_deterministic) instead of running.  The library option: it refuses, instead of taking, the zero-fill + atomics form of
+    # ramnet_si_loss_fwd / ramnet_si_log_loss_fwd when the fixed-order one-launch form has no scratch (a stream capture, a failed allocation).
+    "deterministic": _Switch("_DETERMINISTIC", False, bool, """Off by default: every launch, its order, its kernel and its descriptor are then
+    what they are without this switch.""", lib=(b"ordered_only", _ON_OFF),
+                             guards=((True, "wgrad_slabs", False, "set_deterministic(True) needs the slab join of the backward-weights "
+                                      "launches: set_wgrad_slabs(True) first"),
+                                     (True, "grad_loss_batched", False, "set_deterministic(True) needs the batched multi-scale gradient "
+                                      "loss: set_grad_loss_batched(True) first"))),
+}
+for _row in _SWITCHES.values():
+    if _row.var is not None:
+        _env = _os.environ.get(_row.env) if _row.env else None
+        globals()[_row.var] = _row.default if _env is None else (_env != "0" if _row.default else _env == "1")
 
 
-def set_winograd(on):
-    global _WINOGRAD
-    _WINOGRAD = bool(on)
+def _switch_key():
+    return tuple(globals()[row.var] for row in _SWITCHES.values() if row.key)
 
 
-_WINO_2X4 = "auto"
-_WGRAD_SLABS = True
-_WGRAD_2X4 = "auto"       # F(2x4,3x3) backward-weights (csrc/conv_wgrad_wino6.hip): "auto" (with set_wgrad_overlap(True)) | "off" | "force"
+_SWITCH_KEY = _switch_key()         # the descriptor keys' one element for every key=True row; rebuilt by their setters
 
 
-def set_wgrad_slabs(on):
-    """Winograd backward-weights: tile splits join per-split slabs of the workspace by plain read-modify-write (default: no atomics,
-    bit-reproducible gradients) or meet in slab 0 by atomic adds (A/B runs)."""
-    global _WGRAD_SLABS
-    if not on and _DETERMINISTIC:
-        raise RuntimeError("set_wgrad_slabs(False) has no deterministic form: the atomic join of the backward-weights tile splits "
-                           "contradicts set_deterministic(True)")
-    _WGRAD_SLABS = bool(on)
+def _switch_value(name):
+    row = _SWITCHES[name]
+    if row.var is not None:
+        return globals()[row.var]
+    option, values = row.lib
+    held = H.lib().ramnet_get_option(option)
+    return held if values is None else next(v for v, o in values.items() if o == held)
 
 
-# Deterministic mode: every floating-point join of the training step runs in a fixed order — the same loss, gradients and (with a deterministic
-# optimiser) weights, bit for bit, on the same machine, device, world size and library build.  The backward-weights launches of EVERY family
-# then own per-split slabs (ramnet_wgrad_desc.dw_slabs, folded by ramnet_reduce_slabs as the 3x3 families' always were), the border-GEMM,
-# bias and prediction-layer gradients and the normalisation statistics go through the library's *_ordered entry points, the voxeliser is
-# the sorted one; an operation without an ordered form raises RuntimeError naming itself (not_deterministic) instead of running.
-_DETERMINISTIC = False
+def _set_switch(name, value):
+    global _SWITCH_KEY
+    row = _SWITCHES[name]
+    for refused, other, state, text in row.guards:
+        if bool(value) == refused and _switch_value(other) == state:
+            raise RuntimeError(text)
+    if row.domain in (bool, int):
+        value = row.domain(value)
+    elif isinstance(row.domain, range):
+        value = int(value)
+        assert value in row.domain
+    elif row.lib is None:               # (a library-held mode is refused by the KeyError of its value mapping, below)
+        assert value in row.domain
+    if row.var is not None:
+        globals()[row.var] = value
+    if row.lib is not None:
+        option, values = row.lib
+        H.check(H.lib().ramnet_set_option(option, value if values is None else values[value]), "set_option")
+    for fn in row.invalidates:
+        globals()[fn]()
+    if row.key:
+        _SWITCH_KEY = _switch_key()
 
 
-def set_deterministic(on):
-    """Off by default: every launch, its order, its kernel and its descriptor are then what they are without this switch."""
-    global _DETERMINISTIC
-    if on and not _WGRAD_SLABS:
-        raise RuntimeError("set_deterministic(True) needs the slab join of the backward-weights launches: set_wgrad_slabs(True) first")
-    if on and not _GRAD_LOSS_BATCHED:
-        raise RuntimeError("set_deterministic(True) needs the batched multi-scale gradient loss: set_grad_loss_batched(True) first")
-    _DETERMINISTIC = bool(on)
-    # the library refuses, instead of taking, the zero-fill + atomics form of ramnet_si_loss_fwd / ramnet_si_log_loss_fwd when the fixed-order
-    # one-launch form has no scratch (a stream capture, a failed allocation)
-    H.check(H.lib().ramnet_set_option(b"ordered_only", int(_DETERMINISTIC)), "set_option")
+def _setter(name):
+    def setter(value):
+        _set_switch(name, value)
+    setter.__name__ = setter.__qualname__ = "set_" + name
+    setter.__doc__ = _SWITCHES[name].doc
+    return setter
 
 
-def deterministic():
-    return _DETERMINISTIC
-
-
-def not_deterministic(what):
-    """Called by an operation that has no ordered form, before it launches anything."""
-    if _DETERMINISTIC:
-        raise RuntimeError("%s has no deterministic form: it joins floating-point partial sums by atomic adds (set_deterministic(True) is on)" % what)
-
+globals().update(("set_" + _name, _setter(_name)) for _name, _row in _SWITCHES.items() if _row.setter)
 
 
 def set_winograd_2x4(mode, min_wgs=None):
-    """F(2x4,3x3) variant of the Winograd forward / backward-data launches (csrc/conv_wino6.hip): "auto" = where the library's size
-    heuristics pick it (large maps: the two fine scales at the training batch), "off" = F(2x2,3x3) everywhere, "force" = every
-    structurally eligible launch (tests).  The ConvLSTM cell launch (hidden size a multiple of 16; gate-interleaved pack "2x4g") and its
-    backward-data launch are governed like every other launch.  min_wgs: launch-size threshold of "auto" (library default when None)."""
-    global _WINO_2X4
-    assert mode in ("auto", "off", "force")
-    _WINO_2X4 = mode
+    _set_switch("winograd_2x4", mode)
     if min_wgs is not None:
         H.check(H.lib().ramnet_wino2x4_config(int(min_wgs)), "wino2x4_config")
         invalidate_descs()
+
+
+def set_time_batching(on, max_decodes=None):
+    _set_switch("time_batching", on)
+    if max_decodes is not None:
+        _set_switch("time_batch_max_decodes", max_decodes)
+
+
+def set_cell_state_half(mode, min_pix=None):
+    _set_switch("cell_state_half", mode)
+    if min_pix is not None:
+        _set_switch("cell_state_half_min_pix", min_pix)
+
+
+for _name in ("winograd_2x4", "time_batching", "cell_state_half"):
+    globals()["set_" + _name].__doc__ = _SWITCHES[_name].doc
+
+
+def switch_values():
+    """{row name: current value} of every switch (library-held ones through ramnet_get_option)."""
+    return {name: _switch_value(name) for name in _SWITCHES}
+
+
+@contextlib.contextmanager
+def switches(**values):
+    """Apply the named switches in the order given; on exit, also when the body or one of the changes raises, put back the values that were
+    there before, in reverse order."""
+    undo = []
+    try:
+        for name, value in values.items():
+            old = _switch_value(name)
+            _set_switch(name, value)
+            undo.append((name, old))
+        yield
+    finally:
+        for name, value in reversed(undo):
+            _set_switch(name, value)
 
 
 def get_winograd():
     return _WINOGRAD
 
 
-# UpsampleConvLayer forward as four 4x4 parity convolutions of the low-resolution input (16 instead of 25 MACs per output,
-# no interpolation in the loader) plus small border-correction GEMMs (DESIGN 3.1c).  RAMNET_FOLD_UPSAMPLE=0 /
-# set_fold_upsample(False) keeps the direct 5x5 kernel with the bilinear loader.
-_FOLD_UP = True
-
-
-_FOLD_WINO = True
-_FOLD_WINO_MIN_COUT = 32
-_FOLD_WINO_WGRAD = True
-_SAVE_XPAD = False         # keep pad2(x + skip) of a folded decoder layer for its backward: +2 GB, no measurable gain
-
-
-def set_fold_winograd_wgrad(on):
-    """Folded upsample-conv backward-weights in the Winograd F(2x2,4x4) domain (32 x 64 or 64 x 32 channel workgroups) or as four
-    direct 16-tap parity launches."""
-    global _FOLD_WINO_WGRAD
-    _FOLD_WINO_WGRAD = bool(on)
-
-
-def set_fold_pair(on):
-    """32-channel folded decoders in the pair form (default) or as 64 tiles x 32 channels; the library option and the packs follow."""
-    H.check(H.lib().ramnet_set_option(b"fold_pair", int(bool(on))), "set_option")
-    invalidate_packs()
-    invalidate_descs()
-
-
-_GRU_BWD_FUSED = True
-
-
-def set_gru_bwd_fused(on):
-    """Stage B of the ConvGRU backward (ramnet_gru_bwd_b) in the epilogue of the candidate convolution's backward-data launch
-    (RAMNET_EPI_GRU_BWD; hidden sizes that are multiples of 64): on by default, off for A/B runs and the unfused path's tests."""
-    global _GRU_BWD_FUSED
-    _GRU_BWD_FUSED = bool(on)
-
-
-_GRU_HR = _os.environ.get("RAMNET_GRU_HR", "1") != "0"
-
-
-def set_gru_materialize_hr(on):
-    """The ConvGRU gates launch also writes h.r (RAMNET_EPI_SIGMOID_HR): the candidate convolution and its backward-weights launch then read
-    the plain concatenation [x | h.r] instead of forming the product in their loaders (one more state-sized tensor per update, saved for the
-    backward; the same single-rounded products either way).  On by default; off for A/B runs and the loader path's tests."""
-    global _GRU_HR
-    _GRU_HR = bool(on)
-
-
-_SPLIT_OPERANDS = False
-
-
-def set_split_operands(on):
-    """F(2x4,3x3) forward / backward-data launches with three-term bf16 splits of both operands on the bf16 matrix pipe (RAMNET_ALGO_WINOGRAD_2X4_SPLIT,
-    csrc/conv_wino6s.hip: six of the nine partial products, fp32 accumulation — fp32-level accuracy, the parity suites run it at unchanged
-    tolerances) instead of the exact-fp32 MFMA.  Off by default: the headline arithmetic is exact fp32."""
-    global _SPLIT_OPERANDS
-    _SPLIT_OPERANDS = bool(on)
-    invalidate_descs()
+def deterministic():
+    return _DETERMINISTIC
 
 
 def get_split_operands():
     return _SPLIT_OPERANDS
 
 
-_SPLIT_WGRAD = _os.environ.get("RAMNET_SPLIT_WGRAD", "0") == "1"
-
-
-def set_split_wgrad(on):
-    """With split operands on (set_split_operands): the backward-weights launches of the layers that would run F(2x4,3x3) run the DIRECT
-    3x3 form on the bf16 matrix pipe instead (RAMNET_ALGO_DIRECT_SPLIT, csrc/conv_wgrad_dsplit.hip: operands split once per element when a
-    strip is staged, no Winograd transform in the loop).  OFF by default — measured (profiles/r06_dsplit_notes.md): the six backward-weights
-    launches of a ConvGRU update 1.19 ms against 1.20 ms for the exact-fp32 F(2x4) kernel on their own, and the co-scheduled training step
-    LOSES 7 % (237 against 255 samples/s with split forward / backward-data launches): kept as a correct, tested algorithm and a record of
-    why its loop does not reach the matrix pipe's rate.  Takes effect at the next backward pass."""
-    global _SPLIT_WGRAD
-    _SPLIT_WGRAD = bool(on)
-
-
 def get_split_wgrad():
     return _SPLIT_WGRAD
 
 
-def set_wgrad_winograd_2x4(mode):
-    """F(2x4,3x3) backward-weights for the plain 3x3 layers (ConvGRU / ConvLSTM / residual layers of >= 64 reduction channels): "auto"
-    (default) = when the backward-weights launches are co-scheduled with the backward-data chain (set_wgrad_overlap(True): training step
-    +1.1 % same-box; in stream order the 32 x 32-channel F(2x2) workgroups are faster: 200.4 vs 196.5 samples/s), "force" = always (tests),
-    "off" = F(2x2,3x3) everywhere.  Takes effect at the next backward pass (a pass uses one workspace layout per layer)."""
-    global _WGRAD_2X4
-    assert mode in ("auto", "off", "force")
-    _WGRAD_2X4 = mode
+def get_fold_upsample():
+    return _FOLD_UP
 
 
-def set_winograd_split(on):
-    """Split channel reduction of latency-bound F(2x2,3x3) launches (batch-1 streaming on the coarse scales; csrc/conv_wino.hip): on by
-    default, off for A/B runs.  Descriptors are built per launch, graphs captured before the call keep what they captured."""
-    H.check(H.lib().ramnet_set_option(b"wino_ksplit", int(on)), "set_option")         # (2..16: that many splits, tuning runs)
-    invalidate_descs()
+def get_head_kernel():
+    return _HEAD
+
+
+def decoder_overlap():
+    return _USE_DECODE
+
+
+def branch_overlap():
+    return _USE_BRANCH
+
+
+def wgrad_defer():
+    return _WGRAD_DEFER
+
+
+def get_space_to_depth():
+    return _S2D
+
+
+def time_batch_max_decodes():
+    return _TIME_BATCH_MAX_DECODES
+
+
+def time_batching():
+    return _TIME_BATCH
+
+
+def get_relu_premask():
+    return _RELU_PREMASK
+
+
+def si_fusion():
+    return _SI_FUSION
+
+
+def grad_loss_batched():
+    return _GRAD_LOSS_BATCHED
+
+
+if _ABL_SKIP_WGRAD:
+    import warnings as _warnings
+    _warnings.warn("RAMNET_ABL_SKIP_WGRAD=1: backward-weights launches are SKIPPED — every weight gradient of this process is zero "
+                   "(tuning runs only; unset the variable for anything else)", RuntimeWarning)
+
+_WINO_MIN_CIN = 32        # smallest reduction depth that uses the Winograd kernels
+_FOLD_WINO_MIN_COUT = 32
+_SAVE_XPAD = False         # keep pad2(x + skip) of a folded decoder layer for its backward: +2 GB, no measurable gain
+_S2D_SPARSE = True         # skip the Winograd positions that the zero slices of the space-to-depth view annihilate (ramnet_conv_desc.s2d_5x5)
+
+
+def not_deterministic(what):
+    """Called by an operation that has no ordered form, before it launches anything."""
+    if _DETERMINISTIC:
+        raise RuntimeError("%s has no deterministic form: it joins floating-point partial sums by atomic adds (set_deterministic(True) is on)" % what)
 
 
 def _fold_pair(Cout, Cin):
@@ -208,41 +360,7 @@ def _fold_wino_ok(Cin, Cout):
     return Cout % 32 == 0 and Cout >= _FOLD_WINO_MIN_COUT and Cin % (2 * kc) == 0
 
 
-def set_fold_winograd(on):
-    """Folded upsample-conv forward on the Winograd F(2x2,4x4) kernel (shapes: _fold_wino_ok) or the direct one."""
-    global _FOLD_WINO
-    _FOLD_WINO = bool(on)
-
-
-_FOLD_2X3 = "auto"
-
-
-def set_fold_winograd_2x3(mode):
-    """F(2x3,4x4) variant of the folded decoders' Winograd forward / backward-data launches (conv_wino24_kernel<.., 3>): "auto" = where
-    the library's size heuristics pick it (ramnet_fold_wino_variant: the training-batch launches), "off" = F(2x2,4x4) everywhere,
-    "force" = every structurally eligible launch (tests)."""
-    global _FOLD_2X3
-    assert mode in ("auto", "off", "force")
-    _FOLD_2X3 = mode
-
-
-def set_fold_half_wg(mode):
-    """F(2x3,4x4) forward / backward-data launches of the folded decoders as half workgroups (conv_wino24_kernel<.., HALF>: 4 waves,
-    16 tiles, two workgroups per CU; same outputs bit for bit): "auto" (default) = where the library's rule picks it
-    (ramnet_fold_halfwg_variant: the training-batch launches), "off" = the 8-wave workgroups everywhere, "force" = every such launch.  The library decides per launch; graphs captured before the call keep what they captured."""
-    H.check(H.lib().ramnet_set_option(b"fold_half_wg", {"off": 0, "force": 1, "auto": 2}[mode]), "set_option")
-
-
-_FOLD_WGRAD_2X3 = "auto"
 _FOLD_WGRAD_VARIANT = {}
-
-
-def set_fold_winograd_wgrad_2x3(mode):
-    """Backward-weights of the folded upsample-conv on 2 x 3 gradient tiles (F(2x3,4x4), csrc/conv_wgrad_wino24.hip): "auto" = where the
-    library's size rule picks it (ramnet_fold_wgrad_variant), "off" = F(2x2,4x4) everywhere, "force" = every launch the kernel takes."""
-    global _FOLD_WGRAD_2X3
-    assert mode in ("auto", "off", "force")
-    _FOLD_WGRAD_2X3 = mode
 
 
 def _fold_wgrad_2x3(B, Hh, W, Cin, Cout):
@@ -259,15 +377,6 @@ def _fold_wgrad_2x3(B, Hh, W, Cin, Cout):
         d.Cout = d.ldg = d.ldgm = Cout
         hit = _FOLD_WGRAD_VARIANT[key] = bool(H.lib().ramnet_fold_wgrad_variant(C.byref(d), int(_FOLD_WGRAD_2X3 == "force")))
     return hit
-
-
-def set_fold_upsample(on):
-    global _FOLD_UP
-    _FOLD_UP = bool(on)
-
-
-def get_fold_upsample():
-    return _FOLD_UP
 
 
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -371,20 +480,6 @@ def uses_winograd(taps, w, stride, epi, in_mode, C0, C1):
                 and C0 + C1 >= _WINO_MIN_CIN and (C1 == 0 or C0 % 8 == 0))
 
 
-# The two 5x5 head layers (1 / 5 real input channels -> 32 maps at full resolution) on their own kernel:
-# dense (tap, channel) reduction with the weights in registers.  RAMNET_HEAD_KERNEL=0 / set_head_kernel(False): generic kernel.
-_HEAD = True
-
-
-def set_head_kernel(on):
-    global _HEAD
-    _HEAD = bool(on)
-
-
-def get_head_kernel():
-    return _HEAD
-
-
 def uses_head(taps, w, stride, epi, in_mode):
     """Does this forward launch run the head kernel?  (dense 5x5 stride-1 window, fp32, plain input, 1/3/5 real input
     channels, <= 32 outputs, bias + optional ReLU only.)"""
@@ -397,10 +492,9 @@ def uses_head(taps, w, stride, epi, in_mode):
 # the shapes / strides and the kernel-selection switches — filling ~45 ctypes fields and asking the library twice (F(2x4) variant, split
 # reduction) cost ~17 us per launch, ~1100 launches per training step on the two host threads.  A hit copies the template and sets the
 # pointers (~5 us).  The key holds every argument that is not a tensor's address, the strides, the 16-byte alignment of the epilogue
-# operands (the library's variant choice looks at it) and the switches; _DESC_EPOCH covers library-side options.
+# operands (the library's variant choice looks at it) and the switches (_SWITCH_KEY); _DESC_EPOCH covers library-side options.
 _DESC_CACHE = {}
 _DESC_EPOCH = 0
-_DESC_CACHE_ON = _os.environ.get("RAMNET_DESC_CACHE", "1") != "0"
 
 
 def invalidate_descs():
@@ -424,8 +518,8 @@ def _conv_desc(x0, taps, w, out, Cout, *, stride=1, x1=None, xm=None, xm_off=0, 
             al |= t.data_ptr()
     key = (id(taps), id(w.cp) if is_ref else 0, w.transposed if is_ref else -1, id(ws_owner), Cout, stride, in_mode, C0, C1, Hin, Win, epi, beta, Ho,
            Wo, os, out_off, frame, out_s2d, wino24, xm_off, tuple(x0.shape), x0.stride(2), _sd(x1), _sd(xm), out.shape[1], out.shape[2],
-           out.stride(2), _sd(e0), _sd(e1), _sd(o1), _sd(o2), bias is None, al & 15, _WINOGRAD, _WINO_2X4, _SPLIT_OPERANDS, _HEAD, _S2D_SPARSE, _S2D_2X4,
-           _FOLD_2X3, _DESC_EPOCH, x0.device.index)
+           out.stride(2), _sd(e0), _sd(e1), _sd(o1), _sd(o2), bias is None, al & 15, _SWITCH_KEY, _S2D_SPARSE, _DESC_EPOCH,
+           x0.device.index)
     hit = _DESC_CACHE.get(key) if _DESC_CACHE_ON else None
     if hit is not None and (not is_ref or hit[3]() is w.cp) and (ws_owner is None or hit[4]() is ws_owner):
         tmpl, kind, nsplit = hit[0], hit[1], hit[2]
@@ -679,7 +773,7 @@ def wgrad_launch(x0, taps, dout, dw, Cout, *, stride=1, x1=None, xm=None, xm_off
     # (descriptor cache as for _conv_desc: the template holds everything but the six pointers)
     key = (id(taps), id(dw), _layout_of(dw), _det_slabs(dw), getattr(dw, "head_cin", 0), Cout, stride,
            in_mode, C0, C1, Hin, Win, Ho, Wo, gview, dw_off, wino24, xm_off, tuple(x0.shape), x0.stride(2), _sd(x1), _sd(xm), dout.shape[1],
-           dout.shape[2], dout.stride(2), _sd(gmask), _WGRAD_SLABS, _HEAD, x0.device.index)
+           dout.shape[2], dout.stride(2), _sd(gmask), _SWITCH_KEY, x0.device.index)
     tmpl = _WDESC_CACHE.get(key) if _DESC_CACHE_ON else None
     if tmpl is not None:
         d = H.WgradDesc.from_buffer_copy(tmpl)
@@ -705,35 +799,8 @@ def wgrad_launch(x0, taps, dout, dw, Cout, *, stride=1, x1=None, xm=None, xm_off
 # (its inputs are ready), the end-of-backward fold waits for the side stream; inputs are record_stream()'ed so the
 # caching allocator does not recycle them while the side stream still reads them.
 _SIDE = {}
-_USE_SIDE = False
-
-
-def set_wgrad_overlap(on):
-    """Run backward-weights kernels on a side stream, co-scheduled with the backward-data chain (+4-6 % step rate on
-    MI355X; per-kernel timings then include co-scheduled time, so profiling runs keep it off)."""
-    global _USE_SIDE
-    _USE_SIDE = bool(on)
-    # the Winograd backward-weights kernel in the shape that suits the schedule: 32 x 64-channel workgroups (two per CU) share the CUs
-    # with the backward-data chain of the other stream; 32 x 32-channel workgroups (168 registers: three per CU) are 13-20 % faster on
-    # their own and 3 % slower in the co-scheduled step, where three of them leave a CU no room for a backward-data workgroup
-    H.check(H.lib().ramnet_set_option(b"wgrad_wino_nf", 2 if _USE_SIDE else 1), "set_option")
-
-
-# The decoder of update k (prediction for that measurement) and the state update k+1 both depend only on the state after
-# update k: with set_decoder_overlap(True) the model runs its decoders on a second stream, in forward and — because
-# autograd runs a node's backward on its forward stream — in backward, so the two kernel chains fill each other's tails.
-_DECODE = {}
-_USE_DECODE = False
+_DECODE = {}            # the decoders' second stream (set_decoder_overlap)
 _DECODE_USED = set()
-
-
-def set_decoder_overlap(on):
-    global _USE_DECODE
-    _USE_DECODE = bool(on)
-
-
-def decoder_overlap():
-    return _USE_DECODE
 
 
 def decode_stream(dev):
@@ -744,22 +811,7 @@ def decode_stream(dev):
     return st
 
 
-# Inference, asynchronous RAM-Net: the state update of scale i depends on the encoder feature x_i and the state h_i only
-# (statenet.py:215-237 — x chains through the encoders, the states do not), so the three ConvGRU / ConvLSTM updates of one
-# measurement are independent of each other and of the next encoder.  With set_branch_overlap(True) every scale but the last runs
-# on a stream of its own (forked behind its encoder, joined at the end of the update): at batch 1 a launch fills a fraction of
-# the chip, and the critical path of an update shrinks from head + 3 encoders + 6 state launches to head + 3 encoders + 2.
-_BRANCH = {}
-_USE_BRANCH = False
-
-
-def set_branch_overlap(on):
-    global _USE_BRANCH
-    _USE_BRANCH = bool(on)
-
-
-def branch_overlap():
-    return _USE_BRANCH
+_BRANCH = {}            # one stream per scale but the last (set_branch_overlap)
 
 
 def branch_stream(dev, i):
@@ -817,23 +869,7 @@ def wgrad_side(tensors, *args, **kw):
 # update: a launch pays its prologue and — more — the join of every tile split's partial sums with the layer's workspace once (24 x 32 x 32
 # floats read and written per workgroup: ~40 us of a ~250 us launch at the training batch) whatever its length.  The cell's backward
 # queues its tensors on the layer (ConvParam._defer) and goes on with the backward-data chain; the queue is launched on the
-# backward-weights stream when it holds `_WGRAD_DEFER` updates and, for what is left, when the engine finishes the pass.
-_WGRAD_DEFER = 0
-
-
-def set_wgrad_defer(n):
-    """Cell updates per deferred multi-segment backward-weights launch of a ConvGRU layer (0 / 1: every update launches its own;
-    <= 48).  The queued tensors (x, h, [u|r], the gate gradients: ~0.24 GB per update at the bench shape) stay alive until the launch."""
-    global _WGRAD_DEFER
-    n = int(n)
-    assert 0 <= n <= H.WGRAD_MAX_SEGMENTS
-    _WGRAD_DEFER = n
-
-
-def wgrad_defer():
-    return _WGRAD_DEFER
-
-
+# backward-weights stream when it holds `_WGRAD_DEFER` updates (set_wgrad_defer) and, for what is left, when the engine finishes the pass.
 def _wgrad_cell(cp, dw, tensors, x0, taps, dout, Cout, **kw):
     """Backward-weights of one recurrent-cell convolution: launched now (wgrad_side) or queued on the layer for a multi-segment launch."""
     if _WGRAD_DEFER <= 1 or _layout_of(dw)[0] != "wino6" or not _WGRAD_SLABS:
@@ -1437,22 +1473,6 @@ class StateHalfConvParam(ConvParam):
         pass
 
 
-# Backward-data of a recurrent cell whose x needs no gradient: the launches form dh alone from the state half of the transposed weights
-# (half the output channels, written into dxh[..., C:] at ld 2C).  The ConvGRU then runs stage B as its own launch (RAMNET_EPI_GRU_BWD
-# tells the halves apart by Cout = 2C).  "auto": where it pays (launches of at least _STATE_HALF_MIN_PIX pixels; profiles/
-# partial_training_notes.md has the table), "off": full-width launches everywhere, "force": every cell (tests).
-_STATE_HALF = "auto"
-_STATE_HALF_MIN_PIX = 0
-
-
-def set_cell_state_half(mode, min_pix=None):
-    global _STATE_HALF, _STATE_HALF_MIN_PIX
-    assert mode in ("auto", "off", "force")
-    _STATE_HALF = mode
-    if min_pix is not None:
-        _STATE_HALF_MIN_PIX = int(min_pix)
-
-
 def _state_half_ok(want_x, npix, Cc):
     if want_x or _STATE_HALF == "off" or Cc % 4:
         return False
@@ -1609,42 +1629,9 @@ def _folded_upsample_conv(x, skip, cp, y, epi):
     return xpad
 
 
-# Stride-2 5x5 layers (the encoders) as 3x3 stride-1 convolutions of the space-to-depth input on the Winograd kernels
-# (DESIGN 3.1d).  RAMNET_S2D=0 / set_space_to_depth(False) keeps the direct stride-2 kernels.
-_S2D = True
-
-
-def set_space_to_depth(on):
-    global _S2D
-    _S2D = bool(on)
-
-
-def get_space_to_depth():
-    return _S2D
-
-
 def _s2d_eligible(x, cp, k, stride, up):
     return bool(_S2D and _WINOGRAD and stride == 2 and k == 5 and not up and x.shape[1] % 2 == 0
                 and x.shape[2] % 2 == 0 and x.shape[3] == cp.Cin and cp.Cin % 8 == 0 and cp.gates == 1 and len(cp.weights) == 1)
-
-
-# The space-to-depth view is read / written in place by the Winograd kernels (RAMNET_IN_S2D loader, out_s2d epilogue) when
-# the channel count is a power of two >= 32; ops.set_space_to_depth_fused(False) materialises it with ramnet_space_to_depth2 instead.
-_S2D_FUSED = True
-# ... and skip the Winograd positions that the zero slices of that view annihilate (ramnet_conv_desc.s2d_5x5)
-_S2D_SPARSE = True
-# ... or run the view on the F(2x4,3x3) kernel (dense) where the library's size heuristics select it (the training batch)
-_S2D_2X4 = _os.environ.get("RAMNET_S2D_2X4", "1") != "0"      # (environment: A/B runs of bench.py)
-
-
-def set_space_to_depth_2x4(on):
-    global _S2D_2X4
-    _S2D_2X4 = bool(on)
-
-
-def set_space_to_depth_fused(on):
-    global _S2D_FUSED
-    _S2D_FUSED = bool(on)
 
 
 def _s2d_fused(C):
@@ -1703,17 +1690,6 @@ def _folded_upsample_wgrad(x, skip, dy, y, cp, xpad=None):
         H.check(L.ramnet_frame_gather(_p(dy), _p(y), _p(g_rows), _p(g_cols), B, H2, W2, cp.Cout, _st()), "ramnet_frame_gather")
         # w[s] += a[s]^T g[s]: the border GEMMs' weight gradient (deterministic mode: the reduction slices joined in slice order through a buffer of the layer)
         gemm2(a_rows, g_rows, wr, a_cols, g_cols, wc, trans_a=True, accumulate=True, owner=cp)
-
-
-# Backward-data of the folded upsample-conv: the adjoint of (four parity convolutions of the replicate-padded input + border GEMMs),
-# i.e. conv_wino24_kernel over the parity sub-grids of dy * mask with the flipped filters -> gradient of the padded tensor ->
-# replicate-padding adjoint, plus the border GEMMs' adjoint scattered through the bilinear taps.  RAMNET_FOLD_DGRAD=0: direct 5x5 kernel on the full-resolution grid + bilinear adjoint.
-_FOLD_DGRAD = True
-
-
-def set_fold_dgrad(on):
-    global _FOLD_DGRAD
-    _FOLD_DGRAD = bool(on)
 
 
 def _fold_dgrad_ok(B, H2, W2, cp):
@@ -2167,45 +2143,6 @@ class GRUCell(Function):
         return (dxh[..., :Cc] if want_x else None), (dxh[..., Cc:] if want_h else None), None, None, None, None, None, None, None, None, None, None
 
 
-_TIME_BATCH = True
-
-
-_TIME_BATCH_MAX_DECODES = 0      # decodes per chain of the time-batched forward (0: a whole group)
-
-
-def set_time_batching(on, max_decodes=None):
-    """ERGB2DepthRecurrent.forward batches over TIME what does not depend on the order of the state updates (the event encoders of a
-    package as ONE chain at batch K x B, the decodes of a package in groups: model/model.py) — on by default, off for A/B runs and the
-    pass-by-pass path's tests.  max_decodes: split a decode group into chains of at most that many measurements (0 = no split)."""
-    global _TIME_BATCH, _TIME_BATCH_MAX_DECODES
-    _TIME_BATCH = bool(on)
-    if max_decodes is not None:
-        _TIME_BATCH_MAX_DECODES = int(max_decodes)
-
-
-def time_batch_max_decodes():
-    return _TIME_BATCH_MAX_DECODES
-
-
-def time_batching():
-    return _TIME_BATCH
-
-
-# A time-batched feature that is a ReLU output gets its ReLU mask where its gradient is summed (TimeSplit / TimeFan backward: one more
-# operand in an HBM-bound launch) instead of in the loaders of its layer's backward-data and backward-weights launches (two operands per
-# staged slot on the matrix kernels: RAMNET_IN_RELUMASK / gmask).  The same values reach the same products: bit-identical gradients.
-_RELU_PREMASK = True
-
-
-def set_relu_premask(on):
-    global _RELU_PREMASK
-    _RELU_PREMASK = bool(on)
-
-
-def get_relu_premask():
-    return _RELU_PREMASK
-
-
 def premask_relu_feature(y):
     """y = the output of a ConvAct with ReLU whose ONLY consumer is the TimeSplit / TimeFan the caller builds next (model/model.py): tell the
     layer's backward that the gradient it receives is already masked.  Returns whether the fan-in should apply the mask."""
@@ -2437,20 +2374,6 @@ class PredSigmoid(Function):
         H.check(H.lib().ramnet_pred_sigmoid_bwd(_p(x), ld(x), Cc, _p(w.detach()), _p(y), _p(dy), _p(dx), Cc,
                                                 _p(dw), _p(db), B * Hh * W, _st()), "pred_bwd")
         return dx, None, None
-
-
-_SI_FUSION = True
-
-
-def set_si_fusion(on):
-    """Scale-invariant loss of the supervised predictions inside the prediction layer's launches (PredSigmoidSI; trainer.sequence_loss
-    asks the model for it): on by default, off for A/B runs and the separate-launch path's tests."""
-    global _SI_FUSION
-    _SI_FUSION = bool(on)
-
-
-def si_fusion():
-    return _SI_FUSION
 
 
 class PredSigmoidSI(Function):
@@ -2712,24 +2635,8 @@ def multi_scale_grad_loss(prediction, target, num_scales=4):
 
 
 # ---- the gradient loss of a whole sequence as one batched operation (csrc/grad_loss.hip)
-_GRAD_LOSS_BATCHED = True
 _msg_tables = {}        # (device index, pointers of the pairs) -> int64 [2][G] device table
 _msg_workspaces = {}    # (device index, raw stream) -> float64 workspace of ramnet_grad_loss_stats (per-workgroup slots)
-
-
-def set_grad_loss_batched(on):
-    """trainer.sequence_loss forms the multi-scale gradient loss of all supervised maps of a sequence in ONE batched call after the
-    forward loop (multi_scale_grad_loss_batch: deterministic, no saved pyramid) — on by default; off: one multi_scale_grad_loss per
-    map, as before (A/B runs and the per-pair path's tests)."""
-    global _GRAD_LOSS_BATCHED
-    if not on and _DETERMINISTIC:
-        raise RuntimeError("set_grad_loss_batched(False) has no deterministic form: the unbatched multi-scale gradient loss joins by "
-                           "atomic adds (set_deterministic(True) is on)")
-    _GRAD_LOSS_BATCHED = bool(on)
-
-
-def grad_loss_batched():
-    return _GRAD_LOSS_BATCHED
 
 
 def _msg_pairs(preds, targets, what):

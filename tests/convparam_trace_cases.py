@@ -13,23 +13,23 @@ import torch
 from recipe import make_item
 from util import build_hip_model, ref_cfg
 
-# name -> [(setter, value, module global that holds the current value)].  The launch-side "force" switches ride with the backward-weights
+# name -> {switch: value}, in the order ops.switches applies them.  The launch-side "force" switches ride with the backward-weights
 # one: the maps of these networks are far below the sizes at which the library picks the F(2x4,3x3) / F(2x3,4x4) kernels by itself, and
 # the split-operand weight gradient replaces the F(2x4,3x3) one, so it needs that layout selected first.
-_FORCE = [("set_wgrad_winograd_2x4", "force", "_WGRAD_2X4"), ("set_winograd_2x4", "force", "_WINO_2X4"), ("set_fold_winograd_2x3", "force", "_FOLD_2X3")]
+_FORCE = {"wgrad_winograd_2x4": "force", "winograd_2x4": "force", "fold_winograd_2x3": "force"}
 SETTINGS = {
-    "defaults": [],
+    "defaults": {},
     "wgrad_2x4_force": _FORCE,
-    "split_operands": _FORCE + [("set_split_operands", True, "_SPLIT_OPERANDS"), ("set_split_wgrad", True, "_SPLIT_WGRAD")],
-    "winograd_off": [("set_winograd", False, "_WINOGRAD")],
-    "frozen_weight": [],
+    "split_operands": {**_FORCE, "split_operands": True, "split_wgrad": True},
+    "winograd_off": {"winograd": False},
+    "frozen_weight": {},
     # deterministic mode gives slabs to the direct, head and fold launches as well: with the decoders' one-launch form (F(2x2,4x4); at
-    # these map sizes F(2x3,4x4) only when forced) and as four direct parity launches.  set_deterministic goes last in, first out: the
-    # other switches refuse to change under it or it under them (ops.set_wgrad_slabs)
-    "deterministic": [("set_deterministic", True, "_DETERMINISTIC")],
-    "deterministic_fold_direct": [("set_fold_winograd_wgrad", False, "_FOLD_WINO_WGRAD"), ("set_deterministic", True, "_DETERMINISTIC")],
-    "deterministic_fold_2x3": [("set_fold_winograd_wgrad_2x3", "force", "_FOLD_WGRAD_2X3"), ("set_deterministic", True, "_DETERMINISTIC")],
-    "wgrad_atomic": [("set_wgrad_slabs", False, "_WGRAD_SLABS")],        # the tile splits meet in slab 0 by atomic adds; the joins still run
+    # these map sizes F(2x3,4x4) only when forced) and as four direct parity launches.  deterministic goes last in, first out: the
+    # other switches refuse to change under it or it under them (the guards of the rows of ops._SWITCHES)
+    "deterministic": {"deterministic": True},
+    "deterministic_fold_direct": {"fold_winograd_wgrad": False, "deterministic": True},
+    "deterministic_fold_2x3": {"fold_winograd_wgrad_2x3": "force", "deterministic": True},
+    "wgrad_atomic": {"wgrad_slabs": False},        # the tile splits meet in slab 0 by atomic adds; the joins still run
 }
 DETERMINISTIC = ("deterministic", "deterministic_fold_direct", "deterministic_fold_2x3")
 NETS = ("gru", "lstm", "unet")
@@ -106,38 +106,33 @@ def build(net):
 def run_case(net, setting, after_first_backward=None):
     """Forward, backward, an in-place update of every trained parameter, forward and backward again: the records of the two passes."""
     from rpg_ramnet_amd import _hip, ops
-    todo = SETTINGS[setting]
-    prev = [getattr(ops, g) for _, _, g in todo]
     rec = Recorder()
     passes = []
-    try:
-        for setter, value, _ in todo:
-            getattr(ops, setter)(value)
-        model, loss = build(net)
-        if setting == "frozen_weight":
-            hit = [p for k, p in model.named_parameters() if k.endswith(FROZEN)]
-            assert len(hit) == 1
-            hit[0].requires_grad_(False)
-        _hip.set_tracer(rec)
-        for i in range(2):
-            rec.calls = []
-            model.zero_grad()
-            loss().backward()
-            torch.cuda.synchronize()
-            passes.append(rec.calls)
-            if i == 0:
-                if after_first_backward is not None:
-                    _hip.set_tracer(None)
-                    after_first_backward(model)
-                    _hip.set_tracer(rec)
-                with torch.no_grad():
-                    for p in model.parameters():
-                        if p.grad is not None:
-                            p.add_(p.grad, alpha=-1e-3)
-    finally:
-        _hip.set_tracer(None)
-        for (setter, _, _), value in reversed(list(zip(todo, prev))):
-            getattr(ops, setter)(value)
+    with ops.switches(**SETTINGS[setting]):
+        try:
+            model, loss = build(net)
+            if setting == "frozen_weight":
+                hit = [p for k, p in model.named_parameters() if k.endswith(FROZEN)]
+                assert len(hit) == 1
+                hit[0].requires_grad_(False)
+            _hip.set_tracer(rec)
+            for i in range(2):
+                rec.calls = []
+                model.zero_grad()
+                loss().backward()
+                torch.cuda.synchronize()
+                passes.append(rec.calls)
+                if i == 0:
+                    if after_first_backward is not None:
+                        _hip.set_tracer(None)
+                        after_first_backward(model)
+                        _hip.set_tracer(rec)
+                    with torch.no_grad():
+                        for p in model.parameters():
+                            if p.grad is not None:
+                                p.add_(p.grad, alpha=-1e-3)
+        finally:
+            _hip.set_tracer(None)
     return passes
 
 

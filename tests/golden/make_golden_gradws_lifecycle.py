@@ -34,18 +34,17 @@ LAYERS = {
     "fold23_64_k5": ([64], 64, 5, "fold23"),
     "fold_direct_64_k5": ([64], 64, 5, "fold_direct"),
 }
-# row -> (layer, deterministic, set_wgrad_winograd_2x4, further (setter, value, module global), end of a pass)
+# row -> (layer, deterministic, wgrad_winograd_2x4, further {switch: value} of ops.switches, end of a pass)
 ROWS = {}
 for _det in (False, True):
     for _w24 in ("auto", "force"):
         for _layer in LAYERS:
             if _layer != "fold_direct_64_k5" or _det:
-                ROWS["%s/det%d/%s" % (_layer, _det, _w24)] = (_layer, _det, _w24, [], "flush")
-ROWS["k3_64_wino/wgrad_atomic"] = ("k3_64_wino", False, "auto", [("set_wgrad_slabs", False, "_WGRAD_SLABS")], "flush")
-ROWS["k3_64_wino/split_operands"] = ("k3_64_wino", False, "force", [("set_split_operands", True, "_SPLIT_OPERANDS"),
-                                                                    ("set_split_wgrad", True, "_SPLIT_WGRAD")], "flush")
-ROWS["k3_64_wino/winograd_off"] = ("k3_64_wino", False, "auto", [("set_winograd", False, "_WINOGRAD")], "flush")
-ROWS["k3_64_wino/discard"] = ("k3_64_wino", False, "auto", [], "discard")
+                ROWS["%s/det%d/%s" % (_layer, _det, _w24)] = (_layer, _det, _w24, {}, "flush")
+ROWS["k3_64_wino/wgrad_atomic"] = ("k3_64_wino", False, "auto", {"wgrad_slabs": False}, "flush")
+ROWS["k3_64_wino/split_operands"] = ("k3_64_wino", False, "force", {"split_operands": True, "split_wgrad": True}, "flush")
+ROWS["k3_64_wino/winograd_off"] = ("k3_64_wino", False, "auto", {"winograd": False}, "flush")
+ROWS["k3_64_wino/discard"] = ("k3_64_wino", False, "auto", {}, "discard")
 
 
 class Recorder:
@@ -116,39 +115,34 @@ def run_row(row):
     """The record of one row: two passes of one layer."""
     from rpg_ramnet_amd import _hip, ops
     layer, det, w24, extra, end = ROWS[row]
-    todo = [("set_wgrad_winograd_2x4", w24, "_WGRAD_2X4")] + extra + [("set_deterministic", det, "_DETERMINISTIC")]
-    prev = [getattr(ops, g) for _, _, g in todo]
     rec, st, out = Recorder(), ops._st, []
-    try:
-        for setter, value, _ in todo:
-            getattr(ops, setter)(value)
-        ops._st = lambda: None
-        _hip.set_tracer(rec)
-        cp = _layer(layer)
-        for _ in range(2):
-            rec.calls = []
-            ws, taps, wino24 = _ask(cp, LAYERS[layer][3])
-            x0, dout = torch.zeros(1, 8, 8, cp.CinWs), torch.zeros(1, 8, 8, cp.Cout)
-            d = ops._wgrad_desc_build(x0, taps, dout, ws, cp.Cout, 1, None, None, 0, _hip.IN_PLAIN, None, 0, None, None, None, None, None, None,
-                                      None, 0, wino24)
-            p = {"layout": list(ops._layout_of(ws)), "det_slabs": ops._det_slabs(ws), "head_cin": getattr(ws, "head_cin", 0),
-                 "dw_slabs": d.dw_slabs, "algo": d.algo, "numel": {n: (None if t is None else t.numel()) for n, t in workspaces(cp)}}
-            for _, t in workspaces(cp):
-                if t is not None:
-                    t.fill_(1.0)
-            rec.watch(cp)
-            if end == "discard":
-                ops._Engine.reset()                 # (cp.discard() of every layer of the aborted pass)
-            else:
-                ops._Engine.flush()
-            p["calls"] = rec.calls
-            p["zero_runs"] = {n: zero_runs(t) for n, t in workspaces(cp) if t is not None}
-            out.append(p)
-    finally:
-        _hip.set_tracer(None)
-        ops._st = st
-        for (setter, _, _), value in reversed(list(zip(todo, prev))):
-            getattr(ops, setter)(value)
+    with ops.switches(wgrad_winograd_2x4=w24, **extra, deterministic=det):
+        try:
+            ops._st = lambda: None
+            _hip.set_tracer(rec)
+            cp = _layer(layer)
+            for _ in range(2):
+                rec.calls = []
+                ws, taps, wino24 = _ask(cp, LAYERS[layer][3])
+                x0, dout = torch.zeros(1, 8, 8, cp.CinWs), torch.zeros(1, 8, 8, cp.Cout)
+                d = ops._wgrad_desc_build(x0, taps, dout, ws, cp.Cout, 1, None, None, 0, _hip.IN_PLAIN, None, 0, None, None, None, None, None,
+                                          None, None, 0, wino24)
+                p = {"layout": list(ops._layout_of(ws)), "det_slabs": ops._det_slabs(ws), "head_cin": getattr(ws, "head_cin", 0),
+                     "dw_slabs": d.dw_slabs, "algo": d.algo, "numel": {n: (None if t is None else t.numel()) for n, t in workspaces(cp)}}
+                for _, t in workspaces(cp):
+                    if t is not None:
+                        t.fill_(1.0)
+                rec.watch(cp)
+                if end == "discard":
+                    ops._Engine.reset()                 # (cp.discard() of every layer of the aborted pass)
+                else:
+                    ops._Engine.flush()
+                p["calls"] = rec.calls
+                p["zero_runs"] = {n: zero_runs(t) for n, t in workspaces(cp) if t is not None}
+                out.append(p)
+        finally:
+            _hip.set_tracer(None)
+            ops._st = st
     return out
 
 

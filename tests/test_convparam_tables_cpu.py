@@ -50,11 +50,8 @@ def test_stamped_layout_reaches_the_descriptor(kind, slabs_on):
     ws = ops._stamp_layout(torch.zeros(4), kind, 5)
     assert ops._layout_of(ws) == (kind, 5)
     assert (ws.wino, ws.wino6, ws.wg_dsplit, ws.slabs, ws.head_cin) == (kind == "wino", kind == "wino6", kind == "dsplit", 5, 0)
-    ops.set_wgrad_slabs(slabs_on)
-    try:
+    with ops.switches(wgrad_slabs=slabs_on):
         d = desc(ws)
-    finally:
-        ops.set_wgrad_slabs(True)
     assert d.algo == ALGO[kind]
     assert d.dw_slabs == (5 if slabs_on and kind != "direct" else 0)
     assert d.head_cin == 0

@@ -138,9 +138,8 @@ def test_fold_rows_are_what_the_issue_states():
 
 def test_the_switch_round_trips_and_the_conflicting_settings_raise():
     from rpg_ramnet_amd import ops
-    old = ops.deterministic()
-    try:
-        assert old is False                         # off by default
+    assert ops.deterministic() is False             # off by default
+    with ops.switches(wgrad_slabs=True, grad_loss_batched=True, deterministic=False):       # (the body's own changes are put back as well)
         ops.set_deterministic(True)
         assert ops.deterministic() is True
         for setter in (ops.set_wgrad_slabs, ops.set_grad_loss_batched):
@@ -160,17 +159,10 @@ def test_the_switch_round_trips_and_the_conflicting_settings_raise():
                 assert ops.deterministic() is False
             finally:
                 setter(True)
-    finally:
-        ops.set_wgrad_slabs(True)
-        ops.set_grad_loss_batched(True)
-        ops.set_deterministic(old)
 
 
 def test_the_trainer_key_is_read_and_defaults_to_false():
     from rpg_ramnet_amd import ops, trainer
-    old = ops.deterministic()
-    try:
+    with ops.switches(deterministic=ops.deterministic()):           # (what the trainer sets is put back)
         assert trainer.apply_deterministic_config({"trainer": {}}) is False and trainer.apply_deterministic_config({}) is False
         assert trainer.apply_deterministic_config({"trainer": {"deterministic": True}}) is True and ops.deterministic()
-    finally:
-        ops.set_deterministic(old)

@@ -57,13 +57,10 @@ def test_argument_errors_are_raised_before_the_library_is_touched(monkeypatch):
 def test_option_getter_and_setter():
     from rpg_ramnet_amd import ops
     assert ops.grad_loss_batched() is True                     # default: on
-    try:
-        ops.set_grad_loss_batched(False)
+    with ops.switches(grad_loss_batched=False):
         assert ops.grad_loss_batched() is False
         ops.set_grad_loss_batched(1)
         assert ops.grad_loss_batched() is True
-    finally:
-        ops.set_grad_loss_batched(True)
 
 
 def test_header_and_ctypes_table_carry_the_entry_points():

@@ -10,7 +10,6 @@ NaN targets.  The NaN pixels are drawn outside a 24 x 24 corner of every target 
 NaN spread over the whole map no 8 x 8 cell of the coarsest scale of the gradient loss is valid at this size and the loss VALUE is NaN in
 either mode (the gradients stay finite), which would leave nothing to compare.  Every test sets the mode inside try / finally and restores
 it, and the schedule switches to what they were."""
-import contextlib
 import sys
 
 import numpy as np
@@ -52,21 +51,9 @@ def _targets_with_nan(rng, it, frac=0.2, keep=24):
     return it
 
 
-@contextlib.contextmanager
 def bench_schedule(det):
     from rpg_ramnet_amd import ops
-    old = (ops.deterministic(), ops._USE_SIDE, ops.decoder_overlap(), ops.wgrad_defer())
-    try:
-        ops.set_wgrad_overlap(True)
-        ops.set_decoder_overlap(True)
-        ops.set_wgrad_defer(2)
-        ops.set_deterministic(det)
-        yield
-    finally:
-        ops.set_deterministic(old[0])
-        ops.set_wgrad_defer(old[3])
-        ops.set_decoder_overlap(old[2])
-        ops.set_wgrad_overlap(old[1])
+    return ops.switches(wgrad_overlap=True, decoder_overlap=True, wgrad_defer=2, deterministic=det)
 
 
 def _seq(model, seed, irregular=False):
@@ -191,9 +178,7 @@ def test_input_pipeline_from_raw_events_gives_the_same_tensors():
     cat, off, mx = voxel.pack_event_lists(lists, dev)
     params = augment.ParamTable([augment.draw(D.Compose([D.RandomRotationFlip(20.0, 0.5, 0.5), D.RandomCrop((H, W))]), s, Hs, Ws)
                                  for s in range(G)], Hs, Ws).to(dev)
-    old = ops.deterministic()
-    try:
-        ops.set_deterministic(True)
+    with ops.switches(deterministic=True):
         runs = []
         for _ in range(3):
             out = augment.voxelize_augmented(cat, off, mx, bins, Ws, Hs, params)
@@ -206,8 +191,6 @@ def test_input_pipeline_from_raw_events_gives_the_same_tensors():
                 assert torch.equal(a, b)
         assert torch.equal(runs[0][-1], runs[0][-2][1]), "one list through the sorted form == its grid in the batch"
         assert float(runs[0][-2][2].abs().max()) == 0.0 and float(runs[0][-2][0].abs().max()) > 0.0
-    finally:
-        ops.set_deterministic(old)
     ref = voxel.events_to_voxel_grids(lists, bins, Ws, Hs, device=dev, normalize=True)           # the default mode: the same grids up to the fp64 sums' last bits
     assert_close(runs[0][-2].cpu().numpy(), ref.cpu().numpy(), 1e-6, "deterministic vs default grids")
 
@@ -232,8 +215,7 @@ def test_operations_without_an_ordered_form_raise_in_the_mode_and_work_outside_i
     refused = {"mse_loss": lambda: ops.mse_loss(pred, target), "multi_scale_grad_loss": lambda: ops.multi_scale_grad_loss(pred, target),
                "depth_metrics": lambda: metrics.depth_metrics(pred, target, 80.0, 3.70378), "unsorted voxeliser": unsorted,
                "set_wgrad_slabs": lambda: ops.set_wgrad_slabs(False), "set_grad_loss_batched": lambda: ops.set_grad_loss_batched(False)}
-    old = ops.deterministic()
-    try:
+    with ops.switches(wgrad_slabs=True, grad_loss_batched=True, deterministic=False):          # (the body's own changes are put back as well)
         for name, fn in refused.items():
             ops.set_deterministic(False)
             fn()                                    # works as before outside the mode
@@ -256,10 +238,6 @@ def test_operations_without_an_ordered_form_raise_in_the_mode_and_work_outside_i
             with pytest.raises(RuntimeError):
                 ops.set_deterministic(True)
             setter(True)
-    finally:
-        ops.set_wgrad_slabs(True)
-        ops.set_grad_loss_batched(True)
-        ops.set_deterministic(old)
     torch.cuda.synchronize()
 
 
@@ -288,9 +266,7 @@ def test_the_fused_prediction_layer_refuses_its_atomic_fall_back_and_the_si_loss
         return w.grad
 
     pred = torch.rand(2, 1, 16, 24, generator=g).to(dev)
-    old = ops.deterministic()
-    try:
-        ops.set_deterministic(False)
+    with ops.switches(deterministic=False):
         assert bool(torch.isfinite(fused(True)).all())          # the atomic fall-back works outside the mode
         ops.set_deterministic(True)
         assert L_.ramnet_get_option(b"ordered_only") == 1
@@ -312,5 +288,3 @@ def test_the_fused_prediction_layer_refuses_its_atomic_fall_back_and_the_si_loss
         graph.replay()
         torch.cuda.synchronize()
         assert np.isfinite(float(out))
-    finally:
-        ops.set_deterministic(old)

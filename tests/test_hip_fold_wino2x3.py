@@ -24,13 +24,9 @@ def fold2x3():
     """The folded Winograd path (forward, backward-data through the folded adjoint, Winograd-domain backward-weights) with F(2x3,4x4)
     on every structurally eligible forward / backward-data launch; records which descriptors took it."""
     from rpg_ramnet_amd import ops
-    old = (ops.get_fold_upsample(), ops._FOLD_WINO, ops._FOLD_WINO_WGRAD, ops._FOLD_DGRAD)
-    ops.set_fold_upsample(True), ops.set_fold_winograd(True), ops.set_fold_winograd_wgrad(True), ops.set_fold_dgrad(True)
-    ops.set_fold_winograd_2x3("force")
-    ops._DESC_CACHE.clear()
-    yield ops
-    ops.set_fold_winograd_2x3("auto")
-    ops.set_fold_upsample(old[0]), ops.set_fold_winograd(old[1]), ops.set_fold_winograd_wgrad(old[2]), ops.set_fold_dgrad(old[3])
+    with ops.switches(fold_upsample=True, fold_winograd=True, fold_winograd_wgrad=True, fold_dgrad=True, fold_winograd_2x3="force"):
+        ops._DESC_CACHE.clear()
+        yield ops
 
 
 def _kinds(ops):

@@ -25,13 +25,9 @@ def ptr(t):
 def wgrad2x3():
     """The folded Winograd path with F(2x3,4x4) forced on the backward-weights launches (forward / backward-data stay on "auto")."""
     from rpg_ramnet_amd import ops
-    old = (ops.get_fold_upsample(), ops._FOLD_WINO, ops._FOLD_WINO_WGRAD, ops._FOLD_DGRAD)
-    ops.set_fold_upsample(True), ops.set_fold_winograd(True), ops.set_fold_winograd_wgrad(True), ops.set_fold_dgrad(True)
-    ops.set_fold_winograd_wgrad_2x3("force")
-    ops._WDESC_CACHE.clear()
-    yield ops
-    ops.set_fold_winograd_wgrad_2x3("auto")
-    ops.set_fold_upsample(old[0]), ops.set_fold_winograd(old[1]), ops.set_fold_winograd_wgrad(old[2]), ops.set_fold_dgrad(old[3])
+    with ops.switches(fold_upsample=True, fold_winograd=True, fold_winograd_wgrad=True, fold_dgrad=True, fold_winograd_wgrad_2x3="force"):
+        ops._WDESC_CACHE.clear()
+        yield ops
 
 
 def _algos(ops):

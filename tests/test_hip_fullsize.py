@@ -32,13 +32,8 @@ def bench_schedule():
     """bench.py's default schedule: backward-weights on a side stream (the ConvGRU cells' launches in pairs of updates), decoders on a
     second stream."""
     from rpg_ramnet_amd import ops
-    ops.set_wgrad_overlap(True)
-    ops.set_decoder_overlap(True)
-    ops.set_wgrad_defer(2)
-    yield
-    ops.set_wgrad_overlap(False)
-    ops.set_decoder_overlap(False)
-    ops.set_wgrad_defer(0)
+    with ops.switches(wgrad_overlap=True, decoder_overlap=True, wgrad_defer=2):
+        yield
 
 
 @pytest.fixture(params=["f2x4", "f2x2"])
@@ -46,9 +41,8 @@ def wgrad_algo(request):
     """Both backward-weights kernels of the plain 3x3 layers at the real shapes: F(2x4,3x3) (what the co-scheduled step selects) and
     F(2x2,3x3) in its 32 x 64-channel shape."""
     from rpg_ramnet_amd import ops
-    ops.set_wgrad_winograd_2x4("auto" if request.param == "f2x4" else "off")
-    yield request.param
-    ops.set_wgrad_winograd_2x4("auto")
+    with ops.switches(wgrad_winograd_2x4="auto" if request.param == "f2x4" else "off"):
+        yield request.param
 
 
 def run_pair64(module, oracle_fn, inputs, input_grads=True, seed=0):
@@ -279,11 +273,8 @@ def test_bench_step_B8_L8_vs_oracle_split_operands(bench_schedule):
     """the bench step of test_bench_step_B8_L8_vs_oracle with the F(2x4,3x3) forward / backward-data launches on split bf16
     operands (ops.set_split_operands; csrc/conv_wino6s.hip) — loss and all 70 gradients against the float64 oracle at the UNCHANGED bounds."""
     from rpg_ramnet_amd import ops
-    ops.set_split_operands(True)
-    try:
+    with ops.switches(split_operands=True):
         _training_step_vs_oracle("bench_B8_L8")
-    finally:
-        ops.set_split_operands(False)
 
 
 def test_config4_shape_training_step_vs_oracle(bench_schedule):
@@ -364,11 +355,8 @@ def wino_variant(request):
     TRAINING batch runs, driven here through the long sequences that only fit the checker's time budget at batch 1; f2x4_split: the same
     launches with split bf16 operands on the bf16 matrix pipe (csrc/conv_wino6s.hip) — at the SAME bounds, ELEM_FLOOR included."""
     from rpg_ramnet_amd import ops
-    ops.set_winograd_2x4("auto" if request.param == "auto" else "force")
-    ops.set_split_operands(request.param == "f2x4_split")
-    yield request.param
-    ops.set_winograd_2x4("auto")
-    ops.set_split_operands(False)
+    with ops.switches(winograd_2x4="auto" if request.param == "auto" else "force", split_operands=request.param == "f2x4_split"):
+        yield request.param
 
 
 def _close_to_fixture(z, key, got, tol, what):

@@ -240,9 +240,8 @@ def test_sequence_loss_uses_one_batched_call_and_agrees_with_the_per_pair_path()
             assert not any(c.startswith("ramnet_msg_loss") for c in on[3])
             counts[L] = [sum(c == n for c in on[3]) for n in ("ramnet_grad_loss_stats", "ramnet_grad_loss_bwd")]
         assert counts[1] == counts[2] == [1, 1]                       # independent of L (and of the number of supervised maps)
-        ops.set_grad_loss_batched(False)
-        off = _run(model, seq, lc, calls)
-        ops.set_grad_loss_batched(True)
+        with ops.switches(grad_loss_batched=False):
+            off = _run(model, seq, lc, calls)
         assert sum(c == "ramnet_msg_loss_fwd" for c in off[3]) == 2 * len(lc) and "ramnet_grad_loss_stats" not in off[3]
         _same(on, off, "batched vs per-pair")
         dp = _run(model, seq, lc, calls, dp_exact=True)                # a single process: world 1
@@ -250,7 +249,6 @@ def test_sequence_loss_uses_one_batched_call_and_agrees_with_the_per_pair_path()
         assert not any(c.startswith("ramnet_msg_loss") for c in dp[3])
         _same(dp, on, "dp_exact vs plain")
     finally:
-        ops.set_grad_loss_batched(True)
         Hh.set_tracer(None)
     step = graph.GraphedTrainStep(model, seq, lc, [1.0, 0.5], grad_loss_weight=0.25)
     total, _ = step()

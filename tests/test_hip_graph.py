@@ -108,8 +108,7 @@ def test_graphed_package_equals_model_forward(monkeypatch):
     rng = np.random.default_rng(3)
     items = [make_item(rng, 2, 32, 48, 3, 5, 1) for _ in range(2)]
     for overlap in (False, True):
-        ops.set_decoder_overlap(overlap)
-        try:
+        with ops.switches(decoder_overlap=overlap):
             gp = GraphedPackage(model, items[0])
             prev, lstm = None, ramnet_ref.empty_states_lstm(3)
             for item in items:
@@ -120,8 +119,6 @@ def test_graphed_package_equals_model_forward(monkeypatch):
                 assert list(got.keys()) == list(want.keys())
                 for k in want:
                     assert torch.equal(got[k], want[k]), (overlap, k)
-        finally:
-            ops.set_decoder_overlap(False)
 
 
 @pytest.mark.parametrize("schedule", ["single_stream", "three_streams"])
@@ -136,9 +133,7 @@ def test_graphed_train_step_equals_eager_steps(schedule):
     rng = np.random.default_rng(4)
     seq = [make_item(rng, 2, 32, 48, 2, 5, 1, True, 0.1) for _ in range(2)]
     on = schedule == "three_streams"
-    ops.set_wgrad_overlap(on)
-    ops.set_decoder_overlap(on)
-    try:
+    with ops.switches(wgrad_overlap=on, decoder_overlap=on):
         losses, weights = {}, {}
         for mode in ("eager", "graph"):
             model = build_hip_model("ERGB2DepthRecurrent", cfg).train()
@@ -174,9 +169,6 @@ def test_graphed_train_step_equals_eager_steps(schedule):
             assert worst[0][0] / scale < 5e-3, "gradients of step %d: %s (scale %.2e)" % (i, worst, scale)
         assert float((weights["graph"] - weights["eager"]).abs().max()) < 2e-5
         assert losses["graph"][2][0] != losses["graph"][0][0]          # the steps really trained
-    finally:
-        ops.set_wgrad_overlap(False)
-        ops.set_decoder_overlap(False)
 
 
 @pytest.mark.parametrize("with_reducer", [False, True])
@@ -228,8 +220,7 @@ def test_branch_streams_equal_serial_updates():
         item = make_item(rng, B, H, W, 5, 5, 1)
         outs = {}
         for on in (False, True):
-            ops.set_branch_overlap(on)
-            try:
+            with ops.switches(branch_overlap=on):
                 st = model.init_states(B, H, W)
                 preds = []
                 with torch.no_grad():
@@ -238,8 +229,6 @@ def test_branch_streams_equal_serial_updates():
                         preds.append(model.decode(st))
                 torch.cuda.synchronize()
                 outs[on] = (preds, st)
-            finally:
-                ops.set_branch_overlap(False)
         for a, b in zip(outs[False][0], outs[True][0]):
             assert torch.equal(a, b)
         for a, b in zip(outs[False][1], outs[True][1]):

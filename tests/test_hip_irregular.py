@@ -28,14 +28,9 @@ def bits(t):
 def family(request):
     """Force each family a cell launch can take: the direct implicit GEMM, F(2x2,3x3), F(2x4,3x3), F(2x4,3x3) on split operands."""
     from rpg_ramnet_amd import ops
-    old = ops.get_winograd()
-    ops.set_winograd(request.param != "igemm")
-    ops.set_winograd_2x4("force" if request.param.startswith("f2x4") else "off")
-    ops.set_split_operands(request.param == "f2x4_split")
-    yield request.param
-    ops.set_winograd(old)
-    ops.set_winograd_2x4("auto")
-    ops.set_split_operands(False)
+    with ops.switches(winograd=request.param != "igemm", winograd_2x4="force" if request.param.startswith("f2x4") else "off",
+                      split_operands=request.param == "f2x4_split"):
+        yield request.param
 
 
 CELL_CASES = [(3, 8, 16, 64, [1, 0, 1]), (2, 16, 32, 128, [0, 1]), (4, 4, 43, 256, [0, 1, 1, 0]),

@@ -40,11 +40,8 @@ def last_kernel():
 def forced():
     """Every structurally eligible forward / backward-data launch on F(2x4,3x3), backward-weights on its F(2x4,3x3) kernel."""
     from rpg_ramnet_amd import ops
-    ops.set_winograd_2x4("force")
-    ops.set_wgrad_winograd_2x4("force")
-    yield
-    ops.set_winograd_2x4("auto")
-    ops.set_wgrad_winograd_2x4("auto")
+    with ops.switches(winograd_2x4="force", wgrad_winograd_2x4="force"):
+        yield
 
 
 def _lstm_param(C, seed=11):
@@ -92,15 +89,12 @@ def test_lstm_cell_raw(B, H, W, C):
     xg, hg, cg = (nhwc(t).to(dev()) for t in (x, h, c))
     outs = {}
     for mode in ("force", "off"):
-        ops.set_winograd_2x4(mode)
-        try:
+        with ops.switches(winograd_2x4=mode):
             outs[mode] = _launch(cp, xg, hg, cg, C)
             if mode == "force":
                 again = _launch(cp, xg, hg, cg, C)
                 nocell = _launch(cp, xg, hg, None, C)
                 infer = _launch(cp, xg, hg, cg, C, gates=False)
-        finally:
-            ops.set_winograd_2x4("auto")
     assert outs["force"][3].startswith(R6) and "lstm" in outs["force"][3], outs["force"][3]
     assert outs["off"][3].startswith("conv_wino_r_kernel"), outs["off"][3]
     assert nocell[3].startswith(R6) and infer[3].startswith(R6)
@@ -319,8 +313,7 @@ def test_conv_lstm_full_size_auto(C, div, monkeypatch):
     from rpg_ramnet_amd.model.submodules import ConvLSTM
     seen, orig, spy = _spy_kernels()
     monkeypatch.setattr(ops, "conv_launch", spy)
-    ops.set_wgrad_overlap(True)
-    try:
+    with ops.switches(wgrad_overlap=True):
         torch.manual_seed(30 + div)
         m = ConvLSTM(C, C, 3)
         with torch.no_grad():
@@ -339,8 +332,6 @@ def test_conv_lstm_full_size_auto(C, div, monkeypatch):
                 return torch.cat(self.L(a, (hh, cc)), 3)
 
         run_pair64(Both(), lambda sd, a, hh, cc: torch.cat(ramnet_ref.conv_lstm(sd, "L", a, (hh, cc)), 1), [x, h, c])
-    finally:
-        ops.set_wgrad_overlap(False)
     assert [k for e, k in seen if e == Hh.EPI_LSTM] and all(k.startswith(R6) for e, k in seen), seen
 
 
@@ -352,11 +343,8 @@ def test_reference_golden_forward_lstm_f2x4(tag, monkeypatch):
     from rpg_ramnet_amd import ops, _hip as Hh
     seen, orig, spy = _spy_kernels()
     monkeypatch.setattr(ops, "conv_launch", spy)
-    ops.set_winograd_2x4("force")
-    try:
+    with ops.switches(winograd_2x4="force"):
         thm.run_fixture(tag)
-    finally:
-        ops.set_winograd_2x4("auto")
     cells = [k for e, k in seen if e == Hh.EPI_LSTM]
     assert any(k.startswith(R6) for k in cells), sorted(set(cells))
     if tag != "seeded_ramnet_lstm":
@@ -406,11 +394,8 @@ def lstm_variant(request):
     scales' cell launches (352 and 176 workgroups against the threshold of 150) already run F(2x4); f2x4: every eligible launch forced;
     f2x4_split: the same with split operands (the cell launch stays on the exact-fp32 kernel, the other 3x3 layers split)."""
     from rpg_ramnet_amd import ops
-    ops.set_winograd_2x4({"off": "off", "auto": "auto"}.get(request.param, "force"))
-    ops.set_split_operands(request.param == "f2x4_split")
-    yield request.param
-    ops.set_winograd_2x4("auto")
-    ops.set_split_operands(False)
+    with ops.switches(winograd_2x4={"off": "off", "auto": "auto"}.get(request.param, "force"), split_operands=request.param == "f2x4_split"):
+        yield request.param
 
 
 class _Worst:

@@ -62,11 +62,8 @@ def test_reference_golden_forward_f2x4(tag):
     """The same reference-generated fixtures with every eligible 3x3 launch forced onto the F(2x4,3x3) kernel (csrc/conv_wino6.hip; the
     library's size test would keep these small maps on F(2x2,3x3)): 1e-3 max-norm and element-wise, ragged 2 x 4 tilings included."""
     from rpg_ramnet_amd import ops
-    ops.set_winograd_2x4("force")
-    try:
+    with ops.switches(winograd_2x4="force"):
         run_fixture(tag)
-    finally:
-        ops.set_winograd_2x4("auto")
 
 
 @pytest.mark.parametrize("tag", ["small_gru", "small_lstm", "small_gru_enclstm", "small_tconv", "small_base_rgb",
@@ -214,9 +211,8 @@ def test_bptt_gradients_vs_reference_fixture(tag):
 @pytest.fixture
 def wgrad_overlap():
     from rpg_ramnet_amd import ops
-    ops.set_wgrad_overlap(True)
-    yield
-    ops.set_wgrad_overlap(False)
+    with ops.switches(wgrad_overlap=True):
+        yield
 
 
 def test_wgrad_side_stream_gradients(wgrad_overlap):
@@ -231,11 +227,11 @@ def test_wgrad_side_stream_gradients(wgrad_overlap):
     seq = [make_item(rng, 2, 32, 48, 3, 5, cfg["num_bins_rgb"], True, 0.1) for _ in range(3)]
     grads = {}
     for on in (True, False, True):
-        ops.set_wgrad_overlap(on)
-        model.zero_grad()
-        total, _ = sequence_loss(model, seq, cfg["loss_composition"], [1, 1])
-        total.backward()
-        torch.cuda.synchronize()
+        with ops.switches(wgrad_overlap=on):
+            model.zero_grad()
+            total, _ = sequence_loss(model, seq, cfg["loss_composition"], [1, 1])
+            total.backward()
+            torch.cuda.synchronize()
         g = {k: p.grad.detach().clone() for k, p in model.named_parameters()}
         gmax = max(float(v.abs().max()) for v in g.values())
         if on in grads:     # run-to-run: only the order of the atomic partial sums differs (pred.bias cancels to ~1e-6: floor)
@@ -269,18 +265,17 @@ def test_relu_premask_in_the_time_fan_in_same_gradients():
         return fn(*args)
     try:
         for on in (True, False):
-            ops.set_relu_premask(on)
             calls["masked"] = 0
-            Hh.set_tracer(tracer)
-            model.zero_grad()
-            total, _ = sequence_loss(model, seq, cfg["loss_composition"], [1, 1])
-            total.backward()
-            torch.cuda.synchronize()
-            Hh.set_tracer(None)
+            with ops.switches(relu_premask=on):
+                Hh.set_tracer(tracer)
+                model.zero_grad()
+                total, _ = sequence_loss(model, seq, cfg["loss_composition"], [1, 1])
+                total.backward()
+                torch.cuda.synchronize()
+                Hh.set_tracer(None)
             assert (calls["masked"] > 0) == on, "the masked fan-in runs exactly when the switch is on"
             res[on] = (float(total.detach()), {k: p.grad.detach().clone() for k, p in model.named_parameters()})
     finally:
-        ops.set_relu_premask(True)
         Hh.set_tracer(None)
     assert res[True][0] == res[False][0]
     gmax = max(float(v.abs().max()) for v in res[True][1].values())
@@ -299,10 +294,8 @@ def test_decoder_stream_overlap_same_results():
     rng = np.random.default_rng(7)
     seq = [make_item(rng, 2, 32, 48, 3, 5, cfg["num_bins_rgb"], True, 0.1) for _ in range(3)]
     res = {}
-    try:
-        for on in (False, True, True):
-            ops.set_decoder_overlap(on)
-            ops.set_wgrad_overlap(on)
+    for on in (False, True, True):
+        with ops.switches(decoder_overlap=on, wgrad_overlap=on):
             model.zero_grad()
             with torch.no_grad():
                 preds, _, _ = model(seq[0], None, ramnet_ref.empty_states_lstm(cfg["every_x_rgb_frame"]))
@@ -311,9 +304,6 @@ def test_decoder_stream_overlap_same_results():
             torch.cuda.synchronize()
             res[on] = ({k: v.clone() for k, v in preds.items()}, float(total.detach()),
                        {k: p.grad.detach().clone() for k, p in model.named_parameters()})
-    finally:
-        ops.set_decoder_overlap(False)
-        ops.set_wgrad_overlap(False)
     for k in res[False][0]:
         assert torch.equal(res[False][0][k], res[True][0][k]), k
     assert res[False][1] == res[True][1]
@@ -384,8 +374,7 @@ def test_time_batched_forward_equals_pass_by_pass(lc, full_frame, state):
             it.setdefault("depth_" + k, it["depth_image"].clone())
     res = {}
     for on in (True, False):
-        ops.set_time_batching(on)
-        try:
+        with ops.switches(time_batching=on):
             model.zero_grad()
             total, _ = sequence_loss(model, seq, keys, [1, 1])
             total.backward()
@@ -400,8 +389,6 @@ def test_time_batched_forward_equals_pass_by_pass(lc, full_frame, state):
                     outs.append(([preds[k].clone() for k in preds], [t for k in supers for t in flat(supers[k])],
                                  [t for k in lstm for t in flat(lstm[k]["state_comb"])]))
             res[on] = (float(total.detach()), grads, outs)
-        finally:
-            ops.set_time_batching(True)
     np.testing.assert_allclose(res[True][0], res[False][0], rtol=1e-5)
     for (pa, sa, la), (pb, sb, lb) in zip(res[True][2], res[False][2]):
         for a, c in zip(pa + sa + la, pb + sb + lb):
@@ -513,15 +500,14 @@ def test_scale_invariant_loss_inside_the_prediction_layer(lc, nan, gw):
     res = {}
     try:
         for on in (True, False):
-            ops.set_si_fusion(on)
             calls.clear()
-            model.zero_grad()
-            total, rep = sequence_loss(model, seq, lc, [1.0, 0.5, 2.0][:len(lc)], grad_loss_weight=gw)
-            total.backward()
-            torch.cuda.synchronize()
+            with ops.switches(si_fusion=on):
+                model.zero_grad()
+                total, rep = sequence_loss(model, seq, lc, [1.0, 0.5, 2.0][:len(lc)], grad_loss_weight=gw)
+                total.backward()
+                torch.cuda.synchronize()
             res[on] = (float(total.detach()), float(rep), {k: p.grad.clone() for k, p in model.named_parameters()}, list(calls))
     finally:
-        ops.set_si_fusion(True)
         Hh.set_tracer(None)
     assert not any(c.startswith("ramnet_si_loss") for c in res[True][3]) and "ramnet_pred_sigmoid_si_fwd" in res[True][3]
     assert sum(c == "ramnet_si_loss_fwd" for c in res[False][3]) == L * len(lc)
@@ -744,14 +730,8 @@ def test_training_trajectory_matches_oracle(arith):
     launch forced onto F(2x4,3x3) with split bf16 operands (csrc/conv_wino6s.hip) — the same bound."""
     from rpg_ramnet_amd import ops
     from rpg_ramnet_amd.trainer import sequence_loss
-    if arith == "split_operands":
-        ops.set_winograd_2x4("force")
-        ops.set_split_operands(True)
-    try:
+    with ops.switches(**(dict(winograd_2x4="force", split_operands=True) if arith == "split_operands" else {})):
         _training_trajectory(sequence_loss)
-    finally:
-        ops.set_winograd_2x4("auto")
-        ops.set_split_operands(False)
 
 
 def _training_trajectory(sequence_loss):

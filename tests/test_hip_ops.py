@@ -68,12 +68,8 @@ def stride2_algo(request):
     """5x5 stride-2 layers: 3x3 Winograd over the space-to-depth view read in place (default; channel counts that are not a
     power of two >= 32 materialise it), over the materialised view, and the direct stride-2 kernels."""
     from rpg_ramnet_amd import ops
-    old, oldf = ops.get_space_to_depth(), ops._S2D_FUSED
-    ops.set_space_to_depth(request.param != "direct")
-    ops.set_space_to_depth_fused(request.param == "s2d")
-    yield request.param
-    ops.set_space_to_depth(old)
-    ops.set_space_to_depth_fused(oldf)
+    with ops.switches(space_to_depth=request.param != "direct", space_to_depth_fused=request.param == "s2d"):
+        yield request.param
 
 
 @pytest.mark.parametrize("B,H,W", SHAPES)
@@ -111,16 +107,10 @@ def upsample_algo(request):
     the channel counts allow (default) or on the direct kernel — and the direct 5x5 kernel with the bilinear loader, all against
     the oracle."""
     from rpg_ramnet_amd import ops
-    old, oldw, oldg, oldd = ops.get_fold_upsample(), ops._FOLD_WINO, ops._FOLD_WINO_WGRAD, ops._FOLD_DGRAD
-    ops.set_fold_upsample(request.param != "direct")
-    ops.set_fold_winograd(request.param in ("folded", "folded_dgrad"))
-    ops.set_fold_winograd_wgrad(request.param in ("folded", "folded_dgrad"))
-    ops.set_fold_dgrad(request.param == "folded_dgrad")           # backward-data through the folded operator's adjoint
-    yield request.param
-    ops.set_fold_dgrad(oldd)
-    ops.set_fold_upsample(old)
-    ops.set_fold_winograd(oldw)
-    ops.set_fold_winograd_wgrad(oldg)
+    wino = request.param in ("folded", "folded_dgrad")
+    with ops.switches(fold_upsample=request.param != "direct", fold_winograd=wino, fold_winograd_wgrad=wino,
+                      fold_dgrad=request.param == "folded_dgrad"):           # backward-data through the folded operator's adjoint
+        yield request.param
 
 
 @pytest.mark.parametrize("B,H,W", [(2, 8, 16), (1, 5, 11), (2, 16, 24), (1, 4, 4), (1, 32, 43)])
@@ -214,17 +204,11 @@ def algo3x3(request):
     kernel of the training batch, forced here for every eligible launch) and F(2x4,3x3) with split bf16 operands (csrc/conv_wino6s.hip),
     all against the oracle at the same tolerances."""
     from rpg_ramnet_amd import ops
-    old = ops.get_winograd()
-    ops.set_winograd(request.param != "direct")
-    if request.param.startswith("winograd2x4"):
-        ops.set_winograd_2x4("force")
-        ops.set_wgrad_winograd_2x4("force")         # ... and the F(2x4,3x3) backward-weights kernel (csrc/conv_wgrad_wino6.hip)
-        ops.set_split_operands(request.param.endswith("_split"))
-    yield request.param
-    ops.set_winograd(old)
-    ops.set_winograd_2x4("auto")
-    ops.set_wgrad_winograd_2x4("auto")
-    ops.set_split_operands(False)
+    values = dict(winograd=request.param != "direct")
+    if request.param.startswith("winograd2x4"):         # ... and the F(2x4,3x3) backward-weights kernel (csrc/conv_wgrad_wino6.hip)
+        values.update(winograd_2x4="force", wgrad_winograd_2x4="force", split_operands=request.param.endswith("_split"))
+    with ops.switches(**values):
+        yield request.param
 
 
 @pytest.mark.parametrize("B,H,W", [(2, 16, 32), (1, 7, 13), (2, 9, 43), (1, 2, 2), (1, 32, 8), (2, 8, 32), (1, 64, 86)])
@@ -249,9 +233,7 @@ def test_winograd2x4_conv3x3_raw(B, H, W, cin, cout):
     ref = F.conv2d(x.double(), w.double(), b.double(), 1, 1)
     outs = {}
     for mode in ("force", "split", "off"):
-        ops.set_winograd_2x4("force" if mode == "split" else mode)
-        ops.set_split_operands(mode == "split")
-        try:
+        with ops.switches(winograd_2x4="force" if mode == "split" else mode, split_operands=mode == "split"):
             kern = []
             y = torch.full((B, H, W, cout), float("nan"), device=dev())
             ops.conv_launch(xg, taps, cp.fwd(), y, cout, bias=cp.bias(), epi=Hh.EPI_RES_RELU, e0=resg)
@@ -265,9 +247,6 @@ def test_winograd2x4_conv3x3_raw(B, H, W, cin, cout):
                 kern.append(Hh.lib().ramnet_last_kernel().decode())
             else:
                 acc = None
-        finally:
-            ops.set_winograd_2x4("auto")
-            ops.set_split_operands(False)
         assert all(k.startswith({"force": "conv_wino_r6_kernel<", "split": "conv_wino_r6s_kernel<", "off": "conv_wino_r_kernel"}[mode]) for k in kern), kern
         outs[mode] = (y, dx, acc)
     yref = torch.relu(ref + res.double())
@@ -307,9 +286,7 @@ def test_winograd_xcd_groups(ch):
     yref = torch.relu(F.conv2d(x.double(), w.double(), b.double(), 1, 1) + res.double())
     dxref = F.conv_transpose2d(torch.where(res > 0, yref, torch.zeros_like(yref)), w.double(), None, 1, 1)
     for mode in ("off", "force", "split"):
-        ops.set_winograd_2x4("force" if mode == "split" else mode)
-        ops.set_split_operands(mode == "split")
-        try:
+        with ops.switches(winograd_2x4="force" if mode == "split" else mode, split_operands=mode == "split"):
             kern = []
             y = torch.full((B, H, W, ch), float("nan"), device=dev())
             ops.conv_launch(xg, taps, cp.fwd(), y, ch, bias=cp.bias(), epi=Hh.EPI_RES_RELU, e0=resg)
@@ -317,9 +294,6 @@ def test_winograd_xcd_groups(ch):
             dx = torch.full((B, H, W, ch), float("nan"), device=dev())
             ops.conv_launch(y, tapsd, cp.bwd(), dx, ch, xm=resg, in_mode=Hh.IN_RELUMASK)
             kern.append(Hh.lib().ramnet_last_kernel().decode())
-        finally:
-            ops.set_winograd_2x4("auto")
-            ops.set_split_operands(False)
         assert all(k.startswith({"force": "conv_wino_r6_kernel<", "split": "conv_wino_r6s_kernel<", "off": "conv_wino_r_kernel"}[mode]) for k in kern), kern
         assert_close(nchw(y).cpu().numpy(), yref.numpy(), TOL, "forward 2x4=%s" % mode)
         assert_close(nchw(dx).cpu().numpy(), dxref.numpy(), TOL, "dgrad 2x4=%s" % mode)
@@ -344,16 +318,13 @@ def test_winograd_conv3x3_raw(B, H, W, cin, cout):
     ref = F.conv2d(x.double(), w.double(), b.double(), 1, 1)
     outs = {}
     for on in (True, False):
-        ops.set_winograd(on)
-        try:
+        with ops.switches(winograd=on):
             y = torch.full((B, H, W, cout), float("nan"), device=dev())
             ops.conv_launch(xg, taps, cp.fwd(), y, cout, bias=cp.bias(), epi=Hh.EPI_RES_RELU, e0=resg)
             dx = torch.full((B, H, W, cin), float("nan"), device=dev())
             ops.conv_launch(y, tapsd, cp.bwd(), dx, cin, xm=resg, in_mode=Hh.IN_RELUMASK)
             acc = xg.clone()
             ops.conv_launch(y, tapsd, cp.bwd(), acc, cin, beta=1.0)
-        finally:
-            ops.set_winograd(True)
         outs[on] = (y, dx, acc)
     yref = torch.relu(ref + res.double())
     dy = torch.where(res > 0, yref, torch.zeros_like(yref))                     # the RELUMASK loader of the backward pass
@@ -390,8 +361,7 @@ def test_winograd_split_reduction(B, H, W, cin, cout):
     ref = F.conv2d(x.double(), w.double(), b.double(), 1, 1)
     outs, split = {}, []
     for on in (True, True, False):
-        ops.set_winograd_split(on)
-        try:
+        with ops.switches(winograd_split=on):
             y = torch.full((B, H, W, cout), float("nan"), device=dev())
             d = ops._conv_desc(xg, taps, cp.fwd(), y, cout, bias=cp.bias(), epi=Hh.EPI_RES_RELU, e0=resg)
             split.append(int(d.splitk_floats))
@@ -402,8 +372,6 @@ def test_winograd_split_reduction(B, H, W, cin, cout):
             Hh.check(Hh.lib().ramnet_conv_launch(C.byref(d), ops._st()), "ramnet_conv_launch")
             acc = xg.clone()
             ops.conv_launch(y, tapsd, cp.bwd(), acc, cin, beta=1.0)
-        finally:
-            ops.set_winograd_split(True)
         outs.setdefault(on, []).append((y, dx, acc))
     assert (max(split[:4]) > 0 or cin < 256) and split[4:] == [0, 0], split          # (reductions of 32 chunks and more split)
     yref = torch.relu(ref + res.double())
@@ -435,13 +403,10 @@ def test_conv_gru_and_encoder_split_reduction_equals_unsplit(B, H, W, C):
     h0 = torch.tanh(torch.randn(B, H, W, C, device=dev()))
     outs = {}
     for on in (True, False):
-        ops.set_winograd_split(on)
-        try:
+        with ops.switches(winograd_split=on):
             with torch.no_grad():
                 e = enc(xin)
                 outs[on] = (e, gru(e, h0))
-        finally:
-            ops.set_winograd_split(True)
     used = {k: bool(cp.__dict__.get("_splitk")) for m in (gru, enc) for k, cp in m._cps.items()}
     assert used["ur"] or used["o"], used
     for a, c in zip(outs[True], outs[False]):
@@ -460,12 +425,9 @@ def test_folded_decoder_split_reduction_equals_unsplit(B, H, W, cin, cout):
     x, sk = torch.randn(B, H, W, cin, device=dev()), torch.randn(B, H, W, cin, device=dev())
     outs = []
     for on in (True, True, False):
-        ops.set_winograd_split(on)
-        try:
+        with ops.switches(winograd_split=on):
             with torch.no_grad():
                 outs.append(m(x, sk))
-        finally:
-            ops.set_winograd_split(True)
     pools = [cp.__dict__.get("_splitk", {}) for cp in m._cps.values()]
     assert any(pools), "the launch did not split"
     assert torch.equal(outs[0], outs[1])
@@ -764,15 +726,8 @@ def direct_split_wgrad():
     """Split operands everywhere they exist: F(2x4,3x3) forward / backward-data with split operands (csrc/conv_wino6s.hip) AND the direct
     split backward-weights kernel (csrc/conv_wgrad_dsplit.hip, ops.set_split_wgrad — off by default: profiles/r06_dsplit_notes.md)."""
     from rpg_ramnet_amd import ops
-    ops.set_winograd_2x4("force")
-    ops.set_wgrad_winograd_2x4("force")
-    ops.set_split_operands(True)
-    ops.set_split_wgrad(True)
-    yield
-    ops.set_split_wgrad(False)
-    ops.set_split_operands(False)
-    ops.set_winograd_2x4("auto")
-    ops.set_wgrad_winograd_2x4("auto")
+    with ops.switches(winograd_2x4="force", wgrad_winograd_2x4="force", split_operands=True, split_wgrad=True):
+        yield
 
 
 @pytest.mark.parametrize("B,H,W,C", [(2, 8, 16, 64), (1, 7, 13, 32), (2, 4, 43, 256), (1, 16, 32, 128)])
@@ -825,14 +780,11 @@ def test_conv_gru_backward_stage_b_fused_equals_unfused(B, H, W, C, algo3x3):
     wgt = torch.randn(B, H, W, C, device=dev())
     res = {}
     for on in (True, False):
-        ops.set_gru_bwd_fused(on)
-        try:
+        with ops.switches(gru_bwd_fused=on):
             m.zero_grad()
             x, h = x0.clone().requires_grad_(True), h0.clone().requires_grad_(True)
             (m(x, h) * wgt).sum().backward()
             res[on] = [x.grad.clone(), h.grad.clone()] + [p.grad.clone() for p in m.parameters()]
-        finally:
-            ops.set_gru_bwd_fused(True)
     for a, c in zip(res[True], res[False]):
         assert_close(a.cpu().numpy(), c.cpu().numpy(), 1e-5, "fused vs unfused stage B")
 
@@ -851,15 +803,12 @@ def test_conv_gru_materialised_h_r_equals_the_loader_product(B, H, W, C, algo3x3
     wgt = torch.randn(B, H, W, C, device=dev())
     res = {}
     for on in (True, False):
-        ops.set_gru_materialize_hr(on)
-        try:
+        with ops.switches(gru_materialize_hr=on):
             m.zero_grad()
             x, h = x0.clone().requires_grad_(True), h0.clone().requires_grad_(True)
             y = m(x, h)
             (y * wgt).sum().backward()
             res[on] = [y.detach().clone(), x.grad.clone(), h.grad.clone()] + [p.grad.clone() for p in m.parameters()]
-        finally:
-            ops.set_gru_materialize_hr(True)
     for k, (a, c) in enumerate(zip(res[True], res[False])):
         if k >= 3 and algo3x3 == "direct":      # (the direct backward-weights kernel joins its tile splits with atomic adds: order-dependent sums)
             assert_close(a.cpu().numpy(), c.cpu().numpy(), 1e-5, "materialised h.r vs loader product, weight gradients")
@@ -920,10 +869,8 @@ def test_conv_gru_deferred_backward_weights_equal_per_update_launches(n, defer, 
     h0 = torch.tanh(torch.randn(B, H, W, C, device=dev()))
     wgt = torch.randn(B, H, W, C, device=dev())
     res = []
-    ops.set_wgrad_winograd_2x4("force")
-    try:
-        for d in (defer, defer, 0):
-            ops.set_wgrad_defer(d)
+    for d in (defer, defer, 0):
+        with ops.switches(wgrad_winograd_2x4="force", wgrad_defer=d):       # (between passes: no launch runs under the values put back)
             m.zero_grad()
             h = h0.clone().requires_grad_(True)
             st = h
@@ -931,9 +878,6 @@ def test_conv_gru_deferred_backward_weights_equal_per_update_launches(n, defer, 
                 st = m(x, st)
             (st * wgt).sum().backward()
             res.append([h.grad.clone()] + [p.grad.clone() for p in m.parameters()])
-    finally:
-        ops.set_wgrad_defer(0)
-        ops.set_wgrad_winograd_2x4("auto")
     for a, c in zip(res[0], res[1]):
         assert torch.equal(a, c), "deferred launches are bit-reproducible"
     assert torch.equal(res[0][0], res[2][0])

@@ -121,12 +121,9 @@ def test_state_half_backward_data_against_float64(cout_mult, beta, wino2x4):
     if beta:
         dxh[..., Cc:] = old.to(_dev())
     before = buf.clone()
-    ops.set_winograd_2x4(wino2x4)
-    try:
+    with ops.switches(winograd_2x4=wino2x4):
         ops.conv_launch(gd, ops.Taps.get("dgrad1", 3, 1), cp.state_half().bwd(), dxh, Cc, out_off=Cc, beta=beta)
         torch.cuda.synchronize()
-    finally:
-        ops.set_winograd_2x4("auto")
     ref = F.conv_transpose2d(g.double(), w.detach().cpu().double(), padding=1)[:, Cc:].permute(0, 2, 3, 1)
     if beta:
         ref = ref + old.double()
@@ -151,8 +148,7 @@ def test_cell_backward_behind_a_frozen_encoder(cell):
     x, h0, c0, gout = (torch.randn(B, Hh, W, Cc, device=_dev()) for _ in range(4))
     res = {}
     for mode in ("off", "force"):
-        ops.set_cell_state_half(mode)
-        try:
+        with ops.switches(cell_state_half=mode):
             h = h0.clone().requires_grad_(True)
             m.zero_grad()
             out = m(x, h) if cell == "convgru" else m(x, (h, c0))[0]
@@ -167,8 +163,6 @@ def test_cell_backward_behind_a_frozen_encoder(cell):
             finally:
                 _hip.set_tracer(None)
             torch.cuda.synchronize()
-        finally:
-            ops.set_cell_state_half("auto")
         widths = [c for n, c in names if n == "ramnet_conv_launch"]
         assert widths and all(c == (Cc if mode == "force" else 2 * Cc) for c in widths), (mode, names)
         res[mode] = [h.grad.clone()] + [p.grad.clone() for p in m.parameters()]

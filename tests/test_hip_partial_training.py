@@ -85,12 +85,9 @@ def reference(tag, tb):
     """the all-trainable step of a model, computed once per (model, schedule)"""
     from rpg_ramnet_amd import ops
     if (tag, tb) not in _REF:
-        ops.set_time_batching(tb)
-        try:
+        with ops.switches(time_batching=tb):
             model, cfg = make(tag)
             _REF[tag, tb] = run(model, cfg)
-        finally:
-            ops.set_time_batching(True)
     return _REF[tag, tb]
 
 
@@ -108,13 +105,10 @@ def same_gradients(got, ref, frozen, what):
 def test_frozen_tensors_get_no_gradient_and_the_rest_the_same_one(tag, fs, tb):
     from rpg_ramnet_amd import ops
     ref_loss, ref_g, ref_names = reference(tag, tb)
-    ops.set_time_batching(tb)
-    try:
+    with ops.switches(time_batching=tb):
         model, cfg = make(tag)
         frozen = apply_set(model, fs)
         loss, g, names = run(model, cfg)
-    finally:
-        ops.set_time_batching(True)
     # 1. no .grad on a frozen tensor, and Adam over ALL parameters (what the reference's BaseTrainer builds) leaves it bit for bit
     for k, p in model.named_parameters():
         assert (p.grad is None) == (k in frozen), k
@@ -145,9 +139,7 @@ def test_frozen_tensors_get_no_gradient_and_the_rest_the_same_one(tag, fs, tb):
 def test_deferred_cell_launches_with_frozen_gates():
     """set_wgrad_defer > 1 (bench.py's schedule) on the side stream: the queue of a frozen cell stays empty, a half-frozen one flushes."""
     from rpg_ramnet_amd import ops
-    ops.set_wgrad_overlap(True)
-    ops.set_wgrad_defer(2)
-    try:
+    with ops.switches(wgrad_overlap=True, wgrad_defer=2):
         model, cfg = make("gru")
         _, ref_g, _ = run(model, cfg)
         for fs in ("B", "C_gate"):
@@ -156,9 +148,6 @@ def test_deferred_cell_launches_with_frozen_gates():
             _, g, _ = run(model, cfg)
             assert all((g[k] is None) == (k in frozen) for k in g)
             same_gradients(g, ref_g, frozen, "deferred, set %s" % fs)
-    finally:
-        ops.set_wgrad_overlap(False)
-        ops.set_wgrad_defer(0)
 
 
 def test_gradual_unfreezing_takes_effect_at_the_next_forward():

@@ -268,12 +268,8 @@ def test_wrappers(name):
     out = torch.full((len(lists), r["bins"], r["H"], r["W"]), SENT, device=dev)
     assert voxel.events_to_voxel_grids_packed(cat, off, mx, r["bins"], r["W"], r["H"], out=out) is out
     same_bits(out.cpu().numpy(), ref, "events_to_voxel_grids_packed %s" % name)
-    old = ops.deterministic()
-    try:
-        ops.set_deterministic(True)
+    with ops.switches(deterministic=True):
         for g, ev in enumerate(lists):              # one list through the sorted form
             got = voxel.events_to_voxel_grid(ev, r["bins"], r["W"], r["H"])
             assert last_kernel() == (expected_kernel(name, "sorted") if len(ev) else "zero_fill")
             same_bits(got.cpu().numpy(), ref[g], "deterministic events_to_voxel_grid %s[%d]" % (name, g))
-    finally:
-        ops.set_deterministic(old)

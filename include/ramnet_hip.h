@@ -673,7 +673,9 @@ int ramnet_augment_batch(const float *const *src, float *const *dst, const int *
  * workspace: ramnet_batch_metrics_workspace(G, N, npix) bytes (0 for arguments the call would reject), 256-byte aligned.  Its first
  * RAMNET_BATCH_METRICS_TICKET_BYTES must be ZERO WHEN IT IS ALLOCATED; every call leaves them zero again and writes whatever else
  * it reads, so calls of any (G, N, npix) that fit the allocation follow each other with no memset in between — one call at a time
- * per workspace (order them on one stream).  G = 0 is a no-op.                                                                      */
+ * per workspace (order them on one stream).  G = 0 is a no-op that returns 0 before any pointer is looked at.  RAMNET_E_BADARG, nothing
+ * launched and nothing written: N or npix = 0, G or N > 65535, N * npix >= 2^31, a NULL, a workspace off 256 bytes, an out off 8.
+ * Nothing in front of or behind a pair's N * npix floats is read, whatever its alignment.                                           */
 #define RAMNET_BATCH_METRICS_TICKET_BYTES 262144
 size_t ramnet_batch_metrics_workspace(int G, int N, size_t npix);
 int ramnet_batch_metrics(const float *const *pred, const float *const *target, int G, int N, size_t npix, void *workspace,
@@ -684,7 +686,8 @@ int ramnet_batch_metrics(const float *const *pred, const float *const *target, i
  * [expf(-reg_factor) * clip_distance, clip_distance] (the prediction side of prepare_depth_data); NaN stays NaN.  The table kernels
  * convert with the same device function.
  * The table: pred / target are DEVICE tables of G device pointers to npix floats of normalised log depth each (NaN target = no ground
- * truth); mask is NULL or a DEVICE table of G pointers to npix bytes (non-zero = inside the event mask; a NULL entry = all inside).
+ * truth); mask is NULL or a DEVICE table of G pointers to npix bytes (ANY non-zero byte = inside the event mask; a NULL entry = all inside).
+ * The maps need 4-byte alignment only and the masks none; nothing in front of or behind a map or a mask is read.
  * cutoffs: HOST array of ncut ascending positive metric depths, 0 <= ncut <= 8, read during the call.
  * out[G][V][16] doubles, V = (1 + ncut) * (mask ? 2 : 1); variants: all pixels, cut-off 0 .. ncut - 1, then the same under the mask.
  * A pixel is inside a variant when (mask byte != 0 or the variant is unmasked) and (target NaN or metric target < cutoff) — the
@@ -701,7 +704,10 @@ int ramnet_batch_metrics(const float *const *pred, const float *const *target, i
  * call; nothing is read back.  workspace: the size the workspace function returns (0 for sizes the call would reject), 256-byte
  * aligned; its first RAMNET_EVAL_TABLE_TICKET_BYTES must be ZERO WHEN IT IS ALLOCATED, every call leaves them zero again and writes
  * whatever else it reads: calls of any shape that fit the allocation follow each other with no memset in between (one call at a time
- * per workspace: order them on one stream).  G * V may not exceed the tickets (RAMNET_EVAL_TABLE_TICKET_BYTES / 4).                 */
+ * per workspace: order them on one stream).  G * V may not exceed the tickets (RAMNET_EVAL_TABLE_TICKET_BYTES / 4 = 65536 cells); the
+ * workspace functions return 0 and the calls RAMNET_E_BADARG beyond that, for G outside 1..65535, npix outside 1..2^32 - 1, ncut outside
+ * 0..8, cut-offs that are not positive and strictly ascending, clip_distance <= 0, unknown flag bits, a workspace off 256 bytes or an
+ * out off 8: nothing is launched and neither out nor the workspace is written.                                                       */
 #define RAMNET_EVAL_TABLE_TICKET_BYTES 262144
 int ramnet_metric_depth(const float *y, size_t n, float clip_distance, float reg_factor, int clamp, float *out, void *stream);
 size_t ramnet_eval_table_workspace(int G, size_t npix, int ncut, int has_mask);
@@ -711,6 +717,9 @@ int ramnet_eval_table(const float *const *pred, const float *const *target, cons
  *   RAMNET_EVAL_RESCALE        the rows are formed after rescale_by_the_median (evaluation.py:99-154), see below;
  *   RAMNET_EVAL_TARGET_METRIC  the target tables hold float32 METRIC depth already (NaN = no ground truth) and are not converted again:
  *                              what the resize entry below writes.  The predictions are normalised log depth as before.
+ *                              Metric targets are >= +0 and THE CALLER OWES THAT: the selection ranks a target by its bit pattern
+ *                              without the sign, so a negative target would be ranked by its magnitude (and its log is NaN).
+ *                              +0 is a valid target (the smallest key); a target exactly at a cut-off is OUTSIDE it (strict <).
  * flags = 0 IS the plain table: the same kernels, the same rows bit for bit, the same workspace size.  A workspace allocated for one flag
  * value serves any other call that fits it, with no memset in between (the ticket rule above holds for all of them).
  * The row of a RESCALED call.  Per (pair, variant), t / p = the float32 metric target / clipped metric prediction of the pixels inside,
@@ -729,7 +738,8 @@ int ramnet_eval_table(const float *const *pred, const float *const *target, cons
  * H' = floor(H * scale_factor), W' likewise, 0 < scale_factor <= 1: torch's F.interpolate(metric target, scale_factor, mode='bilinear') at its
  * defaults (align_corners=False; source coordinate max((dst + 0.5) / scale_factor - 0.5, 0) from the given factor, not from the size
  * ratio) on the unclamped metric depths of the conversion above, evaluated in double and rounded once.  A NaN tap makes the output NaN,
- * at weight zero too.  One launch for the G maps.                                                                                     */
+ * at weight zero too.  One launch for the G maps; exactly G x H' x W' floats are written.  RAMNET_E_BADARG, nothing written: scale_factor
+ * outside (0, 1] (a NaN too), H' or W' = 0, G outside 1..65535, clip_distance <= 0.                                                    */
 #define RAMNET_EVAL_RESCALE 1
 #define RAMNET_EVAL_TARGET_METRIC 2
 size_t ramnet_eval_table_ex_workspace(int G, size_t npix, int ncut, int has_mask, int flags);

@@ -1,7 +1,8 @@
-"""The guarded call of the direct kernel tests (tests/test_hip_pointwise.py, tests/test_hip_reductions.py, tests/test_hip_conv_launch.py, tests/test_hip_voxel_launch.py, tests/test_hip_grad_loss_launch.py, tests/test_hip_augment_launch.py): device buffers between
+"""The guarded call of the direct kernel tests (tests/test_hip_pointwise.py, tests/test_hip_reductions.py, tests/test_hip_conv_launch.py, tests/test_hip_voxel_launch.py, tests/test_hip_grad_loss_launch.py, tests/test_hip_augment_launch.py, tests/test_hip_metric_launch.py): device buffers between
 sentinel / NaN guards, the one way to an entry point of the C ABI, and the comparison rules of profiles/pointwise_tests_notes.md §1.
 
-`dtype`: float32 (default), float64 (`stats`, `part`, `mean`, `rstd`) or int64 (`num_batches_tracked`), guards and gaps in that dtype.
+`dtype`: float32 (default), float64 (`stats`, `part`, `mean`, `rstd`), int64 (`num_batches_tracked`) or uint8 (masks: `In(..., fill=SENT_BYTE,
+dtype=torch.uint8)`; workspaces: `workspace`), guards and gaps in that dtype.
 `skew`: elements by which the usable pointer is moved off the 16-byte alignment that every torch allocation has."""
 import ctypes as C
 
@@ -14,6 +15,7 @@ U = 2.0 ** -24
 GUARD = 256                      # elements in front of and behind every buffer
 SENT = -1.2345678e29             # what outputs hold before a launch (nothing a kernel computes here)
 SENT_INT = -1234567890123        # the same for integer outputs
+SENT_BYTE = 0xA5                 # the same for byte buffers (masks, workspaces): non-zero, so a mask guard reads as "inside"
 BADARG = 10001
 TRIP2 = 524288 + 777             # items: 2048 workgroups x 256 threads = the first trip of every grid-stride loop, and a ragged second one
 # maximum absolute error against float64 of sigmoidf_ over [-16, 16] and tanhf_ over [-8, 8], measured on the MI355X through
@@ -28,11 +30,11 @@ def _dev():
 
 
 def _bits(t):
-    return t.contiguous().view(torch.int32 if t.element_size() == 4 else torch.int64)
+    return t.contiguous() if t.element_size() == 1 else t.contiguous().view(torch.int32 if t.element_size() == 4 else torch.int64)
 
 
 def _sentinel(dtype):
-    return SENT if dtype.is_floating_point else SENT_INT
+    return SENT if dtype.is_floating_point else SENT_BYTE if dtype == torch.uint8 else SENT_INT
 
 
 class In:
@@ -106,6 +108,21 @@ def pointer_table(bufs, through_kernel=False, tail=0):
     pre = torch.full((len(ptrs) + tail,), SENT_INT, dtype=torch.int64)
     pre[:len(ptrs)] = torch.tensor(ptrs, dtype=torch.int64)
     return Out(1, len(ptrs) + tail, dtype=torch.int64, prefill=pre).freeze()
+
+
+def workspace(nbytes, ticket_bytes, pattern=0xC3):
+    """A workspace of EXACTLY nbytes between byte guards, 256-byte aligned: the ticket bytes zero (all a caller owes), everything behind them
+    `pattern` (non-zero: a call has to write whatever else it reads).  `call` checks the guards; `tickets_zero` the tickets."""
+    pre = torch.full((nbytes,), pattern, dtype=torch.uint8)
+    pre[:ticket_bytes] = 0
+    ws = Out(1, nbytes, dtype=torch.uint8, prefill=pre)
+    assert ws.ptr % 256 == 0, "the allocator's alignment changed: the workspace is off 256 bytes"
+    ws.ticket_bytes = ticket_bytes
+    return ws
+
+
+def tickets_zero(ws):
+    return not bool(ws.value()[0, :ws.ticket_bytes].any())
 
 
 def call(name, *args, rc=0, stream=None, defer=False):

@@ -1,9 +1,14 @@
 // Host side of the 3x3 launchers (conv_wino.hip, conv_wino6.hip, conv_wino6s.hip, conv_wgrad_wino.hip, conv_wgrad_wino6.hip,
 // conv_wgrad_dsplit.hip): what a launcher reads off its descriptor before it picks a template instantiation — the logical input, the tap
 // window, the conditions of the channel-quad epilogues, the XCD groups, the 32-bit offsets — and the ONE plan of an F(2x4,3x3) launch,
-// which launch_wino6 / launch_wino6s execute and wino6_eligible asks without launching.  No device code; nothing here allocates or formats
-// a string unless a check fails.
+// which launch_wino6 / launch_wino6s execute and wino6_eligible asks without launching.  For the backward-weights launchers (those three
+// and conv_wgrad.hip): the one structural check of the 3x3 families, and the split rule — per family the own figure and the cap its
+// ramnet_wgrad_*_slabs query answers, the clamp chain (wgrad_splits) and the XCD step (wgrad_xcd_splits) that launcher and query both
+// call —, the (XMK, GM) dispatch and the unpack entry.  No device code besides the blocked-workspace address of the two unpack kernels;
+// nothing here allocates or formats a string unless a check fails.
 #pragma once
+#include <stdlib.h>
+#include <type_traits>
 #include "conv_wino_common.hpp"
 
 namespace ramnet {
@@ -164,6 +169,94 @@ inline int wino6_plan(const ramnet_conv_desc &d, int chunk, Wino6Plan &out, bool
     return 0;
 }
 
+// ---- backward-weights (conv_wgrad.hip, conv_wgrad_wino.hip, conv_wgrad_wino6.hip, conv_wgrad_dsplit.hip) --------------------------
+
+// What the three 3x3 families require of a descriptor: nine taps in the forward order kh*3 + kw (the workspace rows follow it; (dy0, dx0)
+// = the first one), stride 1, a same-size map, an input mode their loaders know, the 32 (dsplit: 4) input channels a workgroup (a
+// staging quad) loads together inside one tensor of a concatenation / one parity group of a space-to-depth view (`group`), and
+// several segments only where the kernel walks them (F(2x4)).
+inline int wgrad3x3_check(const ramnet_wgrad_desc &d, int group, bool segments, int &dy0, int &dx0, bool quiet = false) {
+    RAMNET_PLAN_CHECK(d.ntaps == 9 && d.stride == 1 && d.Ho == d.Hin && d.Wo == d.Win && (segments || d.nseg == 0));
+    RAMNET_PLAN_CHECK(d.in_mode == RAMNET_IN_PLAIN || d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL || d.in_mode == RAMNET_IN_RELUMASK ||
+                      d.in_mode == RAMNET_IN_S2D);
+    if (d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL) RAMNET_PLAN_CHECK(d.C0 % group == 0);
+    if (d.in_mode == RAMNET_IN_S2D) RAMNET_PLAN_CHECK(d.C0 >= group && log2_exact(d.C0) > 0);
+    RAMNET_PLAN_CHECK(taps_3x3(d.dy, d.dx, true, dy0, dx0));
+    return 0;
+}
+
+// The Winograd backward-weights kernels address their tensors with 32-bit byte offsets below WOOB: inside ONE image (F(2x2): the batch
+// walk moves the base) or inside the whole tensor of B images (F(2x4): `whole`).  dsplit addresses with 64-bit pixel indices: no check.
+inline int wgrad_offsets32(const ramnet_wgrad_desc &d, bool whole, bool quiet = false) {
+    const unsigned long long n = whole ? d.B : 1, px = n * d.Hin * d.Win * (d.in_mode == RAMNET_IN_S2D ? 4 : 1), gpx = n * d.Ho * d.Wo;
+    const unsigned long long ldx = d.ld0 > d.ld1 ? d.ld0 : d.ld1;
+    RAMNET_PLAN_CHECK(px * ldx * 4ull < WOOB && px * d.ldm * 4ull < WOOB && gpx * d.ldg * 4ull < WOOB && gpx * d.ldgm * 4ull < WOOB);
+    return 0;
+}
+
+// How a launch splits its pixel tiles.  Every family has an OWN figure — the workgroups a launch aims at (an option or a constant),
+// divided by its channel blocks — and a CAP, a function of the channels alone, which is what ramnet_wgrad_*_slabs answers and a caller
+// sizes the [S][...] workspace of the slab form by.  Own figure and cap are NOT ordered: F(2x2) runs 32 x 32-channel workgroups by
+// default (nf = 1: twice the target at half the block) while its cap counts 64-channel blocks, so with an odd number of 32-channel
+// output blocks own > cap (Cin 64, Cout 96: 128 against 96; Cin 32, Cout 32: 768 against 384); "wgrad_wino_blocks" / RAMNET_DS_TARGET
+// move the own figure and leave the cap.  What bounds a launch by its workspace is the dw_slabs term of wgrad_splits, nothing else.
+constexpr int WGRAD_WINO_TARGET = 384;      // F(2x2): workgroups per launch the tile splits aim at
+constexpr int WG6_TARGET = 384;             // F(2x4): the same
+constexpr int DS_TARGET = 512;              // dsplit: the same
+
+inline int wgrad_chan_blocks(int Cin, int ci, int Cout, int co) { return cdiv(Cin, ci) * cdiv(Cout, co); }
+inline int at_least_1(int v) { return v < 1 ? 1 : v; }
+
+inline int wgrad_direct_own(int blocks) { return g_opt_wgrad_blocks / blocks; }                 // (ramnet_set_option("wgrad_blocks"): default 512)
+inline int wgrad_direct_cap(int blocks) { const int o = wgrad_direct_own(blocks); return o < RAMNET_WGRAD_SLAB_CAP ? o : RAMNET_WGRAD_SLAB_CAP; }     // slab form only
+inline int wgrad_wino_own(int Cin, int Cout, int nf) { return g_opt_wgrad_wino_blocks * (2 / nf) / wgrad_chan_blocks(Cin, 32, Cout, 32 * nf); }
+inline int wgrad_wino_cap(int Cin, int Cout) { return at_least_1(WGRAD_WINO_TARGET / wgrad_chan_blocks(Cin, 32, Cout, 64)); }
+inline int wgrad_wino6_own(int Cin, int Cout) { return g_opt_wgrad_wino_blocks / wgrad_chan_blocks(Cin, 32, Cout, 32); }
+inline int wgrad_wino6_cap(int Cin, int Cout) { return at_least_1(WG6_TARGET / wgrad_chan_blocks(Cin, 32, Cout, 32)); }
+inline int wgrad_dsplit_own(int Cin, int Cout) {
+    static const int target = getenv("RAMNET_DS_TARGET") ? atoi(getenv("RAMNET_DS_TARGET")) : DS_TARGET;      // (tuning runs)
+    return target / wgrad_chan_blocks(Cin, 64, Cout, 64);
+}
+inline int wgrad_dsplit_cap(int Cin, int Cout) { return at_least_1(wgrad_dsplit_own(Cin, Cout)); }
+
+// The clamp chain: the own figure (slab form of the direct family: its cap), at most the units the launch can divide (pixel tiles or
+// batches of them), at most the slabs the caller gave (dw_slabs > 0), at least 1.
+inline int wgrad_splits(int own, int units, int dw_slabs) {
+    int s = own < units ? own : units;
+    if (dw_slabs > 0 && s > dw_slabs) s = dw_slabs;
+    return at_least_1(s);
+}
+
+// 1-D grids that deal their splits to the 8 XCDs (the workgroups that share a split's strips then share an L2) need a multiple of 8:
+// from 8 splits up the count moves to one and *xcd_map is set.  F(2x4) rounds to the NEAREST multiple that units and dw_slabs still
+// allow, else down: its target of 384 workgroups leaves room below the 512 that the 256 CUs hold at two per CU, and the at most 4
+// splits added stay within it ((own + 4) x channel blocks <= 512 from own = 12 up, the first figure that rounds up), so nearest keeps
+// the launch closest to the measured target.  dsplit rounds DOWN: its target IS those 512, a step up would leave workgroups waiting
+// for a second wave.
+inline int wgrad_xcd_splits(int splits, int units, int dw_slabs, bool nearest, int *xcd_map) {
+    *xcd_map = splits >= 8;
+    if (splits < 8) return splits;
+    const int up = (splits + 4) / 8 * 8;
+    return nearest && up <= units && (dw_slabs <= 0 || up <= dw_slabs) ? up : splits / 8 * 8;
+}
+
+// Second operand of the input loader (XMK: 0 none, 1 ReLU mask, 2 the product of a CAT_MUL input) and mask on dy (GM) -> the template
+// instantiation: f(std::integral_constant<int, XMK>, std::bool_constant<GM>), whose int is returned
+template <class F>
+inline int wgrad_dispatch(const ramnet_wgrad_desc &d, F &&f) {
+    const auto on_gm = [&](auto xmk) { return d.gmask != nullptr ? f(xmk, std::true_type{}) : f(xmk, std::false_type{}); };
+    if (d.in_mode == RAMNET_IN_RELUMASK) return on_gm(std::integral_constant<int, 1>{});
+    if (d.in_mode == RAMNET_IN_CAT_MUL) return on_gm(std::integral_constant<int, 2>{});
+    return on_gm(std::integral_constant<int, 0>{});
+}
+
+// Address of (input channel c, output channel n) inside one position of a blocked workspace [Cin / 32][Cout / 32][64][16] (the join of
+// conv_wgrad_wino_r6_kernel / conv_wgrad_dsplit_kernel: 32 x 32 accumulator tiles as the MFMA leaves them); nCoB = output blocks
+__device__ __forceinline__ size_t wgrad_blocked_at(int c, int n, int nCoB) {
+    const int c32 = c & 31;
+    return ((size_t)(c >> 5) * nCoB + (n >> 5)) * 1024 + ((n & 31) + 32 * ((c32 >> 2) & 1)) * 16 + (c32 & 3) + 4 * (c32 >> 3);
+}
+
 #undef RAMNET_PLAN_CHECK
 
 // Grid-stride launch of a pack / unpack kernel over `total` elements in blocks of BLOCK threads (args: ALL of the kernel's parameters)
@@ -174,6 +267,13 @@ inline int launch_1d(K kernel, size_t total, void *stream, A... args) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(BLOCK), 0, (hipStream_t)stream, args...);
     RAMNET_LAUNCH_CHECK();
     return 0;
+}
+
+// ramnet_unpack_wgrad_wino / _wino2x4 / _dsplit: the window [n_off, n_off + Cout) x [0, Cin) of a [.][CinWs][CoutWs] workspace -> grad (+=)
+template <class K>
+inline int launch_wgrad_unpack(K kernel, const float *ws, float *grad, int Cout, int Cin, int CinWs, int CoutWs, int n_off, void *stream) {
+    RAMNET_CHECK_ARG(ws && grad && Cout > 0 && Cin > 0 && CinWs >= Cin && n_off >= 0 && CoutWs >= n_off + Cout);
+    return launch_1d(kernel, (size_t)Cout * Cin, stream, ws, grad, Cout, Cin, CinWs, CoutWs, n_off, (size_t)Cout * Cin);
 }
 
 }  // namespace ramnet

@@ -12,9 +12,9 @@
 // fp32 workspace through coalesced atomic adds.  The bias gradient (column sums of g) rides along.
 #include <stdlib.h>
 #include "common.hpp"
+#include "conv_plan.hpp"
 
 namespace ramnet {
-
 
 struct WgradDerived {
     InSrc src;
@@ -37,31 +37,28 @@ struct WgradDerived {
 #undef WGRAD_SLAB
 #undef WGRAD_KERNEL
 
+// Host-only shape of a RAMNET_ALGO_DIRECT launch: which kernel takes it (wide: conv_wgrad_kernel<9,2,2>, 64 x 64 channels per workgroup;
+// narrow: 32 x 32; else 32 x 64), its channel-block grid, and the splits its slab form uses at most (conv_plan.hpp)
+struct WgradShape {
+    bool wide, narrow;
+    int wck, wbn, gy, gz, cap;
+};
+
 template <int MAXT, int NSUB, int CSUB = 1, bool SLAB = false>
-static int launch_wgrad(const ramnet_wgrad_desc &d, const WgradDerived &q, hipStream_t st) {
-    if (!SLAB && d.dw_slabs > 0) return launch_wgrad<MAXT, NSUB, CSUB, true>(d, q, st);
+static int launch_wgrad(const ramnet_wgrad_desc &d, const WgradDerived &q, const WgradShape &s, hipStream_t st) {
+    if (!SLAB && d.dw_slabs > 0) return launch_wgrad<MAXT, NSUB, CSUB, true>(d, q, s, st);
     auto kern = SLAB ? conv_wgrad_kernel_slab<MAXT, NSUB, CSUB> : conv_wgrad_kernel<MAXT, NSUB, CSUB>;
-    constexpr int WBN = 32 * NSUB, WCK = 32 * CSUB;
-    size_t lds = ((size_t)q.PH * q.PW * WCK + q.TH * TWID * WBN) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        RAMNET_FULL_LDS((kern));
-        attr_set = true;
-    }
+    size_t lds = ((size_t)q.PH * q.PW * s.wck + q.TH * TWID * s.wbn) * sizeof(float);
+    RAMNET_FULL_LDS((kern));
     if (lds > 160 * 1024) {
         set_error("wgrad patch does not fit LDS (%zu bytes)", lds);
         return RAMNET_E_UNSUPPORTED;
     }
-    const int gy = cdiv(q.src.Cin, WCK), gz = cdiv(d.Cout, WBN);
     // one resident wave of workgroups (256 CUs x blocks/CU the register budget admits): fewer pixel splits = fewer
     // atomic partial-sum merges, and every CU still gets an equal share
-    int splits = g_opt_wgrad_blocks / (gy * gz);                // (ramnet_set_option("wgrad_blocks"): default 512)
-    if (SLAB && splits > RAMNET_WGRAD_SLAB_CAP) splits = RAMNET_WGRAD_SLAB_CAP;
-    if (SLAB && splits > d.dw_slabs) splits = d.dw_slabs;
-    if (splits > q.ntiles) splits = q.ntiles;
-    if (splits < 1) splits = 1;
+    const int splits = SLAB ? wgrad_splits(s.cap, q.ntiles, d.dw_slabs) : wgrad_splits(wgrad_direct_own(s.gy * s.gz), q.ntiles, 0);
     note_kernel(SLAB ? "conv_wgrad_kernel_slab<%d,%d,%d>" : "conv_wgrad_kernel<%d,%d,%d>", MAXT, NSUB, CSUB);
-    hipLaunchKernelGGL(kern, dim3(splits, gy, gz), dim3(256), lds, st, d, q);
+    hipLaunchKernelGGL(kern, dim3(splits, s.gy, s.gz), dim3(256), lds, st, d, q);
     RAMNET_LAUNCH_CHECK();
     return 0;
 }
@@ -70,7 +67,7 @@ static int launch_wgrad(const ramnet_wgrad_desc &d, const WgradDerived &q, hipSt
 
 using namespace ramnet;
 
-static void wgrad_derive(const ramnet_wgrad_desc &d, WgradDerived &q, bool &wide_out, bool &narrow_out);
+static WgradShape wgrad_derive(const ramnet_wgrad_desc &d, WgradDerived &q);
 
 extern "C" int ramnet_wgrad_launch(const ramnet_wgrad_desc *dp, void *stream) {
     RAMNET_CHECK_ARG(dp != nullptr);
@@ -107,32 +104,26 @@ extern "C" int ramnet_wgrad_launch(const ramnet_wgrad_desc *dp, void *stream) {
     RAMNET_CHECK_ARG(d.algo == RAMNET_ALGO_DIRECT && d.in_mode != RAMNET_IN_S2D);
 
     WgradDerived q;
-    bool wide, narrow;
-    wgrad_derive(d, q, wide, narrow);
+    const WgradShape s = wgrad_derive(d, q);
     hipStream_t st = (hipStream_t)stream;
-    if (narrow) {                                   // WBN = 32: tap tiles spread over 4 waves
+    if (s.narrow) {                                 // WBN = 32: tap tiles spread over 4 waves
         const int per_wave = cdiv(q.ntt, 4);
-        if (per_wave <= 1) return launch_wgrad<1, 1>(d, q, st);
-        if (per_wave <= 3) return launch_wgrad<3, 1>(d, q, st);
-        if (per_wave <= 4) return launch_wgrad<4, 1>(d, q, st);     // 16 taps: one parity of the folded upsample-conv
-        return launch_wgrad<7, 1>(d, q, st);
+        if (per_wave <= 1) return launch_wgrad<1, 1>(d, q, s, st);
+        if (per_wave <= 3) return launch_wgrad<3, 1>(d, q, s, st);
+        if (per_wave <= 4) return launch_wgrad<4, 1>(d, q, s, st);     // 16 taps: one parity of the folded upsample-conv
+        return launch_wgrad<7, 1>(d, q, s, st);
     }
-    if (wide) return launch_wgrad<9, 2, 2>(d, q, st);
+    if (s.wide) return launch_wgrad<9, 2, 2>(d, q, s, st);
     const int per_wave = cdiv(q.ntt, 2);            // WBN = 64: tap tiles spread over 2 wave pairs
-    if (per_wave <= 1) return launch_wgrad<1, 2>(d, q, st);
-    if (per_wave <= 5) return launch_wgrad<5, 2>(d, q, st);
-    return launch_wgrad<13, 2>(d, q, st);
+    if (per_wave <= 1) return launch_wgrad<1, 2>(d, q, s, st);
+    if (per_wave <= 5) return launch_wgrad<5, 2>(d, q, s, st);
+    return launch_wgrad<13, 2>(d, q, s, st);
 }
 
-// Geometry of a RAMNET_ALGO_DIRECT launch (host arithmetic only): pixel tiles, patch, tap tiles, and which kernel shape takes it
-// (wide: conv_wgrad_kernel<9,2,2>; narrow: 32 output channels per workgroup; else 64).
-static void wgrad_derive(const ramnet_wgrad_desc &d, WgradDerived &q, bool &wide_out, bool &narrow_out) {
-    const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
+// Geometry of a RAMNET_ALGO_DIRECT launch (host arithmetic only): pixel tiles, patch, tap tiles, and the shape of the kernel that takes it
+static WgradShape wgrad_derive(const ramnet_wgrad_desc &d, WgradDerived &q) {
     const bool gdense = d.gsy == 0 && d.gsx == 0 && d.goy == 0 && d.gox == 0 && d.HoG == 0 && d.WoG == 0;
-    q.src.x0 = d.x0, q.src.x1 = d.x1, q.src.xm = d.xm;
-    q.src.ld0 = d.ld0, q.src.ld1 = d.ld1, q.src.ldm = d.ldm;
-    q.src.C0 = d.C0, q.src.Cin = d.C0 + (cat ? d.C1 : 0);
-    q.src.mode = d.in_mode, q.src.Hin = d.Hin, q.src.Win = d.Win;
+    fill_in_src(d, q.src);
     int dymin = 127, dymax = -127, dxmin = 127, dxmax = -127;
     for (int t = 0; t < d.ntaps; ++t) {
         dymin = d.dy[t] < dymin ? d.dy[t] : dymin, dymax = d.dy[t] > dymax ? d.dy[t] : dymax;
@@ -160,7 +151,10 @@ static void wgrad_derive(const ramnet_wgrad_desc &d, WgradDerived &q, bool &wide
     q.ntt = cdiv(d.ntaps, q.tpm);
     // measured (profiles/r01_*layers*): 5x5 layers run 1.5x faster with WBN = 32 (7 tiles/wave, 2 workgroups/CU) than with
     // WBN = 64 (13 tiles/wave, 1 workgroup/CU); 3x3 layers prefer WBN = 64 (5 tiles/wave)
-    wide_out = wide, narrow_out = d.Cout <= 32 || d.ntaps > 9;
+    WgradShape s{wide, d.Cout <= 32 || d.ntaps > 9};
+    s.wck = wck, s.wbn = s.narrow ? 32 : 64;
+    s.gy = cdiv(q.src.Cin, s.wck), s.gz = cdiv(d.Cout, s.wbn), s.cap = wgrad_direct_cap(s.gy * s.gz);
+    return s;
 }
 
 // Largest number of splits a launch of this descriptor's algorithm and shape can use in its slab form (ramnet_hip.h)
@@ -168,8 +162,9 @@ extern "C" int ramnet_wgrad_slabs(const ramnet_wgrad_desc *dp) {
     if (dp == nullptr) return 0;
     const ramnet_wgrad_desc &d = *dp;
     if (d.B < 1 || d.Ho < 1 || d.Wo < 1 || d.Cout < 1 || d.C0 < 1) return 0;
-    const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
-    const int Cin = d.in_mode == RAMNET_IN_S2D ? 4 * d.C0 : d.C0 + (cat ? d.C1 : 0);
+    InSrc in;
+    fill_in_src(d, in);
+    const int Cin = in.Cin;
     switch (d.algo) {
     case RAMNET_ALGO_WINOGRAD24:
     case RAMNET_ALGO_WINOGRAD24_2X3: return wgrad_wino24_splits(d);
@@ -182,11 +177,6 @@ extern "C" int ramnet_wgrad_slabs(const ramnet_wgrad_desc *dp) {
     }
     if (d.ntaps < 1 || d.ntaps > 25 || (d.stride != 1 && d.stride != 2) || d.in_mode == RAMNET_IN_S2D) return 0;
     WgradDerived q;
-    bool wide, narrow;
-    wgrad_derive(d, q, wide, narrow);
-    const int gy = cdiv(q.src.Cin, wide ? 64 : WCK), gz = cdiv(d.Cout, narrow ? 32 : 64);
-    int splits = g_opt_wgrad_blocks / (gy * gz);                // (launch_wgrad)
-    if (splits > RAMNET_WGRAD_SLAB_CAP) splits = RAMNET_WGRAD_SLAB_CAP;
-    if (splits > q.ntiles) splits = q.ntiles;
-    return splits < 1 ? 1 : splits;
+    const WgradShape s = wgrad_derive(d, q);
+    return wgrad_splits(s.cap, q.ntiles, 0);
 }

@@ -42,7 +42,6 @@ __device__ __forceinline__ void ds_for(F &&f) { ds_for_impl(f, std::make_integer
 
 __device__ float g_dsplit_zero[4];                    // what an out-of-image / out-of-range slot loads (device globals start as zeros)
 
-constexpr int DS_TARGET = 512;                        // workgroups per launch the tile splits aim at
 // LDS, two buffers of [input strip: channel 64][row 6][term 3][6 dwords: 10 bf16 pixels + pad] + [gradient strip: term 3][row 4][channel 64][16 bytes].
 // A lane reads a window row as two aligned ds_read_b64 + one ds_read_b32 (2 LDS cycles each, banks mod 64; ds_read2_b32 at an odd dword costs
 // 4 cycles on 32 banks): dwords 0-3 are the dx = 0 operand, 1-4 the dx = 2 one (three register moves: MFMA operands are even-aligned register
@@ -446,53 +445,27 @@ __global__ void __launch_bounds__(256, 2) __attribute__((amdgpu_waves_per_eu(2, 
 }
 
 bool wgrad_dsplit_eligible(const ramnet_wgrad_desc &d) {
-    return d.ntaps == 9 && d.stride == 1 && d.Ho == d.Hin && d.Wo == d.Win && d.nseg == 0 &&
-           (d.in_mode == RAMNET_IN_PLAIN || d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL || d.in_mode == RAMNET_IN_RELUMASK ||
-            (d.in_mode == RAMNET_IN_S2D && d.C0 >= 4 && (d.C0 & (d.C0 - 1)) == 0));
-}
-
-static int dsplit_splits(int Cin, int Cout) {
-    static const int target = getenv("RAMNET_DS_TARGET") ? atoi(getenv("RAMNET_DS_TARGET")) : DS_TARGET;      // (tuning runs)
-    const int s = target / (cdiv(Cin, 64) * cdiv(Cout, 64));
-    return s < 1 ? 1 : s;
+    int dy0, dx0;
+    return wgrad3x3_check(d, 4, false, dy0, dx0, true) == 0;
 }
 
 int launch_wgrad_dsplit(const ramnet_wgrad_desc &d, hipStream_t st) {
-    RAMNET_CHECK_ARG(wgrad_dsplit_eligible(d));
     WgradDsParams q{};
-    RAMNET_CHECK_ARG(taps_3x3(d.dy, d.dx, true, q.dy0, q.dx0));      // the forward tap order kh*3 + kw
+    if (int rc = wgrad3x3_check(d, 4, false, q.dy0, q.dx0)) return rc;
     fill_in_src(d, q.src);
     q.bx_n = cdiv(d.Wo, 8), q.ty_n = cdiv(d.Ho, 4), q.nbatch = q.bx_n * q.ty_n * d.B;
-    const int gy = cdiv(q.src.Cin, 64), gz = cdiv(d.Cout, 64);
-    int splits = dsplit_splits(q.src.Cin, d.Cout);
-    if (splits > q.nbatch) splits = q.nbatch;
-    if (d.dw_slabs > 0 && splits > d.dw_slabs) splits = d.dw_slabs;
-    if (splits < 1) splits = 1;
-    q.xcd_map = 0;
-    if (splits >= 8) splits = splits / 8 * 8, q.xcd_map = 1;
-    q.splits = splits, q.gy = gy, q.gz = gz;
-    const dim3 grid(splits * gy * gz);
-    const int xmk = d.in_mode == RAMNET_IN_RELUMASK ? 1 : d.in_mode == RAMNET_IN_CAT_MUL ? 2 : 0;
-    const bool gm = d.gmask != nullptr;
-    note_kernel("conv_wgrad_dsplit_kernel<%d,%d>", xmk, (int)gm);
-#define RAMNET_GO(XMv, GMv)                                                                                          \
-    do {                                                                                                             \
-        static bool attr_set = false;                                                                                \
-        if (!attr_set) {                                                                                             \
-            RAMNET_FULL_LDS((conv_wgrad_dsplit_kernel<XMv, GMv>));                                                    \
-            attr_set = true;                                                                                         \
-        }                                                                                                            \
-        hipLaunchKernelGGL((conv_wgrad_dsplit_kernel<XMv, GMv>), grid, dim3(256), (size_t)(ABLD(512) ? DS_BUF : DS_LDS), st, d, q);          \
-    } while (0)
-    if (xmk == 1 && gm) RAMNET_GO(1, true);
-    else if (xmk == 1) RAMNET_GO(1, false);
-    else if (xmk == 2 && gm) RAMNET_GO(2, true);
-    else if (xmk == 2) RAMNET_GO(2, false);
-    else if (gm) RAMNET_GO(0, true);
-    else RAMNET_GO(0, false);
-#undef RAMNET_GO
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    q.gy = cdiv(q.src.Cin, 64), q.gz = cdiv(d.Cout, 64);
+    q.splits = wgrad_xcd_splits(wgrad_splits(wgrad_dsplit_own(q.src.Cin, d.Cout), q.nbatch, d.dw_slabs), q.nbatch, d.dw_slabs, false, &q.xcd_map);
+    const dim3 grid(q.splits * q.gy * q.gz);
+    return wgrad_dispatch(d, [&](auto xmk, auto gm) {
+        constexpr int XM = decltype(xmk)::value;
+        constexpr bool GM = decltype(gm)::value;
+        note_kernel("conv_wgrad_dsplit_kernel<%d,%d>", XM, (int)GM);
+        RAMNET_FULL_LDS((conv_wgrad_dsplit_kernel<XM, GM>));
+        hipLaunchKernelGGL((conv_wgrad_dsplit_kernel<XM, GM>), grid, dim3(256), (size_t)(ABLD(512) ? DS_BUF : DS_LDS), st, d, q);
+        RAMNET_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 // blocked ws [9][CinWs / 32][CoutWs / 32][64][16] (layout: the kernel's join) -> grad OIHW [Cout][Cin][3][3] (+=)
@@ -502,8 +475,7 @@ __global__ void unpack_wgrad_dsplit_kernel(const float *__restrict__ ws, float *
     const size_t pos_stride = (size_t)nCiB * nCoB * 1024;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % Cin), n = (int)(i / Cin);
-        const int nn = n_off + n, c32 = c & 31;
-        const size_t at = ((size_t)(c >> 5) * nCoB + (nn >> 5)) * 1024 + ((nn & 31) + 32 * ((c32 >> 2) & 1)) * 16 + (c32 & 3) + 4 * (c32 >> 3);
+        const size_t at = wgrad_blocked_at(c, n_off + n, nCoB);
         for (int t = 0; t < 9; ++t) g[((size_t)n * Cin + c) * 9 + t] += ws[(size_t)t * pos_stride + at];
     }
 }
@@ -511,11 +483,10 @@ __global__ void unpack_wgrad_dsplit_kernel(const float *__restrict__ ws, float *
 }  // namespace ramnet
 using namespace ramnet;
 
-extern "C" int ramnet_wgrad_dsplit_slabs(int Cin, int Cout) { return dsplit_splits(Cin, Cout); }
+extern "C" int ramnet_wgrad_dsplit_slabs(int Cin, int Cout) { return wgrad_dsplit_cap(Cin, Cout); }
 
 extern "C" size_t ramnet_wgrad_dsplit_ws_floats(int Cin, int Cout) { return (size_t)9 * cdiv(Cin, 32) * cdiv(Cout, 32) * 1024; }
 
 extern "C" int ramnet_unpack_wgrad_dsplit(const float *ws, float *grad, int Cout, int Cin, int CinWs, int CoutWs, int n_off, void *stream) {
-    RAMNET_CHECK_ARG(ws && grad && Cout > 0 && Cin > 0 && CinWs >= Cin && n_off >= 0 && CoutWs >= n_off + Cout);
-    return launch_1d(unpack_wgrad_dsplit_kernel, (size_t)Cout * Cin, stream, ws, grad, Cout, Cin, CinWs, CoutWs, n_off, (size_t)Cout * Cin);
+    return launch_wgrad_unpack(unpack_wgrad_dsplit_kernel, ws, grad, Cout, Cin, CinWs, CoutWs, n_off, stream);
 }

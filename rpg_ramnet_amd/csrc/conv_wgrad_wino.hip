@@ -28,8 +28,6 @@ namespace ramnet {
 // output channels per workgroup = 32 * NF: NF = 2 (two workgroups per CU) or 4 (one per CU, 256 accumulator VGPRs: every
 // transformed input row then feeds twice the MFMAs)
 
-constexpr int WGRAD_WINO_TARGET = 384;      // workgroups per launch the tile splits aim at
-
 struct WgradWinoParams {
     InSrc src;
     int bx_n, ty_n, nbatch;     // batches per row, tile rows per image, total
@@ -404,67 +402,39 @@ __global__ void unpack_wgrad_wino_kernel(const float *__restrict__ ws, float *__
 }
 
 int launch_wgrad_wino(const ramnet_wgrad_desc &d, hipStream_t st) {
-    RAMNET_CHECK_ARG(d.ntaps == 9 && d.stride == 1);
-    RAMNET_CHECK_ARG(d.in_mode != RAMNET_IN_UP2X && d.in_mode != RAMNET_IN_UP2X_SKIP);
-    RAMNET_CHECK_ARG(d.Ho == d.Hin && d.Wo == d.Win);
-    if (d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL) RAMNET_CHECK_ARG(d.C0 % 32 == 0);   // a workgroup's channels come from one tensor
-    if (d.in_mode == RAMNET_IN_S2D) RAMNET_CHECK_ARG(d.C0 >= 32 && log2_exact(d.C0) > 0);                 // ... or one parity group
     WgradWinoParams q{};
-    // the workspace rows follow the forward tap order (kh*3 + kw): require exactly that list
-    RAMNET_CHECK_ARG(taps_3x3(d.dy, d.dx, true, q.dy0, q.dx0));
+    if (int rc = wgrad3x3_check(d, 32, false, q.dy0, q.dx0)) return rc;
+    if (int rc = wgrad_offsets32(d, false)) return rc;
     fill_in_src(d, q.src);
-    q.bx_n = cdiv(d.Wo, 16), q.ty_n = cdiv(d.Ho, 2);
-    q.nbatch = q.bx_n * q.ty_n * d.B;
     // batches of 8 tiles: a 2 x 16 or an 8 x 4 pixel strip, whichever pads the map less
     const bool tall = (long)cdiv(d.Wo, 4) * 4 * cdiv(d.Ho, 8) * 8 < (long)cdiv(d.Wo, 16) * 16 * cdiv(d.Ho, 2) * 2;
-    if (tall) q.bx_n = cdiv(d.Wo, 4), q.ty_n = cdiv(d.Ho, 8), q.nbatch = q.bx_n * q.ty_n * d.B;
+    q.bx_n = cdiv(d.Wo, tall ? 4 : 16), q.ty_n = cdiv(d.Ho, tall ? 8 : 2), q.nbatch = q.bx_n * q.ty_n * d.B;
     // (A 128-channel workgroup — NF = 4: 256 accumulators, one workgroup per CU, 7.25 instead of 11 instructions per MFMA — was built in
     // round 3: six ConvGRU launches 1.522 -> 1.434 ms alone, training step 200.2 -> 190.5 samples/s co-scheduled; its launch path and
     // environment knob were removed in round 4, the kernel template keeps the parameter.)
     const int nf = g_opt_wgrad_wino_nf;
-    const int gy = cdiv(q.src.Cin, 32), gz = cdiv(d.Cout, 32 * nf);
     // co-scheduled with the backward-data chain on another stream (the training step): 384 workgroups leave it room (measured
-    // 256 ... 512: profiles/r03_h_tuning_notes.md)
-    int splits = g_opt_wgrad_wino_blocks * (2 / nf) / (gy * gz);            // (<= WGRAD_WINO_TARGET: the slabs are sized for that)
-    if (splits > q.nbatch) splits = q.nbatch;
-    if (d.dw_slabs > 0 && splits > d.dw_slabs) splits = d.dw_slabs;
-    if (splits < 1) splits = 1;
-    const dim3 grid(splits, gy, gz);
+    // 256 ... 512: profiles/r03_h_tuning_notes.md).  The own figure can exceed ramnet_wgrad_wino_slabs (conv_plan.hpp): dw_slabs bounds it.
+    const dim3 grid(wgrad_splits(wgrad_wino_own(q.src.Cin, d.Cout, nf), q.nbatch, d.dw_slabs), cdiv(q.src.Cin, 32), cdiv(d.Cout, 32 * nf));
     const size_t lds = ((size_t)2 * ((tall ? GrGeom<2>::XP : GrGeom<8>::XP) + 32 * 32 * nf) + 256 * 4) * sizeof(float);      // strips + scratch cells
-    const int xmk = d.in_mode == RAMNET_IN_RELUMASK ? 1 : d.in_mode == RAMNET_IN_CAT_MUL ? 2 : 0;
-    const bool gm = d.gmask != nullptr;
-    {
-        const unsigned long long px = (unsigned long long)d.Hin * d.Win, ldx = d.ld0 > d.ld1 ? d.ld0 : d.ld1;
-        RAMNET_CHECK_ARG(px * (d.in_mode == RAMNET_IN_S2D ? 4 : 1) * ldx * 4ull < WOOB && px * d.ldm * 4ull < WOOB &&
-                         (unsigned long long)d.Ho * d.Wo * d.ldg * 4ull < WOOB && (unsigned long long)d.Ho * d.Wo * d.ldgm * 4ull < WOOB);
-    }
-    note_kernel("conv_wgrad_wino_r_kernel<%d,%d,%d,%d>", xmk, (int)gm, tall ? 2 : 8, nf);
-#define RAMNET_GO(XMv, GMv)                                                                                                  \
-    do {                                                                                                                     \
-    if (tall && nf == 1) hipLaunchKernelGGL((conv_wgrad_wino_r_kernel<XMv, GMv, 2, 1>), grid, dim3(256), lds, st, d, q); \
-    else if (nf == 1) hipLaunchKernelGGL((conv_wgrad_wino_r_kernel<XMv, GMv, 8, 1>), grid, dim3(256), lds, st, d, q);    \
-    else if (tall) hipLaunchKernelGGL((conv_wgrad_wino_r_kernel<XMv, GMv, 2, 2>), grid, dim3(256), lds, st, d, q);       \
-    else hipLaunchKernelGGL((conv_wgrad_wino_r_kernel<XMv, GMv, 8, 2>), grid, dim3(256), lds, st, d, q);                 \
-    } while (0)
-    if (xmk == 1 && gm) RAMNET_GO(1, true);
-    else if (xmk == 1) RAMNET_GO(1, false);
-    else if (xmk == 2 && gm) RAMNET_GO(2, true);
-    else if (xmk == 2) RAMNET_GO(2, false);
-    else if (gm) RAMNET_GO(0, true);
-    else RAMNET_GO(0, false);
-#undef RAMNET_GO
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return wgrad_dispatch(d, [&](auto xmk, auto gm) {
+        constexpr int XM = decltype(xmk)::value;
+        constexpr bool GM = decltype(gm)::value;
+        note_kernel("conv_wgrad_wino_r_kernel<%d,%d,%d,%d>", XM, (int)GM, tall ? 2 : 8, nf);
+        if (tall && nf == 1) hipLaunchKernelGGL((conv_wgrad_wino_r_kernel<XM, GM, 2, 1>), grid, dim3(256), lds, st, d, q);
+        else if (nf == 1) hipLaunchKernelGGL((conv_wgrad_wino_r_kernel<XM, GM, 8, 1>), grid, dim3(256), lds, st, d, q);
+        else if (tall) hipLaunchKernelGGL((conv_wgrad_wino_r_kernel<XM, GM, 2, 2>), grid, dim3(256), lds, st, d, q);
+        else hipLaunchKernelGGL((conv_wgrad_wino_r_kernel<XM, GM, 8, 2>), grid, dim3(256), lds, st, d, q);
+        RAMNET_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 }  // namespace ramnet
 
 using namespace ramnet;
 
-extern "C" int ramnet_wgrad_wino_slabs(int Cin, int Cout) {
-    const int s = WGRAD_WINO_TARGET / (cdiv(Cin, 32) * cdiv(Cout, 64));
-    return s < 1 ? 1 : s;
-}
+extern "C" int ramnet_wgrad_wino_slabs(int Cin, int Cout) { return wgrad_wino_cap(Cin, Cout); }
 
 extern "C" int ramnet_reduce_slabs(float *ws, int slabs, size_t n, void *stream) {
     RAMNET_CHECK_ARG(ws && slabs >= 1 && n > 0 && n % 4 == 0 && ((uintptr_t)ws & 15) == 0);
@@ -477,6 +447,5 @@ extern "C" int ramnet_reduce_slabs(float *ws, int slabs, size_t n, void *stream)
 }
 
 extern "C" int ramnet_unpack_wgrad_wino(const float *ws, float *grad, int Cout, int Cin, int CinWs, int CoutWs, int n_off, void *stream) {
-    RAMNET_CHECK_ARG(ws && grad && Cout > 0 && Cin > 0 && CinWs >= Cin && n_off >= 0 && CoutWs >= n_off + Cout);
-    return launch_1d(unpack_wgrad_wino_kernel, (size_t)Cout * Cin, stream, ws, grad, Cout, Cin, CinWs, CoutWs, n_off, (size_t)Cout * Cin);
+    return launch_wgrad_unpack(unpack_wgrad_wino_kernel, ws, grad, Cout, Cin, CinWs, CoutWs, n_off, stream);
 }

@@ -35,8 +35,6 @@ namespace ramnet { __device__ unsigned long long g_probe_w6[16384 * 16]; }
 
 namespace ramnet {
 
-constexpr int WG6_TARGET = 384;      // workgroups per launch the tile splits aim at
-
 constexpr int WG6_MAXSEG = RAMNET_WGRAD_MAX_SEGMENTS;
 
 struct WgradWino6Params {
@@ -468,8 +466,7 @@ __global__ void unpack_wgrad_wino2x4_kernel(const float *__restrict__ ws, float 
     const size_t pos_stride = (size_t)nCiB * nCoB * 1024;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(i % Cin), n = (int)(i / Cin);
-        const int nn = n_off + n, c32 = c & 31;
-        const size_t at = ((size_t)(c >> 5) * nCoB + (nn >> 5)) * 1024 + ((nn & 31) + 32 * ((c32 >> 2) & 1)) * 16 + (c32 & 3) + 4 * (c32 >> 3);
+        const size_t at = wgrad_blocked_at(c, n_off + n, nCoB);
         double u[4][6];
         for (int a = 0; a < 4; ++a)
             for (int b = 0; b < 6; ++b) u[a][b] = ws[(size_t)(a * 6 + b) * pos_stride + at];
@@ -484,17 +481,15 @@ __global__ void unpack_wgrad_wino2x4_kernel(const float *__restrict__ ws, float 
 }
 
 bool wgrad_wino6_eligible(const ramnet_wgrad_desc &d) {
-    return d.ntaps == 9 && d.stride == 1 && d.Ho == d.Hin && d.Wo == d.Win &&
-           (d.in_mode == RAMNET_IN_PLAIN || d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL || d.in_mode == RAMNET_IN_RELUMASK ||
-            (d.in_mode == RAMNET_IN_S2D && d.C0 >= 32 && (d.C0 & (d.C0 - 1)) == 0));
+    int dy0, dx0;
+    return wgrad3x3_check(d, 32, true, dy0, dx0, true) == 0;
 }
 
 int launch_wgrad_wino6(const ramnet_wgrad_desc &d, hipStream_t st) {
-    RAMNET_CHECK_ARG(wgrad_wino6_eligible(d));
-    if (d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL) RAMNET_CHECK_ARG(d.C0 % 32 == 0);   // a workgroup's channels come from one tensor
-    const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
     WgradWino6Params q{};
-    RAMNET_CHECK_ARG(taps_3x3(d.dy, d.dx, true, q.dy0, q.dx0));      // the forward tap order kh*3 + kw
+    if (int rc = wgrad3x3_check(d, 32, true, q.dy0, q.dx0)) return rc;
+    if (int rc = wgrad_offsets32(d, true)) return rc;
+    const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
     fill_in_src(d, q.src);
     // strips of 8 tiles: 4 x 16, 8 x 8 or 16 x 4 output pixels, whichever pads the map least (ties: the widest)
     long best = -1;
@@ -513,47 +508,24 @@ int launch_wgrad_wino6(const ramnet_wgrad_desc &d, hipStream_t st) {
                          (d.gmask == nullptr) == (q.seg[i].gmask == nullptr));
     }
     q.bx_n = cdiv(d.Wo, 4 * txb), q.ty_n = cdiv(d.Ho, 16 / txb), q.nbatch = q.bx_n * q.ty_n * d.B * q.nseg;
-    const int gy = cdiv(q.src.Cin, 32), gz = cdiv(d.Cout, 32);
-    int splits = g_opt_wgrad_wino_blocks / (gy * gz);
-    if (splits > q.nbatch) splits = q.nbatch;
-    if (d.dw_slabs > 0 && splits > d.dw_slabs) splits = d.dw_slabs;
-    if (splits < 1) splits = 1;
-    // splits dealt to the XCDs (kernel): from 8 splits up, a multiple of 8 (the nearest the slabs and the batches allow)
-    q.xcd_map = 0;
+    q.gy = cdiv(q.src.Cin, 32), q.gz = cdiv(d.Cout, 32);
+    q.splits = wgrad_splits(wgrad_wino6_own(q.src.Cin, d.Cout), q.nbatch, d.dw_slabs);
 #ifndef RAMNET_NO_XCD_MAP
-    if (splits >= 8) {
-        int s8 = (splits + 4) / 8 * 8;
-        if (s8 > q.nbatch || (d.dw_slabs > 0 && s8 > d.dw_slabs)) s8 = splits / 8 * 8;
-        splits = s8, q.xcd_map = 1;
-    }
+    q.splits = wgrad_xcd_splits(q.splits, q.nbatch, d.dw_slabs, true, &q.xcd_map);      // the kernel deals the splits to the XCDs
 #endif
-    q.splits = splits, q.gy = gy, q.gz = gz;
-    const dim3 grid(splits * gy * gz);
+    const dim3 grid(q.splits * q.gy * q.gz);
     const int strips = txb == 4 ? G6Geom<4>::XTOT + G6Geom<4>::YTOT : txb == 2 ? G6Geom<2>::XTOT + G6Geom<2>::YTOT : G6Geom<1>::XTOT + G6Geom<1>::YTOT;
     const size_t lds = (size_t)(strips > 1024 ? strips : 1024) * sizeof(float);         // (the bias reduction reuses 32 x 32 floats)
-    const int xmk = d.in_mode == RAMNET_IN_RELUMASK ? 1 : d.in_mode == RAMNET_IN_CAT_MUL ? 2 : 0;
-    const bool gm = d.gmask != nullptr;
-    {
-        const unsigned long long px = (unsigned long long)d.Hin * d.Win * (d.in_mode == RAMNET_IN_S2D ? 4 : 1), ldx = d.ld0 > d.ld1 ? d.ld0 : d.ld1;
-        RAMNET_CHECK_ARG(d.B * px * ldx * 4ull < WOOB && d.B * px * d.ldm * 4ull < WOOB &&
-                         (unsigned long long)d.B * d.Ho * d.Wo * d.ldg * 4ull < WOOB && (unsigned long long)d.B * d.Ho * d.Wo * d.ldgm * 4ull < WOOB);
-    }
-    note_kernel("conv_wgrad_wino_r6_kernel<%d,%d,%d>", xmk, (int)gm, txb);
-#define RAMNET_GO(XMv, GMv)                                                                                               \
-    do {                                                                                                                  \
-        if (txb == 4) hipLaunchKernelGGL((conv_wgrad_wino_r6_kernel<XMv, GMv, 4>), grid, dim3(256), lds, st, d, q);       \
-        else if (txb == 2) hipLaunchKernelGGL((conv_wgrad_wino_r6_kernel<XMv, GMv, 2>), grid, dim3(256), lds, st, d, q);  \
-        else hipLaunchKernelGGL((conv_wgrad_wino_r6_kernel<XMv, GMv, 1>), grid, dim3(256), lds, st, d, q);                \
-    } while (0)
-    if (xmk == 1 && gm) RAMNET_GO(1, true);
-    else if (xmk == 1) RAMNET_GO(1, false);
-    else if (xmk == 2 && gm) RAMNET_GO(2, true);
-    else if (xmk == 2) RAMNET_GO(2, false);
-    else if (gm) RAMNET_GO(0, true);
-    else RAMNET_GO(0, false);
-#undef RAMNET_GO
-    RAMNET_LAUNCH_CHECK();
-    return 0;
+    return wgrad_dispatch(d, [&](auto xmk, auto gm) {
+        constexpr int XM = decltype(xmk)::value;
+        constexpr bool GM = decltype(gm)::value;
+        note_kernel("conv_wgrad_wino_r6_kernel<%d,%d,%d>", XM, (int)GM, txb);
+        if (txb == 4) hipLaunchKernelGGL((conv_wgrad_wino_r6_kernel<XM, GM, 4>), grid, dim3(256), lds, st, d, q);
+        else if (txb == 2) hipLaunchKernelGGL((conv_wgrad_wino_r6_kernel<XM, GM, 2>), grid, dim3(256), lds, st, d, q);
+        else hipLaunchKernelGGL((conv_wgrad_wino_r6_kernel<XM, GM, 1>), grid, dim3(256), lds, st, d, q);
+        RAMNET_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 }  // namespace ramnet
@@ -566,14 +538,10 @@ extern "C" int ramnet_probe_w6_read(unsigned long long *dst, size_t n) {
 }
 #endif
 
-extern "C" int ramnet_wgrad_wino2x4_slabs(int Cin, int Cout) {
-    const int s = WG6_TARGET / (cdiv(Cin, 32) * cdiv(Cout, 32));
-    return s < 1 ? 1 : s;
-}
+extern "C" int ramnet_wgrad_wino2x4_slabs(int Cin, int Cout) { return wgrad_wino6_cap(Cin, Cout); }
 
 extern "C" size_t ramnet_wgrad_wino2x4_ws_floats(int Cin, int Cout) { return (size_t)24 * cdiv(Cin, 32) * cdiv(Cout, 32) * 1024; }
 
 extern "C" int ramnet_unpack_wgrad_wino2x4(const float *ws, float *grad, int Cout, int Cin, int CinWs, int CoutWs, int n_off, void *stream) {
-    RAMNET_CHECK_ARG(ws && grad && Cout > 0 && Cin > 0 && CinWs >= Cin && n_off >= 0 && CoutWs >= n_off + Cout);
-    return launch_1d(unpack_wgrad_wino2x4_kernel, (size_t)Cout * Cin, stream, ws, grad, Cout, Cin, CinWs, CoutWs, n_off, (size_t)Cout * Cin);
+    return launch_wgrad_unpack(unpack_wgrad_wino2x4_kernel, ws, grad, Cout, Cin, CinWs, CoutWs, n_off, stream);
 }

@@ -10,6 +10,7 @@ import torch
 
 import conv_launch_cases as cc
 import conv_restatement as cr
+import wgrad_plan_cases as cp
 from guarded import BADARG, F64, In, Out, _bits, assert_bits, assert_exact, assert_within, call, call_desc
 from rpg_ramnet_amd import _hip
 
@@ -482,6 +483,50 @@ def test_wgrad_segments(i, nseg, slab_form):
     finally:
         L.ramnet_set_option(b"wgrad_wino_blocks", old)
     _wgrad_judge(i, d, st, "2x4", dw, dbias, S, "2x4 row %d, %d segments" % (i, nseg))
+
+
+PLANNED = cp.EXPECTED + cp.EXPECTED_DSPLIT
+
+
+@pytest.mark.parametrize("fam,opts,shape,want", PLANNED, ids=["%s-%s-%s" % (f, "x".join(map(str, s)), "-".join("%s%s" % kv for kv in o.items()) or "default")
+                                                             for f, o, s, _ in PLANNED])
+def test_wgrad_launch_uses_the_planned_splits(fam, opts, shape, want):
+    """How many tile splits a launch really uses, seen in the slab form: after ONE launch into a zeroed [S][one] workspace, S = the library's
+    slab query, exactly the slabs 0 .. splits - 1 hold something (normal data: every split's batches sum to non-zero values) and the rest is
+    bit-zero, for dw and for the dbias rows alike; splits, tile shape and nf as the restatement of the rule says (tests/wgrad_plan_cases.py),
+    which is first held to the values written down for this row.  PLAIN input, no masks; `dw_slabs` below S, lowered `wgrad_wino_blocks`,
+    `wgrad_wino_nf` and several segments as the row says."""
+    L = _hip.lib()
+    B, H, W, Cin, Cout = shape
+    p = cp.plan(fam, *shape, **opts)
+    assert {k: p[k] for k in want} == want, p
+    algo, slabs_fn, _, _ = WG_FAMS[fam]
+    S, one, nseg = getattr(L, slabs_fn)(Cin, Cout), _ws_floats(fam, Cin, Cout), opts.get("nseg", 1)
+    assert S == p["cap"] and 1 <= p["splits"] <= p["slabs"] <= S
+    g = cc._gen("planned splits %s %r" % (fam, shape))
+    segs = [dict(x0=In(cc._rn(g, (B, H, W, Cin)), ld=Cin + 4), dout=In(cc._rn(g, (B, H, W, Cout)), ld=Cout + 4)) for _ in range(nseg)]
+    dw, dbias = Out(S, one, prefill=torch.zeros(S, one)), Out(S, Cout, prefill=torch.zeros(S, Cout))
+    f = dict(ld0=Cin + 4, C0=Cin, in_mode=cr.IN_PLAIN, B=B, Hin=H, Win=W, ntaps=9, stride=1, dy=[t // 3 - 1 for t in range(9)],
+             dx=[t % 3 - 1 for t in range(9)], ldg=Cout + 4, Cout=Cout, Ho=H, Wo=W, dw=dw, dbias=dbias, algo=algo, dw_slabs=p["slabs"], **segs[0])
+    if nseg > 1:
+        arr = (_hip.WgradSeg * nseg)()
+        for k, seg in enumerate(segs):
+            arr[k].x0, arr[k].dout = seg["x0"].ptr, seg["dout"].ptr
+        f["nseg"], f["segs"] = nseg, C.cast(arr, C.POINTER(_hip.WgradSeg))
+    old = (L.ramnet_get_option(b"wgrad_wino_blocks"), L.ramnet_get_option(b"wgrad_wino_nf"))
+    try:
+        assert L.ramnet_set_option(b"wgrad_wino_blocks", opts.get("blocks", 384)) == 0
+        assert L.ramnet_set_option(b"wgrad_wino_nf", opts.get("nf", 1)) == 0
+        call_desc("ramnet_wgrad_launch", _hip.WgradDesc, f)
+        assert L.ramnet_last_kernel().decode() == p["kernel"]
+    finally:
+        L.ramnet_set_option(b"wgrad_wino_blocks", old[0])
+        L.ramnet_set_option(b"wgrad_wino_nf", old[1])
+    for what, buf in (("dw", dw), ("dbias", dbias)):
+        used = _bits(buf.value()).ne(0).any(dim=1)
+        print("%s: slabs in use %d of %d, planned %d" % (what, int(used.sum()), S, p["splits"]))
+        assert used.tolist() == [s < p["splits"] for s in range(S)], "%s: slabs in use %r, planned 0 .. %d" % (
+            what, used.nonzero().view(-1).tolist(), p["splits"] - 1)
 
 
 def test_split_third_term_adds_up():

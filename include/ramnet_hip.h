@@ -658,6 +658,23 @@ int ramnet_augment_batch(const float *const *src, float *const *dst, const int *
                          const int *win_host, const double *stats, const float *bx, const float *by, int G, int n_params, int C,
                          int H, int W, int th, int tw, int Cpad, int nhwc, void *stream);
 
+/* The same, followed by the datasets' scale_factor resize (dataset.py:127-140: F.interpolate(scale_factor = s, mode = 'bilinear',
+ * align_corners = False, recompute_scale_factor = False) AFTER the flip and crop) in the same launch (addition to ABI 27): every th x tw
+ * window leaves as oh x ow pixels, oh = floor(th * s), ow = floor(tw * s), 0 < s < 1.  Tables, parameters, stats, win_host and Cpad as
+ * above; dst[g] is [C][oh][ow], or [oh][ow][Cpad] with the pad channels zero.  Output pixel (y, x):
+ *   sy = max((y + 0.5) * (1 / s) - 0.5, 0) from the GIVEN factor, y0 = min(int(sy), th - 1), y1 = y0 + (y0 < th - 1), ly = sy - y0, columns
+ *   likewise; value = (1 - ly) ((1 - lx) a + lx b) + ly ((1 - lx) c + lx d), where a .. d are the WINDOW values at (y0, x0), (y0, x1),
+ *   (y1, x0), (y1, x1): the fp32 values ramnet_augment_batch would have written there (after flip, crop, rotation and the stats).
+ * Coordinates, weights and blend are evaluated in double without contraction and rounded once to fp32 (as ramnet_resize_metric_target);
+ * all four taps are always multiplied, so a NaN tap gives NaN at weight zero too.  Only the window is read and exactly G * C * oh * ow
+ * (nhwc: G * oh * ow * Cpad) floats are written; no atomics: the same bits on every launch.  With s = 0.5, NCHW, exact parameters, ow % 4 == 0
+ * and a 16-byte aligned destination a tensor takes a 4-pixels-per-thread path that gives the same bits.
+ * RAMNET_E_BADARG, nothing launched and nothing written: whatever ramnet_augment_batch refuses; scale_factor not in (0, 1) (NaN
+ * included); oh != floor(th * s) or ow != floor(tw * s); oh < 1 or ow < 1.  G = 0 is a no-op.                                        */
+int ramnet_augment_scale_batch(const float *const *src, float *const *dst, const int *pidx, const float *theta, const int *win,
+                               const int *win_host, const double *stats, const float *bx, const float *by, int G, int n_params, int C,
+                               int H, int W, int th, int tw, int oh, int ow, double scale_factor, int Cpad, int nhwc, void *stream);
+
 /* ---- training metrics of G (prediction, target) pairs: model/metric.py:8-54, lstm_trainer.py:100-106 ----------------------------
  * pred / target: DEVICE tables of G device pointers; pair g is a contiguous [N][npix] fp32 prediction and target (N x 1 x H x W;
  * NaN in the target = no ground truth; 4-byte alignment is enough).  Both are only read.  out[g][10] doubles, d = |t - p| in fp32:

@@ -183,6 +183,7 @@ _SIGS = {
     "ramnet_normalize_nonzero_batch": (C.c_int, [_fp, C.c_int, C.c_size_t, _fp, _fp]),
     "ramnet_nonzero_stats_batch": (C.c_int, [_fp, C.c_int, C.c_size_t, _fp, _fp]),
     "ramnet_augment_batch": (C.c_int, [_fp] * 9 + [C.c_int] * 9 + [_fp]),
+    "ramnet_augment_scale_batch": (C.c_int, [_fp] * 9 + [C.c_int] * 9 + [C.c_double, C.c_int, C.c_int, _fp]),
     "ramnet_batch_metrics_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_size_t]),
     "ramnet_batch_metrics": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_size_t, _fp, _fp, _fp]),
     "ramnet_metric_depth": (C.c_int, [_fp, C.c_size_t, C.c_float, C.c_float, C.c_int, _fp, _fp]),

@@ -7,6 +7,10 @@ angle and window.  What is computed differs from the host transform on purpose (
 flip + crop (values copied bit for bit, NaN included), where the host's ``grid_sample`` blurs by ~1e-4 and spreads every NaN over a 2x2
 window.  Any other angle is ``affine_grid`` + ``grid_sample`` (bilinear, zeros, align_corners=False) in fp32.
 
+``scale_factor`` < 1 (the datasets' ``scale_factor``, dataset.py:127-140: a bilinear ``F.interpolate`` AFTER the flip and crop) is fused into
+the same launch: the window is read, the reduced output is written.  Coordinates, weights and blend are evaluated in double and rounded
+once, where the host's ``F.interpolate`` rounds in fp32 at every step.
+
 No CPU or eager fallback: without the library ``HipLibraryMissing`` is raised."""
 import ctypes as C
 import random as _random
@@ -26,7 +30,7 @@ _launches = 0
 
 
 def launch_count():
-    """Number of ramnet_augment_batch launches this process has enqueued through this module."""
+    """Number of ramnet_augment_batch / ramnet_augment_scale_batch launches this process has enqueued through this module."""
     return _launches
 
 
@@ -160,10 +164,32 @@ def _slices(t, G):
     return tab
 
 
-def _launch(src_tab, dst_tab, pidx, tab, stats, G, Cc, th, tw, cpad, nhwc, device):
+def scaled_shape(th, tw, scale_factor, who="augment"):
+    """scale_factor -> None where nothing is resized (s >= 1, as the reference's ``if self.scale_factor < 1.0``), else (s, oh, ow) of a
+    th x tw window; ValueError for s <= 0, NaN and a window that keeps no pixel."""
+    s = float(scale_factor)
+    if not s > 0.0:
+        raise ValueError("%s: scale_factor must be positive, got %r" % (who, scale_factor))
+    if s >= 1.0:
+        return None
+    from .metrics import resized_shape
+    oh, ow = resized_shape((th, tw), s)
+    if oh < 1 or ow < 1:
+        raise ValueError("%s: a %d x %d window has no pixel left at scale_factor %r" % (who, th, tw, scale_factor))
+    return s, oh, ow
+
+
+def _launch(src_tab, dst_tab, pidx, tab, stats, G, Cc, th, tw, cpad, nhwc, device, scaled=None):
     global _launches
     from .ops import _p, _st
     bx, by = _base_coords(tab.H, tab.W, device)
+    if scaled is not None:
+        s, oh, ow = scaled
+        H.check(H.lib().ramnet_augment_scale_batch(_p(src_tab), _p(dst_tab), _p(pidx), _p(tab.theta_d), _p(tab.win_d), C.c_void_p(tab.win.data_ptr()),
+                                                   _p(stats), _p(bx), _p(by), G, tab.n, Cc, tab.H, tab.W, th, tw, oh, ow, C.c_double(s), cpad,
+                                                   1 if nhwc else 0, _st()), "ramnet_augment_scale_batch")
+        _launches += 1
+        return
     H.check(H.lib().ramnet_augment_batch(_p(src_tab), _p(dst_tab), _p(pidx), _p(tab.theta_d), _p(tab.win_d), C.c_void_p(tab.win.data_ptr()),
                                          _p(stats), _p(bx), _p(by), G, tab.n, Cc, tab.H, tab.W, th, tw, cpad, 1 if nhwc else 0, _st()),
             "ramnet_augment_batch")
@@ -174,14 +200,18 @@ def _out_shape(G, Cc, th, tw, nhwc, cpad):
     return (G, th, tw, cpad) if nhwc else (G, Cc, th, tw)
 
 
-def apply(x, params, pidx=None, out=None, nhwc=False, cpad=None, stats=None):
+def apply(x, params, pidx=None, out=None, nhwc=False, cpad=None, stats=None, scale_factor=1.0):
     """x: [G, C, H, W] fp32 on the device.  params: one ``Params`` (for every tensor), a list of them or a ``ParamTable``; pidx: which set
     tensor g uses (int32 [G] on the device, or a list; default: g, or 0 when there is one set).  Returns [G, C, th, tw], or with
     nhwc=True the model's input layout [G, th, tw, cpad] (channels zero-padded; default cpad: C rounded up to 4) — bitwise
     ``ops.pack_input`` of the NCHW result.  stats: [G, 3] float64 nonzero statistics (ramnet_nonzero_stats_batch) to normalise the source
-    values with while they are read.  One launch, on the current stream."""
+    values with while they are read.  scale_factor < 1: every window is resized to floor(th * s) x floor(tw * s) in the same launch (the
+    datasets' bilinear ``F.interpolate``, evaluated in double on the window's fp32 values and rounded once); >= 1: nothing is resized.
+    One launch, on the current stream."""
     if not (torch.is_tensor(x) and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous()):
         raise ValueError("augment.apply: x must be a contiguous fp32 [G, C, H, W] tensor")
+    if not float(scale_factor) > 0.0:
+        raise ValueError("augment.apply: scale_factor must be positive, got %r" % (scale_factor,))
     H.lib()
     if not x.is_cuda:
         raise ValueError("augment.apply: x must be on the GPU (the host transform is rpg_ramnet_amd.data's)")
@@ -200,7 +230,9 @@ def apply(x, params, pidx=None, out=None, nhwc=False, cpad=None, stats=None):
         cp = (Cc + 3) // 4 * 4 if cpad is None else int(cpad)
         if cp < Cc or cp % 4:
             raise ValueError("augment.apply: cpad=%d cannot hold %d channels in steps of 4" % (cp, Cc))
-    shape = _out_shape(G, Cc, tab.th, tab.tw, nhwc, cp)
+    scaled = scaled_shape(tab.th, tab.tw, scale_factor, "augment.apply")
+    oh, ow = (tab.th, tab.tw) if scaled is None else scaled[1:]
+    shape = _out_shape(G, Cc, oh, ow, nhwc, cp)
     if out is None:
         out = torch.empty(shape, device=x.device, dtype=torch.float32)
     elif tuple(out.shape) != shape or not out.is_contiguous() or out.dtype != torch.float32 or out.device != x.device:
@@ -208,7 +240,7 @@ def apply(x, params, pidx=None, out=None, nhwc=False, cpad=None, stats=None):
     if stats is not None and not (stats.dtype == torch.float64 and stats.numel() == 3 * G and stats.is_contiguous() and stats.device == x.device):
         raise ValueError("augment.apply: stats must be [G, 3] float64 on the device")
     if G:
-        _launch(_slices(x, G), _slices(out, G), pidx, tab, stats, G, Cc, tab.th, tab.tw, cp, nhwc, x.device)
+        _launch(_slices(x, G), _slices(out, G), pidx, tab, stats, G, Cc, tab.th, tab.tw, cp, nhwc, x.device, scaled)
     return out
 
 
@@ -227,8 +259,9 @@ class _Plan:
     """Everything one sequence's launches need, prepared (and uploaded) ahead of them: per (C, H, W) group the pointer tables, the
     parameter indices and the output buffer."""
 
-    def __init__(self, sequence, table, device, non_blocking=False):
+    def __init__(self, sequence, table, device, non_blocking=False, scale_factor=1.0):
         self.sequence, self.table, self.device = sequence, table, device
+        self.scaled = scaled_shape(table.th, table.tw, scale_factor, "augment")
         groups = {}
         for l, item in enumerate(sequence):
             for key, t in item.items():
@@ -240,7 +273,8 @@ class _Plan:
                     raise ValueError("augment: %r of package %d is %s, the parameters are for %d samples of %d x %d"
                                      % (key, l, tuple(t.shape), table.n, table.H, table.W))
                 groups.setdefault(int(t.shape[1]), []).append((l, key, t))
-        B, th, tw = table.n, table.th, table.tw
+        B = table.n
+        th, tw = (table.th, table.tw) if self.scaled is None else self.scaled[1:]          # what a launch writes
         self.groups = []
         words, total = [], 0
         for Cc, members in sorted(groups.items()):
@@ -270,7 +304,7 @@ class _Plan:
         out_seq = [{k: v for k, v in item.items() if k != "transform_seed"} for item in self.sequence]
         for Cc, members, out, first, n in self.groups:
             _launch(self.ptrs[first:first + n], self.ptrs[first + n:first + 2 * n], self.pidx[:n], self.table, None, n, Cc, self.table.th,
-                    self.table.tw, 0, False, self.device)
+                    self.table.tw, 0, False, self.device, self.scaled)
             for i, (l, key, _) in enumerate(members):
                 out_seq[l][key] = out[i]
         return out_seq
@@ -284,12 +318,13 @@ def _sequence_extent(sequence):
     raise ValueError("augment: the sequence holds no events* / image / depth_* tensor")
 
 
-def augment_sequence(sequence, seeds, transform, rng=None):
+def augment_sequence(sequence, seeds, transform, rng=None, scale_factor=1.0):
     """A collated sequence (list of L dicts of [B, C, H, W] device tensors) -> the same structure with every ``events*``, ``image`` and
     ``depth_*`` tensor transformed by its sample's parameters (``draw(transform, seeds[b], H, W)``; one seed per sample for the whole
     sequence, dataset.py:392), other keys passed through and ``transform_seed`` removed.  One launch per channel count — three for the
     RAM-Net recipe (event grids, frames, targets) — on the current stream.  seeds: [B] ints or a CPU tensor; None: the CPU tensor
-    ``sequence[0]['transform_seed']``."""
+    ``sequence[0]['transform_seed']``.  scale_factor < 1: the datasets' resize of every transformed tensor, in the same launches (``apply``);
+    the tensors must then be at full resolution (datasets built with ``defer_scale=True``)."""
     H.lib()
     sequence = list(sequence)
     if seeds is None:
@@ -298,17 +333,18 @@ def augment_sequence(sequence, seeds, transform, rng=None):
             raise ValueError("augment_sequence: no seeds given and the sequence carries no 'transform_seed'")
     Hh, W, device = _sequence_extent(sequence)
     table = ParamTable([draw(transform, s, Hh, W, rng=rng) for s in _seed_list(seeds)], Hh, W)
-    return _Plan(sequence, table, device).run()
+    return _Plan(sequence, table, device, scale_factor=scale_factor).run()
 
 
 # ------------------------------------------------------------------------------------------------ voxelise + normalise + transform
 def voxelize_augmented(cat, off, max_count, num_bins, width, height, params, pidx=None, out=None, scratch=None, normalize=True, nhwc=False,
-                       cpad=None):
+                       cpad=None, scale_factor=1.0):
     """Packed event lists (voxel.pack_event_lists) -> augmented grids: batched voxelisation into full-sensor grids, their nonzero statistics,
     then ONE launch that normalises and flips / rotates / crops while it reads (the reference normalises the full grid and then transforms,
     event_dataset.py:146-155, so the statistics cannot be had from cropped events).  Bitwise ``voxel.events_to_voxel_grids_packed(normalize=
     True)`` followed by ``apply``.  Allocation-free when ``params`` is an uploaded ParamTable, ``pidx`` a device tensor, and ``out`` and
-    ``scratch`` (``voxel_scratch``) are given; everything runs on the current stream."""
+    ``scratch`` (``voxel_scratch``) are given; everything runs on the current stream.  scale_factor < 1: the windows leave at the reduced
+    size (``apply``), normalised with the statistics of the full-resolution grids as before."""
     from . import voxel
     from .ops import _p, _st
     G = int(off.shape[0]) - 1
@@ -325,7 +361,7 @@ def voxelize_augmented(cat, off, max_count, num_bins, width, height, params, pid
             H.check(L.ramnet_nonzero_stats_batch_ordered(_p(grids), G, n, _p(stats), _p(part), _st()), "ramnet_nonzero_stats_batch_ordered")
         else:
             H.check(H.lib().ramnet_nonzero_stats_batch(_p(grids), G, n, _p(stats), _st()), "ramnet_nonzero_stats_batch")
-    return apply(grids, params, pidx=pidx, out=out, nhwc=nhwc, cpad=cpad, stats=stats if normalize else None)
+    return apply(grids, params, pidx=pidx, out=out, nhwc=nhwc, cpad=cpad, stats=stats if normalize else None, scale_factor=scale_factor)
 
 
 def voxel_scratch(G, num_bins, height, width, device):
@@ -335,19 +371,46 @@ def voxel_scratch(G, num_bins, height, width, device):
 
 
 # ------------------------------------------------------------------------------------------------ loader
+def _datasets_of(loader):
+    """The datasets behind a loader as far as they can be seen: through DataLoader.dataset and ConcatDataset.datasets."""
+    from torch.utils.data import DataLoader
+    seen, todo = [], [loader]
+    while todo:
+        ds = todo.pop()
+        if isinstance(ds, DataLoader):
+            todo.append(ds.dataset)
+        elif isinstance(getattr(ds, "datasets", None), (list, tuple)):
+            todo.extend(ds.datasets)
+        else:
+            seen.append(ds)
+    return seen
+
+
 class AugmentedLoader(D.DevicePrefetcher):
     """``data.DevicePrefetcher`` over a loader of ``defer_transform=True`` sequences, followed by ``augment_sequence``: while the caller
     trains on sequence k, sequence k + 1 — its untransformed tensors, pointer tables and parameter tables — is uploaded on the copy
     stream; the launches run on the consumer's stream when the sequence is handed out.  The seeds are read from the CPU batch before it
-    is uploaded: no device-to-host read and no synchronisation.  Yields what the trainer takes (lists of item dicts on the device)."""
+    is uploaded: no device-to-host read and no synchronisation.  Yields what the trainer takes (lists of item dicts on the device).
+    scale_factor < 1: the datasets' resize runs in the same launches; the datasets must then hand out full-resolution tensors
+    (``scale_factor=s, defer_transform=True, defer_scale=True``).  A dataset that this loader can reach (through ``DataLoader.dataset`` and
+    ``ConcatDataset.datasets``) and that has already resized on the host raises ValueError; behind any other wrapper the rule is the caller's."""
 
-    def __init__(self, loader, device, transform, pin=True):
+    def __init__(self, loader, device, transform, pin=True, scale_factor=1.0):
         super().__init__(loader, device, pin)
         if self.stream is None:
             raise ValueError("AugmentedLoader needs a GPU device (the host transform is the datasets' own)")
         H.lib()
         _split(transform)
         self.transform, self._rng = transform, _random.Random()
+        self.scale_factor = float(scale_factor)
+        if not self.scale_factor > 0.0:
+            raise ValueError("AugmentedLoader: scale_factor must be positive, got %r" % (scale_factor,))
+        if self.scale_factor < 1.0:
+            for ds in _datasets_of(loader):
+                s = getattr(ds, "scale_factor", None)
+                if isinstance(s, (int, float)) and s < 1.0 and not getattr(ds, "defer_scale", False):
+                    raise ValueError("AugmentedLoader: scale_factor=%r over a dataset that already resizes by %r on the host (build it with "
+                                     "defer_scale=True)" % (scale_factor, s))
 
     def _stage(self, sequence):
         sequence = list(sequence)
@@ -360,7 +423,7 @@ class AugmentedLoader(D.DevicePrefetcher):
         table = ParamTable([draw(self.transform, s, Hh, W, rng=self._rng) for s in seeds], Hh, W, pin=self.pin)
         with torch.cuda.stream(self.stream):
             moved = self._move(sequence)
-            return _Plan(moved, table, self.device, non_blocking=self.pin)
+            return _Plan(moved, table, self.device, non_blocking=self.pin, scale_factor=self.scale_factor)
 
     def __iter__(self):
         it = iter(self.loader)

@@ -143,6 +143,144 @@ __global__ void __launch_bounds__(256) augment_kernel(const float *const *__rest
     }
 }
 
+// ---- the window, then the datasets' scale_factor resize (dataset.py:127-140: F.interpolate(scale_factor = s, mode = 'bilinear',
+// align_corners = False, recompute_scale_factor = False) AFTER the flip and crop), in one launch: th x tw window -> oh x ow output,
+// oh = floor(th s), ow = floor(tw s), 0 < s < 1.  The four taps of an output pixel are WINDOW values — fp32, exactly what augment_kernel
+// would have written there (aug_val of a direct load, or aug_bilinear) — and source coordinate, weights and blend are evaluated in double
+// without contraction and rounded once (the rule of resize_metric_target_kernel): src = max((dst + 0.5) (1 / s) - 0.5, 0) from the GIVEN
+// factor, i0 = min(int(src), n - 1), i1 = i0 + (i0 < n - 1).  All four taps are always multiplied: a NaN tap gives NaN at weight zero too.
+// Only the window is read, only the scaled output is written; no LDS, no atomics: the same bits on every launch.
+struct aug_axis {
+    int i0, i1;
+    double l;
+};
+
+__device__ __forceinline__ aug_axis aug_scale_axis(unsigned d, int n, double rs) {
+#pragma clang fp contract(off)
+    aug_axis a;
+    const double s = fmax(((double)d + 0.5) * rs - 0.5, 0.0);
+    a.i0 = min((int)s, n - 1);
+    a.i1 = a.i0 + (a.i0 < n - 1);
+    a.l = s - (double)a.i0;
+    return a;
+}
+
+__device__ __forceinline__ float aug_scale_blend(float a, float b, float c, float d, double lx, double ly) {
+#pragma clang fp contract(off)
+    return (float)((1.0 - ly) * ((1.0 - lx) * (double)a + lx * (double)b) + ly * ((1.0 - lx) * (double)c + lx * (double)d));
+}
+
+// where window pixel (wy, wx) is read: the source offset (exact) or the sample point (general), the expressions of augment_kernel
+struct aug_tap {
+    size_t off;
+    float ix, iy;
+};
+
+template <bool EXACT>
+__device__ __forceinline__ aug_tap aug_scale_tap(const aug_params &a, const float *__restrict__ bx, const float *__restrict__ by, int wy, int wx, int H,
+                                                 int W) {
+    const int Y = wy + a.top, X = wx + a.left;
+    aug_tap t = {0, 0.f, 0.f};
+    if (EXACT) {
+        t.off = (size_t)(a.vflip ? H - 1 - Y : Y) * W + (a.hflip ? W - 1 - X : X);
+    } else {
+        const float xn = bx[X], yn = by[Y];
+        const float gx = a.t[0] * xn + a.t[1] * yn + a.t[2], gy = a.t[3] * xn + a.t[4] * yn + a.t[5];
+        t.ix = ((gx + 1.f) * W - 1.f) / 2.f, t.iy = ((gy + 1.f) * H - 1.f) / 2.f;
+    }
+    return t;
+}
+
+// one output pixel of one channel plane: the four window values and their blend
+template <bool EXACT>
+__device__ __forceinline__ float aug_scale_val(gsrc_t pl, const aug_tap (&t)[4], int H, int W, const aug_norm &n, double lx, double ly) {
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = EXACT ? aug_val(pl[t[k].off], n) : aug_bilinear(pl, H, W, t[k].ix, t[k].iy, n);
+    return aug_scale_blend(v[0], v[1], v[2], v[3], lx, ly);
+}
+
+// output pixel i of every channel.  The general mode (16 source loads per value) goes one channel at a time, in the NHWC layout with 4-byte
+// stores, so that the registers of the kernel stay those of the exact mode (four channels x four taps unrolled: 208 VGPRs, 2 waves per SIMD).
+template <bool NHWC, bool EXACT>
+__device__ __forceinline__ void aug_scale_pixel(gsrc_t src, gdst_t dst, const aug_params &a, const aug_norm &nrm, const float *__restrict__ bx,
+                                                const float *__restrict__ by, unsigned i, unsigned npix, int C, int H, int W, int th, int tw, int ow,
+                                                double rs, int Cpad) {
+    const size_t plane = (size_t)H * W;
+    const unsigned y = i / ow, x = i - y * ow;
+    const aug_axis ay = aug_scale_axis(y, th, rs), ax = aug_scale_axis(x, tw, rs);
+    const aug_tap t[4] = {aug_scale_tap<EXACT>(a, bx, by, ay.i0, ax.i0, H, W), aug_scale_tap<EXACT>(a, bx, by, ay.i0, ax.i1, H, W),
+                          aug_scale_tap<EXACT>(a, bx, by, ay.i1, ax.i0, H, W), aug_scale_tap<EXACT>(a, bx, by, ay.i1, ax.i1, H, W)};
+    if (NHWC && !EXACT) {
+        const gdst_t out = dst + (size_t)i * Cpad;
+#pragma unroll 1
+        for (int c = 0; c < Cpad; ++c) out[c] = c < C ? aug_scale_val<EXACT>(src + c * plane, t, H, W, nrm, ax.l, ay.l) : 0.f;
+    } else if (NHWC) {
+        const gdst_t out = dst + (size_t)i * Cpad;
+        for (int c = 0; c < Cpad; c += 4) {
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = c + j < C ? aug_scale_val<EXACT>(src + (c + j) * plane, t, H, W, nrm, ax.l, ay.l) : 0.f;
+            *(f4a __attribute__((address_space(1))) *)(out + c) = (f4a){v[0], v[1], v[2], v[3]};
+        }
+    } else {
+#pragma unroll 1
+        for (int c = 0; c < C; ++c) dst[(size_t)c * npix + i] = aug_scale_val<EXACT>(src + c * plane, t, H, W, nrm, ax.l, ay.l);
+    }
+}
+
+// blockIdx.y = tensor.  HALF: NCHW, exact, s = 0.5 (1 / s == 2: window rows 2y, 2y + 1 and columns 2x, 2x + 1 at weights 0.5), ow % 4 == 0 and
+// a 16-byte aligned destination, decided per tensor (uniform per workgroup): one thread per 4 output pixels = 2 rows x 8 columns of the
+// window in four under-aligned 16-byte loads (reversed in registers for a horizontal flip, rows mirrored for a vertical one) and one
+// 16-byte store, through the same blend as the per-pixel path below: the same bits.
+template <bool NHWC>
+__global__ void __launch_bounds__(256) augment_scale_kernel(const float *const *__restrict__ srcs, float *const *__restrict__ dsts, const int *__restrict__ pidx,
+                                                            const float *__restrict__ theta, const int *__restrict__ win, const double *__restrict__ stats,
+                                                            const float *__restrict__ bx, const float *__restrict__ by, int n_params, int C, int H, int W,
+                                                            int th, int tw, int oh, int ow, double rs, int Cpad) {
+    const int g = blockIdx.y;
+    int p = pidx ? pidx[g] : g;
+    p = min(max(p, 0), n_params - 1);
+    const gsrc_t src = (gsrc_t)srcs[g];
+    const gdst_t dst = (gdst_t)dsts[g];
+    const aug_params a = aug_load(theta, win, p, H, W, th, tw);
+    const aug_norm nrm = aug_norm_of(stats, g);
+    const size_t plane = (size_t)H * W;
+    const unsigned stride = gridDim.x * blockDim.x, first = blockIdx.x * blockDim.x + threadIdx.x;
+
+    if (!NHWC && a.exact && rs == 2.0 && (ow & 3) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+        const unsigned ow4 = ow >> 2, total = (unsigned)C * oh * ow4;
+        for (unsigned i = first; i < total; i += stride) {
+            const unsigned r = i / ow4, x4 = i - r * ow4;        // r = c * oh + y
+            const unsigned c = r / oh, y = r - c * oh;
+            const int Y = (int)(y * 2) + a.top, X = (int)(x4 * 8) + a.left;
+            const int r0 = a.vflip ? H - 1 - Y : Y, r1 = a.vflip ? r0 - 1 : r0 + 1;
+            const int sx = a.hflip ? W - 8 - X : X;               // the 8 source pixels are columns sx .. sx + 7 either way
+            const gsrc_t p0 = src + c * plane + (size_t)r0 * W + sx, p1 = src + c * plane + (size_t)r1 * W + sx;
+            const f4u q00 = *(const f4u __attribute__((address_space(1))) *)p0, q01 = *(const f4u __attribute__((address_space(1))) *)(p0 + 4);
+            const f4u q10 = *(const f4u __attribute__((address_space(1))) *)p1, q11 = *(const f4u __attribute__((address_space(1))) *)(p1 + 4);
+            float u[8], l[8];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                u[j] = a.hflip ? q01[3 - j] : q00[j], u[4 + j] = a.hflip ? q00[3 - j] : q01[j];
+                l[j] = a.hflip ? q11[3 - j] : q10[j], l[4 + j] = a.hflip ? q10[3 - j] : q11[j];
+            }
+            float v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                v[j] = aug_scale_blend(aug_val(u[2 * j], nrm), aug_val(u[2 * j + 1], nrm), aug_val(l[2 * j], nrm), aug_val(l[2 * j + 1], nrm), 0.5, 0.5);
+            *(f4a __attribute__((address_space(1))) *)(dst + (size_t)i * 4) = (f4a){v[0], v[1], v[2], v[3]};
+        }
+        return;
+    }
+
+    const unsigned npix = (unsigned)oh * ow;
+    if (a.exact)
+        for (unsigned i = first; i < npix; i += stride) aug_scale_pixel<NHWC, true>(src, dst, a, nrm, bx, by, i, npix, C, H, W, th, tw, ow, rs, Cpad);
+    else
+        for (unsigned i = first; i < npix; i += stride) aug_scale_pixel<NHWC, false>(src, dst, a, nrm, bx, by, i, npix, C, H, W, th, tw, ow, rs, Cpad);
+}
+
 }  // namespace ramnet
 
 using namespace ramnet;
@@ -175,5 +313,40 @@ extern "C" int ramnet_augment_batch(const float *const *src, float *const *dst, 
                            H, W, th, tw, Cpad);
     RAMNET_LAUNCH_CHECK();
     note_kernel(nhwc ? "augment_kernel<nhwc>" : "augment_kernel<nchw>");
+    return 0;
+}
+
+/* ramnet_augment_batch followed by the datasets' scale_factor resize of every window (th x tw -> oh x ow), in one launch. */
+extern "C" int ramnet_augment_scale_batch(const float *const *src, float *const *dst, const int *pidx, const float *theta, const int *win,
+                                          const int *win_host, const double *stats, const float *bx, const float *by, int G, int n_params, int C,
+                                          int H, int W, int th, int tw, int oh, int ow, double scale_factor, int Cpad, int nhwc, void *stream) {
+    RAMNET_CHECK_ARG(G >= 0 && G <= 65535 && n_params > 0 && C > 0 && H > 0 && W > 0);
+    RAMNET_CHECK_ARG(th > 0 && tw > 0 && th <= H && tw <= W);                       // the window fits the image
+    RAMNET_CHECK_ARG(scale_factor > 0.0 && scale_factor < 1.0);                     // (NaN fails both)
+    RAMNET_CHECK_ARG(oh >= 1 && ow >= 1 && oh == (int)floor((double)th * scale_factor) && ow == (int)floor((double)tw * scale_factor));
+    RAMNET_CHECK_ARG(!nhwc || (Cpad >= C && Cpad % 4 == 0));
+    RAMNET_CHECK_ARG((size_t)C * H * W < ((size_t)1 << 31) && (size_t)(nhwc ? Cpad : C) * oh * ow < ((size_t)1 << 31));
+    if (G == 0) return 0;
+    RAMNET_CHECK_ARG(src && dst && theta && win && bx && by);
+    if (win_host)
+        for (int p = 0; p < n_params; ++p) {
+            const int top = win_host[4 * p], left = win_host[4 * p + 1];
+            RAMNET_CHECK_ARG(top >= 0 && left >= 0 && top + th <= H && left + tw <= W);
+        }
+    const double rs = 1.0 / scale_factor;
+    size_t items = (size_t)oh * ow;                                                  // per-pixel path: one thread per output pixel
+    if (!nhwc && rs == 2.0 && ow % 4 == 0 && (size_t)C * oh * (ow / 4) > items) items = (size_t)C * oh * (ow / 4);
+    int gx = (int)((items + 255) / 256);
+    const int cap = (2048 * 4 + G - 1) / G;                                          // ~32 workgroups per CU over the whole launch
+    if (gx > cap) gx = cap;
+    if (gx < 1) gx = 1;
+    if (nhwc)
+        hipLaunchKernelGGL(augment_scale_kernel<true>, dim3(gx, G), dim3(256), 0, (hipStream_t)stream, src, dst, pidx, theta, win, stats, bx, by, n_params,
+                           C, H, W, th, tw, oh, ow, rs, Cpad);
+    else
+        hipLaunchKernelGGL(augment_scale_kernel<false>, dim3(gx, G), dim3(256), 0, (hipStream_t)stream, src, dst, pidx, theta, win, stats, bx, by, n_params,
+                           C, H, W, th, tw, oh, ow, rs, Cpad);
+    RAMNET_LAUNCH_CHECK();
+    note_kernel(nhwc ? "augment_scale_kernel<nhwc>" : "augment_scale_kernel<nchw>");
     return 0;
 }

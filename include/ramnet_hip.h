@@ -278,6 +278,21 @@ int ramnet_wgrad_dsplit_slabs(int Cin, int Cout);       /* the same for RAMNET_A
  * A launch with 0 < dw_slabs < ramnet_wgrad_slabs() uses dw_slabs splits.                                                              */
 #define RAMNET_WGRAD_SLAB_CAP 64
 int ramnet_wgrad_slabs(const ramnet_wgrad_desc *d);
+/* Addressing limits (additions to ABI 27; profiles/address_limit_tests_notes.md).  RAMNET_ABI_VERSION stays 27, as for the earlier
+ * additions marked so in this header: the number guards the layout of the two descriptor structs and the meaning of existing entry points,
+ * neither of which changes, and ten test modules and _hip.py pin it; a caller that needs the queries tests for the symbols.  Most convolution kernels reach their tensors through
+ * buffer resources with 32-bit byte offsets, and every family's launch refuses (RAMNET_E_BADARG) a descriptor whose operands it cannot
+ * address.  ramnet_conv_addressable / ramnet_wgrad_addressable: 1 when the launch of d->algo can address the operands of d — the SIZE
+ * guards of that launch alone (B, Hin, Win, Ho, Wo, HoF, WoF, HoG, WoG, the leading dimensions, in_mode, C0, Cout; o2 / gmask by being
+ * NULL or not; no pointer is read and nothing structural is checked), so that a caller can pick a family that can before a pass starts.
+ * Host arithmetic only, quiet (ramnet_last_error untouched).  The limits: every forward family: sources below 2^32 elements;
+ * RAMNET_ALGO_WINOGRAD / _2X4 / _2X4_SPLIT forward and backward-data: ONE image of every source and of every epilogue tensor below
+ * 0x7fffff00 bytes; their backward-weights: the WHOLE tensor of x0 / x1 / xm (plus one row and one pixel) / dout / gmask below 0x7fffff00
+ * bytes; RAMNET_ALGO_WINOGRAD24 / _2X3: the whole x0 below 0xffffffff bytes (RAMNET_IN_PARITY4: 2^30), packed weights below 0x7fffffff
+ * bytes, backward-weights: twice the bytes of x0 / dout / gmask below 0x7fffff00; RAMNET_ALGO_DIRECT / _DIRECT_SPLIT / _HEAD
+ * backward-weights: none (64-bit indices).                                                                                          */
+int ramnet_conv_addressable(const ramnet_conv_desc *d);
+int ramnet_wgrad_addressable(const ramnet_wgrad_desc *d);
 /* Floats of ONE slab of the RAMNET_ALGO_DIRECT_SPLIT workspace (ABI 23): blocked [9 taps][ceil(Cin/32)][ceil(Cout/32)][64 lanes][16], element
  * (tap, c, n) where ramnet_wgrad_wino2x4_ws_floats() puts (position, c, n); ramnet_unpack_wgrad_dsplit adds it into the OIHW gradient
  * [Cout][Cin][3][3] of output channels n_off .. n_off + Cout - 1 of a [CinWs][CoutWs] workspace.                                    */

@@ -205,6 +205,9 @@ _SIGS = {
     "ramnet_render_inputs": (C.c_int, [_fp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, _fp, _fp]),
     # ---- joins in a fixed order (additions to ABI 27): slab forms of the backward-weights families, ordered forms of the atomic joins
     "ramnet_wgrad_slabs": (C.c_int, [C.POINTER(WgradDesc)]),
+    # ---- addressing limits (additions to ABI 27): can the launch of d->algo address its operands?
+    "ramnet_conv_addressable": (C.c_int, [C.POINTER(ConvDesc)]),
+    "ramnet_wgrad_addressable": (C.c_int, [C.POINTER(WgradDesc)]),
     "ramnet_gemm_partial_floats": (C.c_size_t, [C.c_int] * 7),
     "ramnet_gemm_ordered": (C.c_int, [_fp, _fp, _fp] + [C.c_int] * 8 + [C.c_long] * 3 + [_fp, _fp]),
     "ramnet_gemm2_ordered": (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_long, C.c_long, C.c_long, C.c_int, _fp, _fp, _fp, C.c_int, C.c_long, C.c_long, C.c_long,

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include "common.hpp"
 #include "conv_epilogue.hpp"
+#include "conv_plan.hpp"
 
 namespace ramnet {
 
@@ -216,6 +217,15 @@ static int launch_cfg(const ramnet_conv_desc &d, const ConvCommon &qc, const Con
     return 0;
 }
 
+// the largest source tensor as the loaders stride it: px = B * Hin * Win (* 4: the space-to-depth view) pixels of ld = the largest pitch in use
+static void src_extent(const ramnet_conv_desc &d, unsigned long long &px, unsigned long long &ld) {
+    const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
+    ld = (unsigned long long)d.ld0;
+    if (cat || d.in_mode == RAMNET_IN_UP2X_SKIP) ld = ld > (unsigned long long)d.ld1 ? ld : (unsigned long long)d.ld1;
+    if (d.xm) ld = ld > (unsigned long long)d.ldm ? ld : (unsigned long long)d.ldm;
+    px = (unsigned long long)d.B * d.Hin * d.Win * (d.in_mode == RAMNET_IN_S2D ? 4 : 1);
+}
+
 static int check_desc(const ramnet_conv_desc &d) {
     RAMNET_CHECK_ARG(d.x0 && d.w && d.out);
     RAMNET_CHECK_ARG(d.ntaps >= 1 && d.ntaps <= 25 && (d.stride == 1 || d.stride == 2));
@@ -233,12 +243,10 @@ static int check_desc(const ramnet_conv_desc &d) {
     if (d.epi == RAMNET_EPI_GRU_BWD) RAMNET_CHECK_ARG(d.e0 && d.o1 && d.Cout % 8 == 0 && !d.bias && d.beta == 0.f && d.frame == 0 && d.out_s2d == 0);
     if (d.epi == RAMNET_EPI_SIGMOID_HR) RAMNET_CHECK_ARG(d.e1 && d.o1 && d.Cout % 8 == 0 && d.beta == 0.f && d.frame == 0 && d.out_s2d == 0 &&
                                                          d.algo != RAMNET_ALGO_WINOGRAD24 && d.algo != RAMNET_ALGO_WINOGRAD24_2X3 && d.algo != RAMNET_ALGO_HEAD);
-    // the patch loaders address their source tensors with 32-bit element offsets (16 GB per tensor: batch ~45 at 256x344x32)
+    // every family: the source tensors stay below 2^32 elements (16 GB per tensor: batch ~45 at 256x344x32)
     {
-        unsigned long long ld = (unsigned long long)d.ld0;
-        if (cat || d.in_mode == RAMNET_IN_UP2X_SKIP) ld = ld > (unsigned long long)d.ld1 ? ld : (unsigned long long)d.ld1;
-        if (d.xm) ld = ld > (unsigned long long)d.ldm ? ld : (unsigned long long)d.ldm;
-        const unsigned long long px = (unsigned long long)d.B * d.Hin * d.Win * (d.in_mode == RAMNET_IN_S2D ? 4 : 1);
+        unsigned long long px, ld;
+        src_extent(d, px, ld);
         RAMNET_CHECK_ARG(px * ld < (1ull << 32));
     }
     RAMNET_CHECK_ARG(d.frame >= 0);
@@ -383,6 +391,23 @@ extern "C" int ramnet_conv_launch(const ramnet_conv_desc *dp, void *stream) {
     }
     RAMNET_CHECK_ARG(dp->algo == RAMNET_ALGO_DIRECT && dp->in_mode != RAMNET_IN_S2D && dp->out_s2d == 0);   // fused space-to-depth: Winograd kernels only
     return launch_classes(dp, 1, (hipStream_t)stream);
+}
+
+// Can the launch of d->algo address its operands (the size guards of that launch alone, nothing structural)?  Quiet.
+extern "C" int ramnet_conv_addressable(const ramnet_conv_desc *dp) {
+    if (dp == nullptr || dp->B < 1 || dp->Hin < 1 || dp->Win < 1) return 0;
+    const ramnet_conv_desc &d = *dp;
+    unsigned long long px, ld;
+    src_extent(d, px, ld);
+    if (!(px * ld < (1ull << 32))) return 0;
+    switch (d.algo) {
+    case RAMNET_ALGO_WINOGRAD:
+    case RAMNET_ALGO_WINOGRAD_2X4_SPLIT: return check_offsets32(d, false, true) == 0;
+    case RAMNET_ALGO_WINOGRAD_2X4: return check_offsets32(d, d.epi == RAMNET_EPI_LSTM && d.o2, true) == 0;
+    case RAMNET_ALGO_WINOGRAD24:
+    case RAMNET_ALGO_WINOGRAD24_2X3: return fold_conv_addressable(d) ? 1 : 0;
+    default: return 1;
+    }
 }
 
 extern "C" int ramnet_conv_launch_multi(const ramnet_conv_desc *descs, int n, void *stream) {

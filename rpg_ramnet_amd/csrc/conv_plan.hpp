@@ -102,6 +102,24 @@ inline int check_offsets32(const ramnet_conv_desc &d, bool with_o2, bool quiet) 
     return 0;
 }
 
+// What the folded families (conv_wino24.hip, conv_wgrad_wino24.hip) address with 32-bit byte offsets into one buffer resource per tensor:
+// the WHOLE x0 of a forward launch, of a PARITY4 backward-data launch below 2^30 (window elements outside the tensor are given offsets from
+// 2^30 up), the packed weights; backward-weights: twice the bytes of x0 / dout / gmask below WOOB (a tile past the last one may stand up
+// to one grid stride of images beyond the tensor).  One statement for the launchers and for ramnet_conv_addressable / ramnet_wgrad_addressable.
+constexpr unsigned long long FOLD_X_LIMIT = 0xffffffffull, FOLD_DGRAD_X_LIMIT = 0x40000000ull, FOLD_W_LIMIT = 0x7fffffffull;
+inline unsigned long long fold_x_bytes(const ramnet_conv_desc &d) { return (unsigned long long)d.B * d.Hin * d.Win * d.ld0 * sizeof(float); }
+inline unsigned long long fold_w_bytes(const ramnet_conv_desc &d) {
+    return (d.algo == RAMNET_ALGO_WINOGRAD24_2X3 ? 120ull : 100ull) * d.C0 * d.Cout * sizeof(float);
+}
+inline bool fold_conv_addressable(const ramnet_conv_desc &d) {
+    return fold_x_bytes(d) < (d.in_mode == RAMNET_IN_PARITY4 ? FOLD_DGRAD_X_LIMIT : FOLD_X_LIMIT) && fold_w_bytes(d) < FOLD_W_LIMIT;
+}
+inline unsigned long long fold_wgrad_x_bytes(const ramnet_wgrad_desc &d) { return (unsigned long long)d.B * d.Hin * d.Win * d.ld0 * 4ull; }
+inline unsigned long long fold_wgrad_g_bytes(const ramnet_wgrad_desc &d, int ld) { return (unsigned long long)d.B * d.HoG * d.WoG * ld * 4ull; }
+inline bool fold_wgrad_addressable(const ramnet_wgrad_desc &d) {
+    return 2 * fold_wgrad_x_bytes(d) < WOOB && 2 * fold_wgrad_g_bytes(d, d.ldg) < WOOB && (!d.gmask || 2 * fold_wgrad_g_bytes(d, d.ldgm) < WOOB);
+}
+
 // Workgroup tile of F(2x4,3x3) for an Ho x Wo map: 32 tiles of 2 x 4 pixels as 16 x 16 (TXG 4), 32 x 8 (TXG 2) or 8 x 32 (TXG 8),
 // whichever pads the map least; returns the padded area.
 inline long wino6_tile(int Ho, int Wo, int &txg) {
@@ -185,12 +203,18 @@ inline int wgrad3x3_check(const ramnet_wgrad_desc &d, int group, bool segments, 
     return 0;
 }
 
-// The Winograd backward-weights kernels address their tensors with 32-bit byte offsets below WOOB: inside ONE image (F(2x2): the batch
-// walk moves the base) or inside the whole tensor of B images (F(2x4): `whole`).  dsplit addresses with 64-bit pixel indices: no check.
-inline int wgrad_offsets32(const ramnet_wgrad_desc &d, bool whole, bool quiet = false) {
-    const unsigned long long n = whole ? d.B : 1, px = n * d.Hin * d.Win * (d.in_mode == RAMNET_IN_S2D ? 4 : 1), gpx = n * d.Ho * d.Wo;
+// The Winograd backward-weights kernels (F(2x2) and F(2x4) alike) address every tensor (of a segment) through ONE buffer resource of WOOB
+// bytes with two 32-bit byte offsets: a per-lane one, the slot inside the strip of a batch, and a scalar one, the strip's corner, which
+// carries the image.  The hardware checks their SUM against the resource's extent (measured: profiles/address_limit_tests_notes.md), so the
+// WHOLE tensor of B images must end below WOOB — for the sources together with the halo in front of them: their resource begins one row
+// and one pixel before the tensor (the first strip's corner), and the last pixel's offset is longer by that much.  Beyond it a load of a
+// pixel INSIDE the tensor returns zero.  dsplit addresses with 64-bit pixel indices: no check.
+inline int wgrad_offsets32(const ramnet_wgrad_desc &d, bool quiet = false) {
+    const bool s2d = d.in_mode == RAMNET_IN_S2D;
+    const unsigned long long n = d.B, px = n * d.Hin * d.Win * (s2d ? 4 : 1) + (s2d ? 4ull * d.Win + 2 : d.Win + 1ull);
+    const unsigned long long mpx = n * d.Hin * d.Win + d.Win + 1ull, gpx = n * d.Ho * d.Wo;
     const unsigned long long ldx = d.ld0 > d.ld1 ? d.ld0 : d.ld1;
-    RAMNET_PLAN_CHECK(px * ldx * 4ull < WOOB && px * d.ldm * 4ull < WOOB && gpx * d.ldg * 4ull < WOOB && gpx * d.ldgm * 4ull < WOOB);
+    RAMNET_PLAN_CHECK(px * ldx * 4ull < WOOB && mpx * d.ldm * 4ull < WOOB && gpx * d.ldg * 4ull < WOOB && gpx * d.ldgm * 4ull < WOOB);
     return 0;
 }
 

@@ -157,6 +157,18 @@ static WgradShape wgrad_derive(const ramnet_wgrad_desc &d, WgradDerived &q) {
     return s;
 }
 
+// Can the launch of d->algo address its operands (the size guards of that launch alone, nothing structural)?  Quiet.
+extern "C" int ramnet_wgrad_addressable(const ramnet_wgrad_desc *dp) {
+    if (dp == nullptr || dp->B < 1 || dp->Hin < 1 || dp->Win < 1) return 0;
+    switch (dp->algo) {
+    case RAMNET_ALGO_WINOGRAD:
+    case RAMNET_ALGO_WINOGRAD_2X4: return wgrad_offsets32(*dp, true) == 0;
+    case RAMNET_ALGO_WINOGRAD24:
+    case RAMNET_ALGO_WINOGRAD24_2X3: return fold_wgrad_addressable(*dp) ? 1 : 0;
+    default: return 1;          // direct, direct-split, head: 64-bit pixel indices
+    }
+}
+
 // Largest number of splits a launch of this descriptor's algorithm and shape can use in its slab form (ramnet_hip.h)
 extern "C" int ramnet_wgrad_slabs(const ramnet_wgrad_desc *dp) {
     if (dp == nullptr) return 0;

@@ -106,7 +106,8 @@ __global__ void __launch_bounds__(256, NF == 4 ? 1 : NF == 1 ? 3 : 2) conv_wgrad
     int lb_ty = 0, lb_bx = 0;
     // Buffer resources built ONCE: each starts `pad` pixels in front of its tensor (the strip of a top / left batch begins before the
     // image: only out-of-image threads would reach that, and they read WOOB) and spans WOOB bytes; a batch then only moves four scalar
-    // byte offsets (32-bit: tensors are < WOOB bytes, checked on the host) instead of rebuilding four descriptors from 64-bit pointers
+    // byte offsets (32-bit, carrying the image; lane + scalar offset are range-checked together, so the whole tensor and its pad end
+    // below WOOB: wgrad_offsets32 on the host) instead of rebuilding four descriptors from 64-bit pointers
     const int pad_src = s2d ? -(q.dy0 * (4 * s.Win) + q.dx0 * 2) : -(q.dy0 * s.Win + q.dx0), pad_m = -(q.dy0 * s.Win + q.dx0);
     const int padS = pad_src > 0 ? pad_src : 0, padM = pad_m > 0 ? pad_m : 0;
     unsigned so_x = 0, so_m = 0, so_g = 0, so_gm = 0;
@@ -404,7 +405,7 @@ __global__ void unpack_wgrad_wino_kernel(const float *__restrict__ ws, float *__
 int launch_wgrad_wino(const ramnet_wgrad_desc &d, hipStream_t st) {
     WgradWinoParams q{};
     if (int rc = wgrad3x3_check(d, 32, false, q.dy0, q.dx0)) return rc;
-    if (int rc = wgrad_offsets32(d, false)) return rc;
+    if (int rc = wgrad_offsets32(d)) return rc;
     fill_in_src(d, q.src);
     // batches of 8 tiles: a 2 x 16 or an 8 x 4 pixel strip, whichever pads the map less
     const bool tall = (long)cdiv(d.Wo, 4) * 4 * cdiv(d.Ho, 8) * 8 < (long)cdiv(d.Wo, 16) * 16 * cdiv(d.Ho, 2) * 2;

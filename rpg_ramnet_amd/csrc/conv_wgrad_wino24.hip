@@ -14,6 +14,7 @@
 // (RAMNET_ALGO_WINOGRAD24_2X3, picked by wgrad_wino24_variant).
 #include <stdlib.h>
 #include "common.hpp"
+#include "conv_plan.hpp"
 
 namespace ramnet {
 
@@ -95,8 +96,8 @@ int launch_wgrad_wino24(const ramnet_wgrad_desc &d, hipStream_t st) {
     q.x = d.x0, q.g = d.dout, q.gm = d.gmask, q.dw = d.dw, q.dbias = d.dbias;
     q.ldx = d.ld0, q.ldg = d.ldg, q.ldgm = d.ldgm, q.Hp = d.Hin, q.Wp = d.Win, q.H2 = d.HoG, q.W2 = d.WoG, q.Hc = d.Ho, q.Wc = d.Wo;
     q.Cin = d.C0, q.Cout = d.Cout;
-    q.xbytes = (size_t)d.B * d.Hin * d.Win * d.ld0 * 4, q.gbytes = (size_t)d.B * d.HoG * d.WoG * d.ldg * 4;
-    q.gmbytes = d.gmask ? (size_t)d.B * d.HoG * d.WoG * d.ldgm * 4 : 0;
+    q.xbytes = fold_wgrad_x_bytes(d), q.gbytes = fold_wgrad_g_bytes(d, d.ldg);
+    q.gmbytes = d.gmask ? fold_wgrad_g_bytes(d, d.ldgm) : 0;
     // per-lane 32-bit byte offsets; a tile past the last one may stand up to one grid stride of images beyond the tensor
     RAMNET_CHECK_ARG(2 * q.xbytes < WOOB && 2 * q.gbytes < WOOB && 2 * q.gmbytes < WOOB);
     const int tiles_per_batch = f23 ? G23_T : G24_T;

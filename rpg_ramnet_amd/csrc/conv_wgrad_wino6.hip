@@ -488,7 +488,7 @@ bool wgrad_wino6_eligible(const ramnet_wgrad_desc &d) {
 int launch_wgrad_wino6(const ramnet_wgrad_desc &d, hipStream_t st) {
     WgradWino6Params q{};
     if (int rc = wgrad3x3_check(d, 32, true, q.dy0, q.dx0)) return rc;
-    if (int rc = wgrad_offsets32(d, true)) return rc;
+    if (int rc = wgrad_offsets32(d)) return rc;
     const bool cat = d.in_mode == RAMNET_IN_CAT || d.in_mode == RAMNET_IN_CAT_MUL;
     fill_in_src(d, q.src);
     // strips of 8 tiles: 4 x 16, 8 x 8 or 16 x 4 output pixels, whichever pads the map least (ties: the widest)

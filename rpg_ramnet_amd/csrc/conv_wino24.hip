@@ -597,8 +597,8 @@ static int launch_wino24_dgrad(const ramnet_conv_desc &d, hipStream_t st) {
     q.ksplit = 1, q.ws = nullptr, q.cnt = nullptr;
     q.Hc = d.Hin / 2, q.Wc = d.Win / 2;
     const bool w23 = d.algo == RAMNET_ALGO_WINOGRAD24_2X3;
-    const size_t xb = (size_t)d.B * d.Hin * d.Win * d.ld0 * sizeof(float), wb = (size_t)(w23 ? 120 : 100) * d.C0 * d.Cout * sizeof(float);
-    RAMNET_CHECK_ARG(xb < 0x40000000ull && wb < 0x7fffffffull);          // invalid window elements use offsets >= 2^30
+    const size_t xb = fold_x_bytes(d), wb = fold_w_bytes(d);
+    RAMNET_CHECK_ARG(xb < FOLD_DGRAD_X_LIMIT && wb < FOLD_W_LIMIT);      // invalid window elements use offsets >= 2^30 (conv_plan.hpp)
     q.xbytes = (unsigned)xb, q.wbytes = (unsigned)wb;
     if (w23) {
         const bool half = fold_halfwg_variant(d, 0);
@@ -703,8 +703,8 @@ int launch_wino24(const ramnet_conv_desc &d, hipStream_t st) {
     q.x = d.x0, q.wp = d.w, q.Hp = d.Hin, q.Wp = d.Win, q.ldx = d.ld0;
     q.nchunks = d.C0 / (wide ? 16 : 8), q.nblk = pair ? 1 : d.Cout / (wide ? 64 : 32);
     q.Hc = d.Ho, q.Wc = d.Wo, q.cpc = 1;
-    const size_t xb = (size_t)d.B * d.Hin * d.Win * d.ld0 * sizeof(float), wb = (size_t)(w23 ? 120 : 100) * d.C0 * d.Cout * sizeof(float);
-    RAMNET_CHECK_ARG(xb < 0xffffffffull && wb < 0x7fffffffull);
+    const size_t xb = fold_x_bytes(d), wb = fold_w_bytes(d);
+    RAMNET_CHECK_ARG(xb < FOLD_X_LIMIT && wb < FOLD_W_LIMIT);
     q.xbytes = (unsigned)xb, q.wbytes = (unsigned)wb;
     if (w23) {
         q.ksplit = 1, q.ws = nullptr, q.cnt = nullptr;

@@ -337,8 +337,11 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r6_kernel(const ramnet_conv_
         unsigned lbad[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) lbad[i] = (ox0 + lpx < p.Wo && oy0 + lpy + i * LSTEP < p.Ho) ? 0u : WOOB;
-        auto loff = [&](int ld, bool have, int i) {
-            return have ? ((lpix * (unsigned)ld + (unsigned)lchn) * 4u + (unsigned)(i * LSTEP * p.WoF * ld * 4)) | lbad[i] : WOOB;
+        // (dn: channels added to the quad — the gates of o2.  They go in BEFORE the pixel's WOOB is OR-ed in: an out-of-map row of an image
+        // near 2 GB has an offset with bit 31 set, `offset | WOOB` is then 0xffffffXX, and adding a gate's 4 C k bytes to THAT wraps to the
+        // first bytes of the image, inside the resource)
+        auto loff = [&](int ld, bool have, int i, int dn = 0) {
+            return have ? ((lpix * (unsigned)ld + (unsigned)(lchn + dn)) * 4u + (unsigned)(i * LSTEP * p.WoF * ld * 4)) | lbad[i] : WOOB;
         };
         float4 cp[2], hp[2];
 #pragma unroll
@@ -368,8 +371,8 @@ __global__ void __launch_bounds__(256, 2) conv_wino_r6_kernel(const ramnet_conv_
             if (MASK) hn = lsel(hn, hp[i]), cn = lsel(cn, c), gi = lsel(gi, f4zero()), gf = lsel(gf, f4zero()), go = lsel(go, f4zero()), gc = lsel(gc, f4zero());
             bst(r_out, loff(p.ldo, true, i), hn);
             bst(r_cn, loff(p.ldo1, true, i), cn);
-            const unsigned og = loff(p.ldo2, p.o2 != nullptr, i);      // (+ 12 C bytes at most on WOOB | offset: still out of range)
-            bst(r_g, og, gi), bst(r_g, og + (unsigned)C * 4u, gf), bst(r_g, og + (unsigned)C * 8u, go), bst(r_g, og + (unsigned)C * 12u, gc);
+            const bool og = p.o2 != nullptr;
+            bst(r_g, loff(p.ldo2, og, i), gi), bst(r_g, loff(p.ldo2, og, i, C), gf), bst(r_g, loff(p.ldo2, og, i, 2 * C), go), bst(r_g, loff(p.ldo2, og, i, 3 * C), gc);
         }
         return;
     }

@@ -379,6 +379,51 @@ def _fold_wgrad_2x3(B, Hh, W, Cin, Cout):
     return hit
 
 
+# Addressing limits (csrc/conv_plan.hpp; profiles/address_limit_tests_notes.md): most convolution kernels reach their tensors through 32-bit
+# byte offsets, and a launch refuses operands it cannot address.  The callers below ask the library BEFORE they pick a family
+# (ramnet_conv_addressable / ramnet_wgrad_addressable: the size guards of the launch, host arithmetic) and take one that can — the direct
+# kernels address with 64-bit indices —, so that no launch of a pass is refused for a reason of size.  Cached per shape.
+_ADDRESSABLE = {}
+
+
+def _fold_desc_fits(kind, B, Hh, W, Cin, Cout):
+    """Can the one-launch form of a folded decoder address its operands at low-resolution shape [B][Hh][W]?  kind:
+    "dgrad" (the RAMNET_IN_PARITY4 launch over dy [B][2Hh][2W][Cout]), "wgrad" (padded input, dy and its mask)."""
+    key = (kind, B, Hh, W, Cin, Cout)
+    hit = _ADDRESSABLE.get(key)
+    if hit is None:
+        if kind == "wgrad":
+            d = H.WgradDesc()
+            d.algo, d.in_mode, d.stride = H.ALGO_WINOGRAD24, H.IN_PLAIN, 1
+            d.B, d.Hin, d.Win, d.Ho, d.Wo, d.HoG, d.WoG = B, Hh + 4, W + 4, Hh, W, 2 * Hh, 2 * W
+            d.C0 = d.ld0 = Cin
+            d.Cout = d.ldg = d.ldgm = Cout
+            hit = bool(H.lib().ramnet_wgrad_addressable(C.byref(d)))
+        else:
+            d = H.ConvDesc()
+            d.algo, d.stride, d.B = H.ALGO_WINOGRAD24, 1, B
+            # (reduces over the layer's output channels, produces its input channels)
+            d.in_mode, d.Hin, d.Win, d.C0, d.ld0, d.Cout = H.IN_PARITY4, 2 * Hh, 2 * W, Cout, Cout, Cin
+            hit = bool(H.lib().ramnet_conv_addressable(C.byref(d)))
+        _ADDRESSABLE[key] = hit
+    return hit
+
+
+def _wino_wgrad_fits(x0, dout, x1=None, xm=None, gmask=None, in_mode=H.IN_PLAIN, Hin=None, Win=None):
+    """Can the Winograd backward-weights kernels (F(2x2,3x3) and F(2x4,3x3): one guard) address the operands of this launch?"""
+    key = ("w3", tuple(x0.shape), ld(x0), ld(dout), tuple(dout.shape[1:3]), ld(x1) if x1 is not None else 0, ld(xm) if xm is not None else 0,
+           ld(gmask) if gmask is not None else 0, in_mode, Hin, Win)
+    hit = _ADDRESSABLE.get(key)
+    if hit is None:
+        d = H.WgradDesc()
+        d.algo, d.in_mode, d.stride = H.ALGO_WINOGRAD_2X4, in_mode, 1
+        d.B, d.Hin, d.Win = x0.shape[0], (x0.shape[1] if Hin is None else Hin), (x0.shape[2] if Win is None else Win)
+        d.Ho, d.Wo = dout.shape[1], dout.shape[2]
+        d.ld0, d.ld1, d.ldm, d.ldg, d.ldgm = key[2], key[5], key[6], key[3], key[7]
+        hit = _ADDRESSABLE[key] = bool(H.lib().ramnet_wgrad_addressable(C.byref(d)))
+    return hit
+
+
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _RAW_DEVICE = getattr(torch._C, "_cuda_getDevice", None)
 
@@ -559,7 +604,7 @@ def _conv_desc_build(x0, taps, w, out, Cout, meta, *, stride=1, x1=None, xm=None
     d.ld0, d.ld1, d.ldm = ld(x0), (ld(x1) if x1 is not None else 0), (ld(xm) if xm is not None else 0)
     d.C0, d.C1, d.in_mode = (x0.shape[3] if C0 is None else C0), C1, in_mode
     d.algo = H.ALGO_DIRECT
-    ref = None
+    ref, pref = None, w                 # (pref: the layer's PackRef, if `w` is one)
     cp = w.cp if isinstance(w, PackRef) else ws_owner            # the layer that owns the split-reduction workspace
     if isinstance(w, PackRef) and beta == 0.0 and frame == 0 and os == (1, 1, 0, 0) and uses_head(taps, w, stride, epi, in_mode):
         d.algo, d.head_cin = H.ALGO_HEAD, w.cp.Cin
@@ -590,6 +635,14 @@ def _conv_desc_build(x0, taps, w, out, Cout, meta, *, stride=1, x1=None, xm=None
     d.lde0, d.lde1 = (ld(e0) if e0 is not None else 0), (ld(e1) if e1 is not None else 0)
     d.out, d.o1, d.o2 = _p(out, out_off), _p(o1), _p(o2)
     d.ldo, d.ldo1, d.ldo2 = ld(out), (ld(o1) if o1 is not None else 0), (ld(o2) if o2 is not None else 0)
+    if d.algo == H.ALGO_WINOGRAD and not H.lib().ramnet_conv_addressable(C.byref(d)):
+        # an image of a source or of an epilogue tensor beyond the 32-bit byte offsets of the Winograd kernels: the direct kernel (64-bit
+        # indices) takes the launch; the fused space-to-depth views exist on the Winograd kernels alone
+        if in_mode == H.IN_S2D or out_s2d:
+            raise RuntimeError("space-to-depth convolution: one image of an operand reaches 2 GB (0x7fffff00 bytes), beyond the 32-bit byte "
+                               "offsets of the Winograd kernels, and no other kernel reads this view (set_space_to_depth_fused(False))")
+        d.algo, d.s2d_5x5, ref, kind = H.ALGO_DIRECT, 0, None, False
+        d.w = _p(pref.cp.pack(pref.transposed, False))
     if wino24:          # w = ConvParam.pack_fold_wino(): all four parities in one Winograd F(2x2,4x4) launch
         d.algo = H.ALGO_WINOGRAD24
     if ref is not None and _WINO_2X4 != "off" and H.lib().ramnet_conv_wino_variant(C.byref(d), int(_WINO_2X4 == "force")):
@@ -1270,9 +1323,10 @@ class ConvParam:
         (_FOLD_LAYOUTS), the [16 taps][CinWs][Cout] of ONE parity class of the direct launches without one."""
         return (4 * _FOLD_LAYOUTS[kind][0] if kind else 16) * self.CinWs * self.Cout
 
-    def _choose_layout(self, wino_ok):
-        """(kind, slabs) of the weight-gradient workspace for the pass that starts: one algorithm per layer and pass."""
-        wino = bool(wino_ok and _WINOGRAD and self.k == 3 and self.CinWs >= _WINO_MIN_CIN)
+    def _choose_layout(self, wino_ok, fits=True):
+        """(kind, slabs) of the weight-gradient workspace for the pass that starts: one algorithm per layer and pass.  fits: the Winograd
+        backward-weights kernels can address the launch's operands (_wino_wgrad_fits); else the direct kernel (64-bit indices) takes the pass."""
+        wino = bool(wino_ok and fits and _WINOGRAD and self.k == 3 and self.CinWs >= _WINO_MIN_CIN)
         # F(2x4,3x3) for the plain 3x3 layers (not the space-to-depth views): slabs of [24][Cin][Cout], half as many as F(2x2)'s
         wino6 = bool(wino and (_WGRAD_2X4 == "force" or (_WGRAD_2X4 == "auto" and _USE_SIDE))
                      and (type(self) is ConvParam or (_S2D_2X4 and self.Cin >= 128)) and self.CinWs >= 64)
@@ -1283,10 +1337,12 @@ class ConvParam:
         ns = getattr(H.lib(), _LAYOUTS[kind][1])(self.CinWs, self.Cout)
         return kind, (min(self._slabs, ns) if kind == "wino6" else ns)
 
-    def grad_ws(self, wino_ok=False):
+    def grad_ws(self, wino_ok=False, launch=None):
         """([tap][CinWs][Cout] weight-gradient workspace, [Cout] bias-gradient workspace), zero at pass start.
         wino_ok: the caller's launch is a plain 3x3 stride-1 convolution (no upsampling loader), i.e. eligible for the
-        Winograd backward-weights kernel, whose workspace holds the transformed-domain gradient [16][CinWs][Cout]."""
+        Winograd backward-weights kernel, whose workspace holds the transformed-domain gradient [16][CinWs][Cout].
+        launch: the tensor arguments of that launch (keywords of _wino_wgrad_fits): the layout is a Winograd one only if those kernels can
+        address them."""
         m, b = self._main, self._bias_ws
         if m.t is None:
             dev = self.weights[0].device
@@ -1301,7 +1357,8 @@ class ConvParam:
             b.reserve(dev, self._slabs * self.Cout)
         _Engine.enter()         # (a new pass after an aborted one resets _dirty first)
         if not self._dirty:     # every launch of the pass accumulates into the same layout
-            kind, ns = self._choose_layout(wino_ok)         # (deterministic mode: the direct / head launches own slabs as well, [S][k x k][CinWs][Cout])
+            fits = not (wino_ok and launch) or _wino_wgrad_fits(**launch)
+            kind, ns = self._choose_layout(wino_ok, fits)   # (deterministic mode: the direct / head launches own slabs as well, [S][k x k][CinWs][Cout])
             det = _det_slab_query(H.ALGO_DIRECT, self.CinWs, self.Cout, self.k) if (_DETERMINISTIC and kind == "direct") else 0
             one, count = self._slab_floats(kind), (det if kind == "direct" else ns)      # `count` slabs for finalize() to join
             n = count * one if (det or kind == "dsplit") else 0         # (every other layout fits the first allocation)
@@ -1466,7 +1523,7 @@ class StateHalfConvParam(ConvParam):
     def _cat_w(self):
         return self.parent._cat_w()[:, self.Cin:].contiguous()
 
-    def grad_ws(self, wino_ok=False):
+    def grad_ws(self, wino_ok=False, launch=None):
         raise RuntimeError("StateHalfConvParam: backward-data operand only; the weight gradient belongs to the parent layer")
 
     def finalize(self):
@@ -1674,7 +1731,7 @@ def _folded_upsample_wgrad(x, skip, dy, y, cp, xpad=None):
             H.check(L.ramnet_pad2_sum_im2col(_p(x), _p(skip), _p(xpad), _p(a_rows), _p(a_cols), B, Hh, W, Cc, _st()), "ramnet_pad2_sum_im2col")
         else:
             H.check(L.ramnet_up2x_border_im2col(_p(x), _p(skip), _p(a_rows), _p(a_cols), B, Hh, W, Cc, _st()), "ramnet_up2x_border_im2col")
-        if _FOLD_WINO_WGRAD and cp._fold_one_launch():
+        if _FOLD_WINO_WGRAD and cp._fold_one_launch() and _fold_desc_fits("wgrad", B, Hh, W, Cc, cp.Cout):
             # one launch, all four parities, in the Winograd F(2x2,4x4) or F(2x3,4x4) domain (csrc/conv_wgrad_wino24.hip)
             kind = "fold23" if _fold_wgrad_2x3(B, Hh, W, Cc, cp.Cout) else "fold24"
             wgrad_launch(xpad, Taps.get("fold", 4, 0, 0, 0), dy, cp.grad_ws_fold24(kind), cp.Cout, gmask=y, dbias=bws, Ho=Hh, Wo=W,
@@ -1694,7 +1751,7 @@ def _folded_upsample_wgrad(x, skip, dy, y, cp, xpad=None):
 
 def _fold_dgrad_ok(B, H2, W2, cp):
     return bool(_FOLD_DGRAD and _FOLD_UP and cp.Cout % 16 == 0 and cp.Cin % 64 == 0
-                and B * H2 * W2 * cp.Cout * 4 < 2 ** 30)
+                and _fold_desc_fits("dgrad", B, H2 // 2, W2 // 2, cp.Cin, cp.Cout))
 
 
 def _folded_upsample_dgrad(x, dy, y, cp):
@@ -1755,7 +1812,10 @@ class ConvAct(Function):
         epi = H.EPI_RELU if relu else H.EPI_LINEAR
         xpad = None
         ctx.s2d = _s2d_eligible(x, cp, k, stride, up)
-        ctx.s2d_fused = ctx.s2d and _s2d_fused(x.shape[3])
+        # (the fused view exists on the Winograd kernels alone: where a weight gradient is wanted and their backward-weights cannot address
+        # x and y — whole tensors of 2 GB — the layer takes the materialised view, whose backward-weights the direct kernel can run)
+        ctx.s2d_fused = ctx.s2d and _s2d_fused(x.shape[3]) and (not _wants(ctx, 2, 3) or _wino_wgrad_fits(
+            x0=x, dout=y, gmask=y if relu else None, in_mode=H.IN_S2D, Hin=Hh // 2, Win=W // 2))
         if ctx.s2d_fused:   # ... reading the four parities straight from x
             conv_launch(x, Taps.get("conv_s2d", 3, 1), cp.s2d().fwd(), y, cp.Cout, in_mode=H.IN_S2D, Hin=Hh // 2, Win=W // 2,
                         bias=cp.bias(), epi=epi)
@@ -1792,7 +1852,7 @@ class ConvAct(Function):
             sp = cp.s2d()
             Hl, Wl = xs.shape[1] // 2, xs.shape[2] // 2
             if want_w:
-                ws, bws = sp.grad_ws(wino_ok=True)
+                ws, bws = sp.grad_ws(wino_ok=True, launch=dict(x0=x, dout=dy, gmask=y if relu else None, in_mode=H.IN_S2D, Hin=Hl, Win=Wl))
                 wgrad_side([x, dy, y], x, Taps.get("conv_s2d", 3, 1), dy, ws, cp.Cout, in_mode=H.IN_S2D, Hin=Hl, Win=Wl,
                            gmask=y if relu else None, dbias=bws)
             dx = None
@@ -1804,7 +1864,7 @@ class ConvAct(Function):
         if ctx.s2d:         # x is the space-to-depth input saved by forward
             sp = cp.s2d()
             if want_w:
-                ws, bws = sp.grad_ws(wino_ok=True)
+                ws, bws = sp.grad_ws(wino_ok=True, launch=dict(x0=x, dout=dy, gmask=y if relu else None))
                 wgrad_side([x, dy, y], x, Taps.get("conv_s2d", 3, 1), dy, ws, cp.Cout, gmask=y if relu else None, dbias=bws)
             dx = None
             if ctx.needs_input_grad[0]:
@@ -1821,7 +1881,8 @@ class ConvAct(Function):
             if want_w:
                 _folded_upsample_wgrad(x, skip, dy, y if relu else None, cp, xpad)
         elif want_w:
-            ws, bws = cp.grad_ws(wino_ok=(stride == 1 and k == 3 and pad == 1 and mode == H.IN_PLAIN))
+            ws, bws = cp.grad_ws(wino_ok=(stride == 1 and k == 3 and pad == 1 and mode == H.IN_PLAIN),
+                                 launch=dict(x0=x, dout=dy, gmask=y if relu else None))
             wgrad_side([x, skip, dy, y], x, Taps.get("conv", k, pad), dy, ws, cp.Cout, stride=stride, x1=skip, in_mode=mode,
                        Hin=Hin, Win=Win, gmask=y if relu else None, dbias=bws)
         dx = dskip = None
@@ -1916,7 +1977,7 @@ class ResConv(Function):
         H.check(H.lib().ramnet_relu_bwd(_p(dy), _p(y), _p(dpre), y.numel(), _st()), "ramnet_relu_bwd")
         want_w = _wants(ctx, 2, 3)
         if want_w:
-            ws, bws = cp.grad_ws(wino_ok=True)
+            ws, bws = cp.grad_ws(wino_ok=True, launch=dict(x0=t, dout=dpre))
             wgrad_side([t, dpre], t, Taps.get("conv", 3, 1), dpre, ws, cp.Cout, dbias=bws)
         dt = None
         if ctx.needs_input_grad[0]:
@@ -2119,7 +2180,7 @@ class GRUCell(Function):
             dhd = torch.empty_like(o)
             H.check(L.ramnet_gru_bwd_a(_p(dhn), _p(ur), _p(o), _p(h), _p(dpo), _p(dpur), _p(dhd), npix, Cc, ld(dhn), _st()), "gru_bwd_a")
         if want_o:
-            ws, bws = cp_o.grad_ws(wino_ok=Cc % 32 == 0)
+            ws, bws = cp_o.grad_ws(wino_ok=Cc % 32 == 0, launch=dict(x0=x, dout=dpo, x1=hr if hr is not None else h, xm=None if hr is not None else ur))
             if hr is not None:
                 _wgrad_cell(cp_o, ws, [x, hr, dpo], x, taps, dpo, Cc, x1=hr, in_mode=H.IN_CAT, C1=Cc, dbias=bws)
             else:
@@ -2134,7 +2195,7 @@ class GRUCell(Function):
                 conv_launch(dpo, tapsd, cp_o.bwd(), dxh, 2 * Cc)
                 H.check(L.ramnet_gru_bwd_b(_p(dxh), _p(ur), _p(h), _p(dpur), _p(dhd), npix, Cc, _st()), "gru_bwd_b")
         if want_ur:
-            ws, bws = cp_ur.grad_ws(wino_ok=Cc % 32 == 0)
+            ws, bws = cp_ur.grad_ws(wino_ok=Cc % 32 == 0, launch=dict(x0=x, dout=dpur, x1=h))
             _wgrad_cell(cp_ur, ws, [x, h, dpur], x, taps, dpur, 2 * Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, dbias=bws)
         if data and half:
             conv_launch(dpur, tapsd, cp_ur.state_half().bwd(), dxh, Cc, out_off=Cc, beta=1.0)
@@ -2320,7 +2381,7 @@ class LSTMCell(Function):
                                                    npix, Hh * W, Cc, _st()), "lstm_bwd_masked")
         want_x, want_h = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if _wants(ctx, 3, 4):       # weight and bias of the gates share the backward-weights launch
-            ws, bws = cp.grad_ws(wino_ok=Cc % 32 == 0)
+            ws, bws = cp.grad_ws(wino_ok=Cc % 32 == 0, launch=dict(x0=x, dout=dpre, x1=h))
             wgrad_side([x, h, dpre], x, Taps.get("conv", 3, 1), dpre, ws, 4 * Cc, x1=h, in_mode=H.IN_CAT, C1=Cc, dbias=bws)
         if want_h and _state_half_ok(want_x, npix, Cc):      # x frozen out: dh alone, from the state half of the weights
             conv_launch(dpre, Taps.get("dgrad1", 3, 1), cp.state_half().bwd(), dxh, Cc, out_off=Cc, beta=0.0 if ctx.active is None else 1.0)

@@ -485,6 +485,19 @@ def test_cabi_argument_errors_and_host_only_entry_points():
     d.C0, d.ld0, d.ldo, d.osy, d.osx = 64, 64, 64, 1, 1
     d.algo = _hip.ALGO_WINOGRAD
     assert L.ramnet_conv_launch(ctypes.byref(d), None) == 10001 and b"px * ld" in L.ramnet_last_error()
+    # the addressing queries are host functions that answer quietly: NULL -> 0, the descriptor refused above -> 0, one image of it -> 1;
+    # a backward-weights launch of the Winograd families over 2 GB -> 0, the direct kernel's over the same tensors -> 1
+    held = L.ramnet_last_error()
+    assert L.ramnet_conv_addressable(None) == 0 and L.ramnet_wgrad_addressable(None) == 0
+    assert L.ramnet_conv_addressable(ctypes.byref(d)) == 0
+    d.B, d.Hin, d.Win = 1, 1024, 1024
+    assert L.ramnet_conv_addressable(ctypes.byref(d)) == 1
+    g = _hip.WgradDesc()
+    g.algo, g.B, g.Hin, g.Win, g.Ho, g.Wo, g.ld0, g.ldg = _hip.ALGO_WINOGRAD_2X4, 2, 2048, 2048, 2048, 2048, 64, 64
+    assert L.ramnet_wgrad_addressable(ctypes.byref(g)) == 0
+    g.algo = _hip.ALGO_DIRECT
+    assert L.ramnet_wgrad_addressable(ctypes.byref(g)) == 1
+    assert L.ramnet_last_error() == held
     assert L.ramnet_voxelize(None, 10, 0, 4, 4, None, None) == 10001
     # packed sizes: [tap][chunk16][Cout_pad32][16]
     assert L.ramnet_packed_weight_elems(64, 32, 5, 5, 0, 1) == 25 * 2 * 64 * 16

@@ -1021,7 +1021,10 @@ static double *si_scratch(hipStream_t st) {
     void *p = nullptr;
     const size_t bytes = (3 * 256 + 1) * sizeof(double);
     if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    if (hipMemset(p, 0, bytes) != hipSuccess) { (void)hipFree(p); return nullptr; }
+    // zeroed ON the stream that will use it: a fill on the null stream is not ordered before a launch on a non-blocking stream (torch's
+    // pool streams are), and the memset calls may return before the fill is done — a ticket that is zeroed after the first workgroups have
+    // drawn theirs never counts to the last one, and loss and stats are never written
+    if (hipMemsetAsync(p, 0, bytes, st) != hipSuccess) { (void)hipFree(p); return nullptr; }
     bufs[{dev, st}] = static_cast<double *>(p);
     return static_cast<double *>(p);
 }

@@ -427,7 +427,10 @@ class TimeBatchedStream:
         return self._close(0) if self.n else None
 
     def _weights_version(self):
-        return sum(p._version for p in self.model.parameters())
+        """What the weight packs follow (ops.ConvParam._versions), per parameter and with the object itself: a sum of versions misses a
+        replaced nn.Parameter and a `p.data = t`.  (Writes THROUGH `.data` move none of the three: ops.invalidate_packs() and a new
+        runner after those — INTEGRATION.md, "Changing weights".)"""
+        return tuple((id(p), p._version, p.data_ptr()) for p in self.model.parameters())
 
     def _close(self, f):
         key = (self.n, f, self.p)

@@ -23,13 +23,20 @@ def _norm_layer(norm, channels, track=True):
 
 
 class _Lazy:
-    """Builds ops.ConvParam on first use (after .to(device))."""
+    """Builds ops.ConvParam on first use (after .to(device)), and again when the layer's nn.Parameter OBJECTS have been replaced
+    (load_state_dict(assign=True), `layer.conv2d.weight = nn.Parameter(...)`): a ConvParam computes with the parameters it was built
+    over and folds into their .grad.  One identity comparison per parameter and layer call; the replaced ConvParam's packs and
+    workspaces go with it, which is safe between passes only."""
 
     def _cp(self, name, weights, biases, gates=1):
+        if ops._Engine.task != -1 and torch._C._current_graph_task_id() == -1:
+            ops._Engine.sweep()          # a forward outside any backward pass: a task still open was aborted
         d = self.__dict__.setdefault("_cps", {})
-        if name not in d:
-            d[name] = ops.ConvParam(weights, biases, gates)
-        return d[name]
+        cp = d.get(name)
+        if cp is None or not cp.holds(weights, biases):
+            assert cp is None or not cp.in_pass(), "a layer's parameters were replaced inside a backward pass"
+            cp = d[name] = ops.ConvParam(weights, biases, gates)
+        return cp
 
 
 class ConvLayer(nn.Module, _Lazy):

@@ -9,7 +9,9 @@ autograd's per-use accumulation, lstm_trainer.py:450).
 import collections
 import contextlib
 import ctypes as C
+import functools
 import os as _os
+import weakref
 
 import torch
 from torch.autograd import Function
@@ -956,21 +958,58 @@ class _Engine:
     """Per-backward-pass bookkeeping: fold weight-gradient workspaces into .grad when the autograd engine finishes the pass.
 
     Keyed on the engine's graph task: the first weight-gradient launch of a backward pass queues ONE end-of-pass callback
-    (flush).  The engine runs callbacks only when the pass completes; a pass that raises mid-way (OOM, a bad argument, a hook)
-    leaves workspaces partly filled, so the next pass — recognised by its new task id — first discards them (reset)."""
-    dirty = []
-    task = -1                # graph task whose callback is queued (-1: none / launches outside autograd, caller flushes)
+    (flush) for that task.  The engine runs callbacks only when the pass completes; a pass that raises mid-way (OOM, a bad argument, a
+    hook) leaves workspaces partly filled, so the next pass first discards them (reset).
+
+    A backward pass may run inside another one (torch.utils.checkpoint(use_reentrant=True) calls backward from a node's backward): the
+    inner graph task gets a dirty list and a callback of its own, folds what it dirtied itself and leaves the enclosing pass's layers to
+    that pass's callback.  An enclosing task is told from an aborted one by its callback: the engine holds the only reference to it and
+    drops it with the graph task, run or not — a task whose callback is gone without having run was aborted."""
+    dirty = []               # the layers of `task`
+    task = -1                # graph task of the launches under way (-1: none / launches outside autograd, caller flushes)
+    callback = None          # weak reference to the callback queued for `task` (None: task -1)
+    outer = []               # (task, dirty, callback) of the tasks that enclose `task`, outermost first
     side_used = None
 
     @classmethod
     def enter(cls):
         tid = torch._C._current_graph_task_id()
         if tid != cls.task:
-            if cls.dirty:            # leftovers of a pass that never reached its callback
-                cls.reset()
-            cls.task = tid
+            cls._open(tid)
+
+    @classmethod
+    def _open(cls, tid):
+        """Make `tid` the task under way: back in an enclosing task, or a new one.  What is left of tasks that never reached their
+        callback is discarded first."""
+        live, found = [], None
+        for ent in cls.outer + [(cls.task, cls.dirty, cls.callback)]:
+            if ent[0] == tid:
+                found = ent
+            elif ent[2] is not None and ent[2]() is not None:
+                live.append(ent)
+            elif ent[1]:             # leftovers of a pass that never reached its callback
+                cls._discard(ent[1])
+        if found is None:
+            found = (tid, [], None)
             if tid != -1:
-                torch.autograd.Variable._execution_engine.queue_callback(cls.flush)
+                cb = functools.partial(cls.flush, tid)
+                torch.autograd.Variable._execution_engine.queue_callback(cb)
+                found = (tid, [], weakref.ref(cb))
+        cls.outer = live
+        cls.task, cls.dirty, cls.callback = found
+
+    @classmethod
+    def _close(cls, tid):
+        """Take task `tid` (None: the one under way) off the books; its dirty list."""
+        if tid is None or tid == cls.task:
+            dirty = cls.dirty
+            cls.task, cls.dirty, cls.callback = cls.outer.pop() if cls.outer else (-1, [], None)
+            return dirty
+        for i, ent in enumerate(cls.outer):
+            if ent[0] == tid:
+                del cls.outer[i]
+                return ent[1]
+        return []
 
     @classmethod
     def mark(cls, cp):
@@ -988,14 +1027,18 @@ class _Engine:
             cls.side_used = None
 
     @classmethod
-    def flush(cls):
-        for cp in cls.dirty:               # queued cell updates go to the backward-weights stream before it is joined
+    def flush(cls, tid=None):
+        """End of graph task `tid` (None: of the task under way): fold what it dirtied."""
+        dirty = cls._close(tid)
+        for cp in dirty:                   # queued cell updates go to the backward-weights stream before it is joined
             cp.flush_deferred()
         cls._join()
-        dirty, cls.dirty, cls.task = cls.dirty, [], -1
         # data-parallel runs: parallel.FlatGradReducer watches the folds and sends a gradient bucket off as soon as its last
         # parameter is final (SURVEY 8e) — not while a hipGraph is being captured (collectives stay outside the training graph)
-        hook = _FINALIZE_HOOK if (_FINALIZE_HOOK is not None and not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())) else None
+        # — and from the outermost task alone: a pass inside a pass folds its layers without telling (they are final, and their buckets
+        # free, by the time the enclosing pass's fold arms the reducer; an inner fold must not use up the reducer's one send per step)
+        hook = _FINALIZE_HOOK if (_FINALIZE_HOOK is not None and cls.task == -1
+                                  and not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())) else None
         if hook is not None:
             hook.begin(dirty)
         global _ZERO_BATCH
@@ -1014,12 +1057,26 @@ class _Engine:
             hook.end()
 
     @classmethod
+    def sweep(cls):
+        """Called where NO backward pass is under way (a layer's forward outside any graph task, submodules._Lazy._cp): whatever task is
+        still open never reached its callback.  The bound on _open's reading of a live callback as an enclosing task — should anything
+        keep an aborted task's callback alive, its layers are discarded here, at the next forward, instead of staying dirty for good."""
+        for ent in cls.outer + [(cls.task, cls.dirty, cls.callback)]:
+            if ent[1]:
+                cls._discard(ent[1])
+        cls.outer = []
+        cls.task, cls.dirty, cls.callback = -1, [], None
+
+    @classmethod
     def reset(cls):
-        """Drop the partial weight-gradient sums of an aborted backward pass (nothing reaches .grad)."""
-        for cp in cls.dirty:
+        """Drop the partial weight-gradient sums of an aborted backward pass (nothing reaches .grad): the task under way."""
+        cls._discard(cls._close(None))
+
+    @classmethod
+    def _discard(cls, dirty):
+        for cp in dirty:
             cp._defer = []
         cls._join()
-        dirty, cls.dirty, cls.task = cls.dirty, [], -1
         for cp in dirty:
             cp.discard()
 
@@ -1035,6 +1092,57 @@ def set_finalize_hook(hook):
 
 def get_finalize_hook():
     return _FINALIZE_HOOK
+
+
+class _PassSum:
+    """The sum over ONE backward pass of a gradient whose launches add into their operand — the prediction layer's weight and bias, the
+    transposed convolution's bias; they have no ConvParam workspace —: zero at pass start, added to .grad once when the engine finishes
+    the pass, as the layers' workspaces are.  Adding every launch straight into .grad gives the same bits only where .grad starts the
+    pass at zero: ((G + g1) + g2) is not G + (g1 + g2), so a second pass without zero_grad would not have doubled the gradient.
+    Kept in a table of this module by id(p) — nothing is hung on the nn.Parameter, whose attributes are pickled with it (torch.save of a
+    module) —, dropped when the parameter dies; the engine treats it as a layer (mark / finalize / discard)."""
+    biases = ()
+    table = {}               # id(parameter) -> its _PassSum
+
+    def __init__(self, p):
+        key = id(p)
+        self.p, self.t, self._dirty, self._defer = weakref.ref(p, lambda _: _PassSum.table.pop(key, None)), None, False, []
+
+    @classmethod
+    def get(cls, p):
+        """The _PassSum of p, None if no pass has asked for one."""
+        s = cls.table.get(id(p))
+        return s if s is not None and s.p() is p else None
+
+    @property
+    def weights(self):          # (what a finalize hook asks a layer for)
+        p = self.p()
+        return [] if p is None else [p]
+
+    @classmethod
+    def of(cls, p):
+        """The zero-at-pass-start buffer that this pass's launches add the gradient of p into."""
+        s = cls.get(p)
+        if s is None:
+            s = cls.table[id(p)] = cls(p)
+        if s.t is None or s.t.device != p.device or s.t.shape != p.shape:
+            s.t = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        _Engine.mark(s)
+        return s.t
+
+    def flush_deferred(self):
+        pass
+
+    def finalize(self):
+        p = self.p()
+        if p is not None and p.requires_grad:
+            ensure_grad(p).add_(self.t)
+        _zero_later(self.t)
+        self._dirty = False
+
+    def discard(self):
+        self.t.zero_()
+        self._dirty = False
 
 
 def ensure_grad(p):
@@ -1176,6 +1284,20 @@ class ConvParam:
         self._part = {}                  # deterministic mode: partial buffers of the ordered joins, by name
         self._dirty = False
         self._defer = []                 # queued backward-weights launches of a recurrent cell (_wgrad_cell)
+
+    def holds(self, weights, biases):
+        """Are these the very nn.Parameter objects this ConvParam was built over?  (submodules._Lazy: a replaced parameter gets a new one)"""
+        for mine, theirs in ((self.weights, weights), (self.biases, biases)):
+            if len(mine) != len(theirs):
+                return False
+            for a, b in zip(mine, theirs):
+                if a is not b:
+                    return False
+        return True
+
+    def in_pass(self):
+        """Does a backward pass under way hold partial sums or queued launches of this layer (its space-to-depth view included)?"""
+        return bool(self._dirty or self._defer or (self._s2d is not None and self._s2d._dirty))
 
     def flush_deferred(self):
         """Launch the queued cell updates as ONE multi-segment backward-weights launch (ramnet_wgrad_desc.segs)."""
@@ -1941,13 +2063,13 @@ class TConvAct(Function):
             ws, _ = cp.grad_ws()
             wgrad_launch(dy, taps, x, ws, Cx, stride=2, xm=mask, in_mode=mode)
         if cp.biases[0] is not None and ctx.needs_input_grad[2]:
-            dyc = dy.contiguous()
+            dyc, db = dy.contiguous(), _PassSum.of(cp.biases[0])
             if _DETERMINISTIC:          # the workgroups' partial rows joined in workgroup order
                 part = cp.det_partial("bias", H.lib().ramnet_bias_grad_partial_floats(cp.Cin))
-                H.check(H.lib().ramnet_bias_grad_ordered(_p(dyc), _p(mask), _p(ensure_grad(cp.biases[0])), B * 4 * Hh * W, cp.Cin, _p(part), _st()),
+                H.check(H.lib().ramnet_bias_grad_ordered(_p(dyc), _p(mask), _p(db), B * 4 * Hh * W, cp.Cin, _p(part), _st()),
                         "bias_grad_ordered")
             else:
-                H.check(H.lib().ramnet_bias_grad(_p(dyc), _p(mask), _p(ensure_grad(cp.biases[0])), B * 4 * Hh * W, cp.Cin, _st()), "bias_grad")
+                H.check(H.lib().ramnet_bias_grad(_p(dyc), _p(mask), _p(db), B * 4 * Hh * W, cp.Cin, _st()), "bias_grad")
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty(B, Hh, W, Cx, device=ctx.xmeta.device)
@@ -2391,10 +2513,10 @@ class LSTMCell(Function):
 
 
 def _pred_grads(ctx, w, b):
-    """(dw, db) operands of a prediction-layer backward launch that forms weight and bias sums together: the .grad of a trainable tensor,
-    a throw-away buffer for a frozen one beside it (b may be None: the layer has no bias)."""
-    dw = ensure_grad(w) if ctx.needs_input_grad[1] else torch.zeros_like(w)
-    db = None if b is None else (ensure_grad(b) if ctx.needs_input_grad[2] else torch.zeros_like(b))
+    """(dw, db) operands of a prediction-layer backward launch that forms weight and bias sums together: the pass's sum of a trainable tensor
+    (_PassSum: added to its .grad when the engine finishes the pass), a throw-away buffer for a frozen one beside it (b may be None: the layer has no bias)."""
+    dw = _PassSum.of(w) if ctx.needs_input_grad[1] else torch.zeros_like(w)
+    db = None if b is None else (_PassSum.of(b) if ctx.needs_input_grad[2] else torch.zeros_like(b))
     return dw, db
 
 

@@ -197,9 +197,9 @@ class FlatGradReducer:
         self._ready()
 
     def end(self):
-        """End of the fold: everything enqueued on the stream afterwards (a second backward pass writing .grad directly — the
-        prediction layer's backward does —, the optimizer) is ordered behind the early collectives.  The overlap that matters, bucket
-        k's collective under the folds of the later layers, has happened by now."""
+        """End of the fold: everything enqueued on the stream afterwards (a second backward pass folding into .grad, the optimizer) is
+        ordered behind the early collectives.  The overlap that matters, bucket k's collective under the folds of the later layers,
+        has happened by now."""
         if self._issued:
             torch.cuda.current_stream().wait_stream(self.side)
 

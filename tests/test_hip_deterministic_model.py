@@ -10,81 +10,15 @@ NaN targets.  The NaN pixels are drawn outside a 24 x 24 corner of every target 
 NaN spread over the whole map no 8 x 8 cell of the coarsest scale of the gradient loss is valid at this size and the loss VALUE is NaN in
 either mode (the gradients stay finite), which would leave nothing to compare.  Every test sets the mode inside try / finally and restores
 it, and the schedule switches to what they were."""
-import sys
-
 import numpy as np
 import pytest
 import torch
 
-from util import GOLDEN, assert_close, build_hip_model
+from history_cases import B, H, K, L, LC, W, WIRINGS, _backward, _cfg, _same, _seq, _targets_with_nan, bench_schedule  # noqa: F401
+from util import assert_close, build_hip_model
 
-sys.path.insert(0, GOLDEN)
-from recipe import make_item  # noqa: E402
-
+# (the models, data and helpers of this file are shared with tests/test_hip_history.py: they live in tests/history_cases.py)
 pytestmark = pytest.mark.gpu
-B, L, K, H, W = 2, 2, 2, 32, 48
-LC = ["image", "events1"]
-
-
-def _cfg(**over):
-    cfg = dict(num_bins_rgb=1, num_bins_events=5, skip_type="sum", recurrent_block_type="conv", state_combination="convgru", num_encoders=3,
-               base_num_channels=32, num_residual_blocks=2, use_upsample_conv=True, norm="none", gpu=0, every_x_rgb_frame=K, baseline=False,
-               loss_composition=LC)
-    cfg.update(over)
-    return cfg
-
-
-def _same(a, b):
-    """finite, and the same bits"""
-    return a.shape == b.shape and bool(torch.isfinite(a).all()) and torch.equal(a, b) and \
-        torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
-
-
-def _targets_with_nan(rng, it, frac=0.2, keep=24):
-    """NaN in `frac` of every depth map, none of it in the [keep x keep] corner (3 x 3 cells of the coarsest gradient-loss scale)"""
-    for k in [k for k in it if k.startswith("depth_")]:
-        d = it[k].clone()
-        m = torch.from_numpy(rng.random(tuple(d.shape)) < frac / (1.0 - keep * keep / float(H * W)))
-        m[..., :keep, :keep] = False
-        d[m] = float("nan")
-        it[k] = d
-    return it
-
-
-def bench_schedule(det):
-    from rpg_ramnet_amd import ops
-    return ops.switches(wgrad_overlap=True, decoder_overlap=True, wgrad_defer=2, deterministic=det)
-
-
-def _seq(model, seed, irregular=False):
-    rng = np.random.default_rng(seed)
-    seq = []
-    for _ in range(L):
-        it = _targets_with_nan(rng, make_item(rng, B, H, W, K, 5, 1, True, 0.0))
-        if irregular:
-            item = {k: v for k, v in it.items() if not k.startswith("depth_")}
-            item["num_events"] = torch.tensor([2, 1], dtype=torch.int64)
-            item["depth_events_last"], item["depth_image_last"] = it["depth_events0"], it["depth_image"]
-            it = item
-        seq.append({k: (v if k == "num_events" else v.to(model.gpu)) for k, v in it.items()})       # (the counts are host data)
-    return seq
-
-
-def _backward(model, seq, lc, unet=False):
-    from rpg_ramnet_amd import ops
-    from rpg_ramnet_amd.trainer import sequence_loss
-    model.zero_grad()
-    if unet:        # the feed-forward wiring has no packages: the image branch of every item, SI loss (its stand-alone operator) on the image
-        total = sum(ops.scale_invariant_loss(model(it, None, None)[0]["image"], it["depth_image"]) for it in seq)
-    else:
-        total, _ = sequence_loss(model, seq, lc, [1, 1], grad_loss_weight=0.25)
-    total.backward()
-    torch.cuda.synchronize()
-    return total.detach().clone(), {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None}
-
-
-WIRINGS = {"convgru": ("ERGB2DepthRecurrent", {}, False), "convlstm": ("ERGB2DepthRecurrent", dict(state_combination="convlstm"), False),
-           "ergb2depth_tconv": ("ERGB2Depth", dict(use_upsample_conv=False), False), "irregular": ("ERGB2DepthRecurrent", {}, True)}
 
 
 @pytest.mark.parametrize("wiring", sorted(WIRINGS))

@@ -1114,11 +1114,25 @@ static int launch_voxel_bands(const double *events, const long long *offsets, lo
     return 0;
 }
 
+// Zero-fill of the grids ahead of the global-atomic form.  While `st` is capturing it is a kernel, not hipMemsetAsync: a kernel node owns a
+// copy of its arguments, so every replay of the graph zeroes the grids whatever was enqueued between the replays (the memset node did not:
+// tests/test_hip_streams.py, row voxel_sorted-capture).  Outside a capture nothing changes.
+__global__ void voxel_zero_kernel(unsigned *__restrict__ p, size_t n) {
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = 0u;
+}
+
+static hipError_t voxel_zero_fill(float *grids, size_t cells, hipStream_t st) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) return hipMemsetAsync(grids, 0, cells * sizeof(float), st);
+    hipLaunchKernelGGL(voxel_zero_kernel, dim3(grid_for(cells)), dim3(256), 0, st, reinterpret_cast<unsigned *>(grids), cells);
+    return hipGetLastError();
+}
+
 extern "C" int ramnet_voxelize(const double *events, size_t n_events, int bins, int W, int H, float *grid, void *stream) {
     RAMNET_CHECK_ARG(grid && bins > 0 && W > 0 && H > 0);
     hipStream_t st = (hipStream_t)stream;
     RAMNET_CHECK_ARG(events != nullptr || n_events == 0);       // (refused before anything is enqueued)
-    RAMNET_HIP(hipMemsetAsync(grid, 0, (size_t)bins * W * H * sizeof(float), st));
+    RAMNET_HIP(voxel_zero_fill(grid, (size_t)bins * W * H, st));
     note_kernel("zero_fill");
     if (n_events == 0) return 0;
     hipLaunchKernelGGL(voxelize_kernel, dim3(grid_for(n_events)), dim3(256), 0, st, events, n_events, bins, W, H, grid);
@@ -1138,7 +1152,7 @@ extern "C" int ramnet_voxelize_batch(const double *events, const long long *offs
         if (rc >= 0) return rc;
     }
     RAMNET_CHECK_ARG(events != nullptr || max_events == 0);     // (refused before anything is enqueued)
-    RAMNET_HIP(hipMemsetAsync(grids, 0, (size_t)n_grids * bins * W * H * sizeof(float), st));
+    RAMNET_HIP(voxel_zero_fill(grids, (size_t)n_grids * bins * W * H, st));
     note_kernel("zero_fill");
     if (max_events == 0) return 0;
     int gx = (int)((max_events + 255) / 256);
@@ -1157,7 +1171,7 @@ extern "C" int ramnet_voxelize_batch_sorted(const double *events, const long lon
     RAMNET_CHECK_ARG(grids && offsets && n_grids > 0 && n_grids <= 65535 && bins > 0 && W > 0 && H > 0);
     hipStream_t st = (hipStream_t)stream;
     if (max_events == 0) {
-        RAMNET_HIP(hipMemsetAsync(grids, 0, (size_t)n_grids * bins * W * H * sizeof(float), st));
+        RAMNET_HIP(voxel_zero_fill(grids, (size_t)n_grids * bins * W * H, st));
         note_kernel("zero_fill");
         return 0;
     }

@@ -67,7 +67,7 @@ _ROW = 10
 TICKET_BYTES = 262144   # RAMNET_BATCH_METRICS_TICKET_BYTES: the part of a workspace that has to be zero when it is allocated
 
 _workspaces = {}        # (device index, raw stream) -> uint8 workspace of ramnet_batch_metrics (tickets zeroed once, at allocation)
-_tables = {}            # (device index, pointers of the pairs) -> int64 [2][G] device table
+_tables = {}            # (device index, raw stream, pointers of the pairs) -> int64 [2][G] device table
 
 
 def resolve_metrics(names):
@@ -100,7 +100,8 @@ def _workspace(device, nbytes):
 
 
 def _pointer_table(device, ps, ts):
-    key = (device.index,) + tuple(ps) + tuple(ts)
+    # (the stream is part of the key: the upload is ordered before its readers on the stream it was enqueued on and on no other)
+    key = (device.index, _st().value or 0) + tuple(ps) + tuple(ts)
     tab = _tables.get(key)
     if tab is None:
         if len(_tables) >= 256:

@@ -2818,7 +2818,7 @@ def multi_scale_grad_loss(prediction, target, num_scales=4):
 
 
 # ---- the gradient loss of a whole sequence as one batched operation (csrc/grad_loss.hip)
-_msg_tables = {}        # (device index, pointers of the pairs) -> int64 [2][G] device table
+_msg_tables = {}        # (device index, raw stream, pointers of the pairs) -> int64 [2][G] device table
 _msg_workspaces = {}    # (device index, raw stream) -> float64 workspace of ramnet_grad_loss_stats (per-workgroup slots)
 
 
@@ -2845,9 +2845,10 @@ def _msg_pairs(preds, targets, what):
 def _msg_table(device, ps, ts):
     """Device table [2][G] of the pairs' pointers, cached by the pointers themselves (a training step meets the same addresses again).
     Filled by kernel argument: nothing on the host has to outlive the call, so a stream capture records the fill; a capture never
-    takes a table from the cache (the graph must own, and refill, what it reads)."""
+    takes a table from the cache (the graph must own, and refill, what it reads).  The stream is part of the key: the fill is ordered
+    before its readers on the stream it was enqueued on and on no other, and the table's memory belongs to that stream's pool."""
     capturing = torch.cuda.is_current_stream_capturing()
-    key = (device.index,) + tuple(ps) + tuple(ts)
+    key = (device.index, _st().value or 0) + tuple(ps) + tuple(ts)
     tab = None if capturing else _msg_tables.get(key)
     if tab is None:
         tab = torch.empty((2, len(ps)), device=device, dtype=torch.int64)

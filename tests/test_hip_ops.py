@@ -942,39 +942,31 @@ def test_pack_input_is_the_padded_channels_last_copy(B, C, H, W):
     assert y.shape == ref.shape and torch.equal(y, ref)
 
 
-@pytest.mark.parametrize("B,H,W,C,n", [(4, 64, 96, 32, 2), (2, 33, 47, 32, 1), (6, 16, 24, 64, 3)])
-def test_pred_sigmoid_si_matches_torch_and_is_bit_reproducible(B, H, W, C, n):
-    """ops.PredSigmoidSI (prediction layer + scale-invariant loss of its n batch segments in the layer's own launches, statenet.py:313 +
-    model/loss.py:6-9) against plain torch in float64 — losses, dx, dw, db — and, ABI 24: the weight / bias gradients are joined in a fixed
-    order through the forward's scratch, so two backward passes give the same bits (the bias gradient is a cancelling sum: with fp32 atomics
-    its last digits followed the arrival order of the workgroups)."""
-    from rpg_ramnet_amd import ops
-    torch.manual_seed(B + C)
+def pred_si_operands(B, H, W, C, n, seed=None):
+    """(x0, w0, b0, targets, dense upstream gradient, loss coefficients) of ops.PredSigmoidSI on the device"""
+    torch.manual_seed(B + C if seed is None else seed)
     x0 = torch.randn(B, H, W, C, device=dev())
     w0 = (torch.randn(1, C, 1, 1, device=dev()) * 0.2)
     b0 = torch.randn(1, device=dev()) * 0.1
     tg = [torch.rand(B // n, 1, H, W, device=dev()) for _ in range(n)]
     tg[0][0, 0, :3, :5] = float("nan")
     dyv = torch.randn(B, 1, H, W, device=dev()) * 1e-3
-    coef = [0.7 + 0.3 * i for i in range(n)]
+    return x0, w0, b0, tg, dyv, [0.7 + 0.3 * i for i in range(n)]
 
-    def run():
-        x, w, b = x0.clone().requires_grad_(True), w0.clone().requires_grad_(True), b0.clone().requires_grad_(True)
-        out = ops.PredSigmoidSI.apply(x, w, b, 1.0, 0.85, False, *tg)
-        total = sum(c * l for c, l in zip(coef, out[1:])) + (out[0] * dyv).sum()
-        total.backward()
-        torch.cuda.synchronize()
-        return [o.detach().clone() for o in out], x.grad.clone(), w.grad.clone(), b.grad.clone()
 
-    o1, dx1, dw1, db1 = run()
-    o2, dx2, dw2, db2 = run()
-    assert torch.equal(dw1, dw2) and torch.equal(db1, db2) and torch.equal(dx1, dx2) and all(torch.equal(a, c) for a, c in zip(o1, o2))
-    # mask_x: dx leaves with the ReLU mask of x itself applied (x = the last decoder's output on the path); everything else unchanged
-    xm, wm, bm = x0.clone().requires_grad_(True), w0.clone().requires_grad_(True), b0.clone().requires_grad_(True)
-    outm = ops.PredSigmoidSI.apply(xm, wm, bm, 1.0, 0.85, True, *tg)
-    (sum(c * l for c, l in zip(coef, outm[1:])) + (outm[0] * dyv).sum()).backward()
-    assert torch.equal(xm.grad, torch.where(x0 > 0, dx1, torch.zeros((), device=dev()))) and torch.equal(wm.grad, dw1) and torch.equal(bm.grad, db1)
-    # float64 torch
+def pred_si_run(x0, w0, b0, tg, dyv, coef, mask_x=False):
+    """forward and backward on the current stream, nothing synchronised -> (outputs, dx, dw, db)"""
+    from rpg_ramnet_amd import ops
+    x, w, b = x0.clone().requires_grad_(True), w0.clone().requires_grad_(True), b0.clone().requires_grad_(True)
+    out = ops.PredSigmoidSI.apply(x, w, b, 1.0, 0.85, mask_x, *tg)
+    total = sum(c * l for c, l in zip(coef, out[1:])) + (out[0] * dyv).sum()
+    total.backward()
+    return [o.detach() for o in out], x.grad, w.grad, b.grad
+
+
+def pred_si_check(o1, dx1, dw1, db1, x0, w0, b0, tg, dyv, coef):
+    """against plain torch in float64: prediction, losses, dx, dw, db"""
+    n, B, C = len(tg), x0.shape[0], x0.shape[3]
     x, w, b = x0.double().requires_grad_(True), w0.double().requires_grad_(True), b0.double().requires_grad_(True)
     y = torch.sigmoid((x * w.view(1, 1, 1, C)).sum(-1, keepdim=True) + b).permute(0, 3, 1, 2)
     losses = []
@@ -989,6 +981,25 @@ def test_pred_sigmoid_si_matches_torch_and_is_bit_reproducible(B, H, W, C, n):
     assert_close(dx1.cpu().numpy(), x.grad.cpu().numpy(), 2e-4, "dx")
     assert_close(dw1.cpu().numpy().reshape(-1), w.grad.cpu().numpy().reshape(-1), 2e-4, "dw")
     assert abs(float(db1) - float(b.grad)) <= 2e-4 * float(x.grad.abs().sum() / C), "db (against the size of its terms)"
+
+
+@pytest.mark.parametrize("B,H,W,C,n", [(4, 64, 96, 32, 2), (2, 33, 47, 32, 1), (6, 16, 24, 64, 3)])
+def test_pred_sigmoid_si_matches_torch_and_is_bit_reproducible(B, H, W, C, n):
+    """ops.PredSigmoidSI (prediction layer + scale-invariant loss of its n batch segments in the layer's own launches, statenet.py:313 +
+    model/loss.py:6-9) against plain torch in float64 — losses, dx, dw, db — and, ABI 24: the weight / bias gradients are joined in a fixed
+    order through the forward's scratch, so two backward passes give the same bits (the bias gradient is a cancelling sum: with fp32 atomics
+    its last digits followed the arrival order of the workgroups)."""
+    args = pred_si_operands(B, H, W, C, n)
+    x0 = args[0]
+    o1, dx1, dw1, db1 = pred_si_run(*args)
+    torch.cuda.synchronize()
+    o2, dx2, dw2, db2 = pred_si_run(*args)
+    torch.cuda.synchronize()
+    assert torch.equal(dw1, dw2) and torch.equal(db1, db2) and torch.equal(dx1, dx2) and all(torch.equal(a, c) for a, c in zip(o1, o2))
+    # mask_x: dx leaves with the ReLU mask of x itself applied (x = the last decoder's output on the path); everything else unchanged
+    _, dxm, dwm, dbm = pred_si_run(*args, mask_x=True)
+    assert torch.equal(dxm, torch.where(x0 > 0, dx1, torch.zeros((), device=dev()))) and torch.equal(dwm, dw1) and torch.equal(dbm, db1)
+    pred_si_check(o1, dx1, dw1, db1, *args)
 
 
 @pytest.mark.parametrize("B,H,W,C", [(2, 8, 16, 64), (1, 7, 13, 32), (2, 4, 43, 256)])

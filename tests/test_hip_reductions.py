@@ -265,6 +265,21 @@ def _mse_data(B, H, W, kind, share, seed):
     return p, t
 
 
+def mse_check(got, loss, p, t, half, kind, what):
+    """test_mse_forward's rule (tests/stream_worker.py holds the launch to it on other streams): got = (sum d^2, count, ...) as the device left them"""
+    ref = rr.mse_stats(p, t, bool(half))
+    assert_count(got[1], ref[1], what + " count")
+    ncell = p.numel() // (4 if half else 1)
+    if kind == "int":
+        assert_exact(got[:1], ref[:1], what + " sum d^2")
+    else:
+        assert_within(got[:1], ref[:1], (ncell + 2) * E64 * ref[:1], what + " sum d^2")
+    if float(ref[1]) == 0:
+        assert bool(torch.isnan(loss).all()) and float(got[0]) == 0.0
+    else:
+        assert_within(loss.view(-1), rr.mse_loss(ref).view(-1), ((ncell + 4) * E64 + U) * rr.mse_loss(ref).view(-1), what + " loss")
+
+
 @pytest.mark.parametrize("half", [0, 1])
 @pytest.mark.parametrize("B,H,W", MSE_SHAPES)
 def test_mse_forward(B, H, W, half):
@@ -275,17 +290,7 @@ def test_mse_forward(B, H, W, half):
             p, t = _mse_data(B, H, W, kind, share, 140)
             stats, loss = Out(1, 4, dtype=F64), Out(1, 1)
             call("ramnet_mse_loss_fwd", In(p.view(-1)), In(t.view(-1)), B, H, W, half, stats, loss)
-            ref, got, what = rr.mse_stats(p, t, bool(half)), stats.value().view(-1), "mse_fwd[%s, %s]" % (share, kind)
-            assert_count(got[1], ref[1], what + " count")
-            ncell = p.numel() // (4 if half else 1)
-            if kind == "int":
-                assert_exact(got[:1], ref[:1], what + " sum d^2")
-            else:
-                assert_within(got[:1], ref[:1], (ncell + 2) * E64 * ref[:1], what + " sum d^2")
-            if float(ref[1]) == 0:
-                assert bool(torch.isnan(loss.value()).all()) and float(got[0]) == 0.0
-            else:
-                assert_within(loss.value().view(-1), rr.mse_loss(ref).view(-1), ((ncell + 4) * E64 + U) * rr.mse_loss(ref).view(-1), what + " loss")
+            mse_check(stats.value().view(-1), loss.value(), p, t, half, kind, "mse_fwd[%s, %s]" % (share, kind))
 
 
 @pytest.mark.parametrize("with_gscale", [False, True])

@@ -203,6 +203,11 @@ def test_render_inputs_thresholds_bit_for_bit():
 
 
 # ------------------------------------------------------------------------------------------------ scale
+def scale_bound(n):
+    """relative bound of a least-squares scale of n pixels against the float64 sums of the same float32 products"""
+    return n * 2.0 ** -52
+
+
 def scale_pairs(shape, G, seed):
     rng = np.random.default_rng(seed)
     return [(np.clip(rng.random(shape) + 0.05 * rng.standard_normal(shape), 0, 1).astype(np.float32), rng.random(shape).astype(np.float32))
@@ -226,8 +231,8 @@ def test_least_squares_scale(shape):
         pm, tm = M.metric_depth(ps[g], CLIP, REG).cpu().numpy(), M.metric_depth(ts[g], CLIP, REG).cpu().numpy()
         want = RR.scale_float64(pm, tm)
         rel = abs(got[g] - want) / abs(want)
-        print("%s pair %d: against the float64 sums %.3e (bound %.3e)" % (shape, g, rel, n * 2.0 ** -52))
-        assert rel <= n * 2.0 ** -52, (g, rel)
+        print("%s pair %d: against the float64 sums %.3e (bound %.3e)" % (shape, g, rel, scale_bound(n)))
+        assert rel <= scale_bound(n), (g, rel)
         if shape == (37, 53):
             ref = float(RR.scale_numpy(pairs[g][0], pairs[g][1], CLIP, REG))
             rel32 = abs(got[g] - ref) / abs(ref)

@@ -264,6 +264,28 @@ int ramnet_nchw_to_nhwc_pad(const float *src, float *dst, int B, int C, int H, i
  * zero-padded to Cpad (the repack of ramnet_nchw_to_nhwc_pad fused in); nhwc = 0: NCHW (Cpad ignored).                        */
 int ramnet_reflect_pad(const float *src, float *dst, int B, int C, int H, int W, int Cpad, int top, int left, int Hc, int Wc, int nhwc,
                        void *stream);
+/* ---- gradients of the model inputs (additions to ABI 27) ---------------------------------------- */
+/* Backward of ramnet_nchw_to_nhwc_pad: the first C of the Cpad lanes of src [B][H][W][Cpad] become dst [B][C][H][W], a copy bit for
+ * bit (no alignment beyond 4 bytes is asked of either pointer).                                                                    */
+int ramnet_nhwc_unpad_to_nchw(const float *src, float *dst, int B, int C, int H, int W, int Cpad, void *stream);
+/* Backward of ramnet_reflect_pad for both of its layouts (same arguments and preconditions; g = the gradient of the padded tensor,
+ * dx = [B][C][H][W]).  A gather: frame pixel (sy, sx) sums the gradients of the padded positions that mirror onto it — per axis at
+ * most three: top - sy (when 1 <= sy <= top), top + sy, top + 2 (H - 1) - sy (when sy <= H - 2 and the position is inside Hc), columns
+ * alike with left / W / Wc — nine in all, in ONE order: padded rows ascending, inside a row padded columns ascending, every term added
+ * in fp32 to a sum that starts at +0.  The same bits on every launch.                                                              */
+int ramnet_reflect_pad_bwd(const float *g, float *dx, int B, int C, int H, int W, int Cpad, int top, int left, int Hc, int Wc, int nhwc,
+                           void *stream);
+/* Backward-data of the 5x5, stride-1, pad-2 head layer (RAMNET_ALGO_HEAD; statenet.py:160-175):
+ *   dx[b,y,x,c] = sum_{n,ky,kx} w[n,c,ky,kx] * m(b,y+2-ky,x+2-kx,n) * dy[b,y+2-ky,x+2-kx,n],   zero outside the image,
+ * dy = [B][H][W] at pitch ldg (Cout <= 32 feature maps), y = the ReLU mask operand at pitch ldgm (m = 1 where y > 0, else 0) or NULL
+ * (m = 1), w = the layer's OIHW weights [Cout][Cin][5][5] as they are (no pack), dx = [B][H][W] at pitch ld, whose lanes Cin..ld-1 are
+ * written as zero.  Preconditions (else RAMNET_E_BADARG and nothing is launched): ramnet_head_supported(Cin, Cout); ld == Cin rounded
+ * up to 4; ldg (and ldgm with y) a multiple of 4 and >= Cout rounded up to 4 — lanes between Cout and the pitch are not read as
+ * values; dy and y 16-byte aligned; B, H, W >= 1 and ceil(W/32) * ceil(H/16) * B < 2^31 (one workgroup per 16 x 32 pixel tile;
+ * pixel indices are 64-bit).  Exact fp32 on v_mfma_f32_16x16x4_f32; a gather with no atomics, no workspace and no state: the same
+ * bits on every launch, on the caller's stream.                                                                                    */
+int ramnet_head_dgrad(const float *dy, int ldg, const float *y, int ldgm, const float *w, float *dx, int ld, int B, int H, int W, int Cin,
+                      int Cout, void *stream);
 /* Slabs the Winograd backward-weights launches of a Cin -> Cout layer use at most (ramnet_wgrad_desc.dw_slabs), and the ordered fold
  * slab 0 += slab 1 + ... + slab S-1 (n floats each, n % 4 == 0; slabs 1.. are zeroed) at the end of a backward pass.            */
 int ramnet_wgrad_wino_slabs(int Cin, int Cout);

@@ -222,6 +222,10 @@ _SIGS = {
     "ramnet_nonzero_stats_batch_ordered": (C.c_int, [_fp, C.c_int, C.c_size_t, _fp, _fp, _fp]),
     "ramnet_normalize_nonzero_batch_ordered": (C.c_int, [_fp, C.c_int, C.c_size_t, _fp, _fp, _fp]),
     "ramnet_normalize_nonzero_ordered": (C.c_int, [_fp, C.c_size_t, _fp, _fp, _fp]),
+    # ---- gradients of the model inputs (additions to ABI 27): backward of the two input repacks, backward-data of the head layer
+    "ramnet_nhwc_unpad_to_nchw": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    "ramnet_reflect_pad_bwd": (C.c_int, [_fp, _fp] + [C.c_int] * 10 + [_fp]),
+    "ramnet_head_dgrad": (C.c_int, [_fp, C.c_int, _fp, C.c_int, _fp, _fp] + [C.c_int] * 6 + [_fp]),
 }
 EXPORTS = tuple(_SIGS)
 

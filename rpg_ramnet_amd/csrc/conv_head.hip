@@ -1,5 +1,6 @@
 // The two head layers of the RAM-Net path (5x5, stride 1, 5 event bins / 1 frame channel -> 32 feature maps at full
-// resolution; statenet.py:160-175, submodules.py:8-35) for gfx950 (MI355X), forward and backward-weights.
+// resolution; statenet.py:160-175, submodules.py:8-35) for gfx950 (MI355X), forward, backward-weights and backward-data (the
+// gradient of the model's event grids and frames: conv_head_dgrad_kernel below).
 //
 // With 1-8 input channels the generic implicit-GEMM kernel has nothing to amortise its patch staging and operand traffic
 // over (one 8-channel chunk, N = 32): it runs at ~16 % of the fp32 MFMA peak.  Here the reduction index is the dense
@@ -191,6 +192,102 @@ int launch_head_wgrad(const ramnet_wgrad_desc &d, hipStream_t st) {
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- backward-data
+// dx[b,y,x,c] = sum_{n,ky,kx} w[n,c,ky,kx] * m(b,y+2-ky,x+2-kx,n) * dy[b,y+2-ky,x+2-kx,n]: the forward kernel with the operand roles
+// swapped.  The reduction index is the dense (tap, feature map) pair, K = 25*32 = 800 in 200 steps of v_mfma_f32_16x16x4_f32; M = 16
+// consecutive pixels of a row, N = the input channel padded to 16 (the 32-wide form would pad 1-10 channels to 32).  The lane's column
+// of the weight matrix lives in REGISTERS (lane = (channel, k), 200 VGPRs, read straight from the OIHW tensor: no pack); the A operand
+// is one 4-byte LDS read per MFMA from a feature-map-planar patch of the masked gradient (lanes = consecutive pixels of 4 planes; the
+// plane stride 720 = 16 mod 64 puts the four planes of a read on different banks), addressed as lane base + a compile-time (tap, map)
+// constant.  A workgroup owns HD_H x HT_W = 16 x 32 pixels (a wave 4 rows x 2 halves = 8 accumulators) and stages its (16+4) x (32+4)
+// patch in two passes of 16 feature maps (46 KB of LDS).  A gather: no atomics, no zero-fill, the same bits on every launch.
+constexpr int HD_H = 16;                            // tile height of the backward-data kernel (tile = HD_H x HT_W)
+constexpr int HD_NC = 16;                           // feature maps staged per pass
+constexpr int HD_PLANE = (HD_H + 4) * HP_W;         // one feature-map plane of the gradient patch
+
+struct HeadDgradParams {
+    const float *g, *gm, *w;
+    float *dx;
+    int ldg, ldgm, ld, B, H, W, Cin, Cout, tiles_x, tiles_y;
+};
+
+__global__ void __launch_bounds__(256) conv_head_dgrad_kernel(const HeadDgradParams p) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    __shared__ float P[HD_NC * HD_PLANE];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 15, k = lane >> 4;         // B operand: (k, channel c); A operand: (pixel c, k); D: (pixel 4k + r, channel c)
+    int bid = blockIdx.x;
+    const int tx = bid % p.tiles_x;
+    bid /= p.tiles_x;
+    const int ty = bid % p.tiles_y, b = bid / p.tiles_y;
+    const int oy0 = ty * HD_H, ox0 = tx * HT_W;
+
+    // the lane's column of the weight matrix: step s = tap*8 + j holds feature map n = 4j + k
+    float wreg[200];
+#pragma unroll
+    for (int s = 0; s < 200; ++s) {
+        const int n = 4 * (s & 7) + k;
+        wreg[s] = (n < p.Cout && c < p.Cin) ? p.w[((size_t)n * p.Cin + c) * 25 + (s >> 3)] : 0.f;
+    }
+
+    f32x4 acc[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const float *pa = P + k * HD_PLANE + (wave * 4) * HP_W + c;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        if (half * HD_NC >= p.Cout) break;          // (uniform: nothing but zeros in the second 16 feature maps)
+        if (half) __syncthreads();
+        // stage feature maps [16 half, 16 half + 16) of the masked gradient patch as planes; zero outside the image and beyond Cout
+        for (int i = tid; i < (HD_H + 4) * HP_W * 4; i += 256) {
+            const int quad = i & 3, pix = i >> 2;
+            const int py = pix / HP_W, px = pix - py * HP_W;
+            const int iy = oy0 - 2 + py, ix = ox0 - 2 + px, n0 = half * HD_NC + quad * 4;
+            float4 v = f4zero();
+            if ((unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W && n0 < p.Cout) {
+                const size_t gp = ((size_t)b * p.H + iy) * p.W + ix;
+                v = ld4(p.g + gp * p.ldg + n0);
+                if (p.gm) {
+                    const float4 m = ld4(p.gm + gp * p.ldgm + n0);
+                    v = make_float4(m.x > 0.f ? v.x : 0.f, m.y > 0.f ? v.y : 0.f, m.z > 0.f ? v.z : 0.f, m.w > 0.f ? v.w : 0.f);
+                }
+                if (n0 + 1 >= p.Cout) v.y = 0.f;    // (the lanes between Cout and the pitch hold whatever the caller left there)
+                if (n0 + 2 >= p.Cout) v.z = 0.f;
+                if (n0 + 3 >= p.Cout) v.w = 0.f;
+            }
+            float *d = P + (quad * 4) * HD_PLANE + pix;
+            d[0] = v.x, d[HD_PLANE] = v.y, d[2 * HD_PLANE] = v.z, d[3 * HD_PLANE] = v.w;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int tap = 0; tap < 25; ++tap) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int off = q * 4 * HD_PLANE + (4 - tap / 5) * HP_W + 4 - tap % 5;
+                float a[8];
+#pragma unroll
+                for (int t = 0; t < 8; ++t) a[t] = pa[off + (t >> 1) * HP_W + 16 * (t & 1)];
+#pragma unroll
+                for (int t = 0; t < 8; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], wreg[tap * 8 + half * 4 + q], acc[t], 0, 0, 0);
+            }
+        }
+    }
+
+    if (c >= p.ld) return;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) {
+        const int oy = oy0 + wave * 4 + (t >> 1);
+        if (oy >= p.H) continue;
+        float *orow = p.dx + ((size_t)b * p.H + oy) * p.W * p.ld + c;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ox = ox0 + 16 * (t & 1) + 4 * k + r;
+            if (ox < p.W) orow[(size_t)ox * p.ld] = c < p.Cin ? acc[t][r] : 0.f;       // lanes Cin..ld-1: zero
+        }
+    }
+}
+
 // OIHW [Cout][Cin][5][5] -> [K pad][32]: row k = tap*Cin + c, zero rows / columns beyond
 __global__ void pack_weight_head_kernel(const float *__restrict__ w, float *__restrict__ wp, int Cout, int Cin, int rows) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -228,6 +325,25 @@ using namespace ramnet;
 extern "C" size_t ramnet_packed_weight_elems_head(int Cin) { return (size_t)((25 * Cin + 1) / 2 * 2) * 32; }
 
 extern "C" int ramnet_head_supported(int Cin, int Cout) { return head_channels_ok(Cin) && Cout >= 1 && Cout <= 32; }
+
+extern "C" int ramnet_head_dgrad(const float *dy, int ldg, const float *y, int ldgm, const float *w, float *dx, int ld, int B, int H, int W, int Cin,
+                                 int Cout, void *stream) {
+    RAMNET_CHECK_ARG(dy && w && dx && B >= 1 && H >= 1 && W >= 1);
+    RAMNET_CHECK_ARG(ramnet_head_supported(Cin, Cout) && ld == roundup(Cin, 4));
+    RAMNET_CHECK_ARG(ldg % 4 == 0 && ldg >= roundup(Cout, 4) && ((uintptr_t)dy & 15) == 0);
+    RAMNET_CHECK_ARG(y == nullptr || (ldgm % 4 == 0 && ldgm >= roundup(Cout, 4) && ((uintptr_t)y & 15) == 0));
+    RAMNET_CHECK_ARG(((uintptr_t)w & 3) == 0 && ((uintptr_t)dx & 3) == 0);
+    const long tiles = (long)cdiv(W, HT_W) * cdiv(H, HD_H) * B;      // (pixel indices are 64-bit in the kernel: the grid is the one limit)
+    RAMNET_CHECK_ARG(tiles <= 0x7fffffffL);
+    HeadDgradParams q;
+    q.g = dy, q.gm = y, q.w = w, q.dx = dx;
+    q.ldg = ldg, q.ldgm = y ? ldgm : 0, q.ld = ld, q.B = B, q.H = H, q.W = W, q.Cin = Cin, q.Cout = Cout;
+    q.tiles_x = cdiv(W, HT_W), q.tiles_y = cdiv(H, HD_H);
+    note_kernel("conv_head_dgrad_kernel");
+    hipLaunchKernelGGL(conv_head_dgrad_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, q);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
 
 extern "C" int ramnet_pack_weight_head(const float *w, float *wp, int Cout, int Cin, void *stream) {
     RAMNET_CHECK_ARG(w && wp && ramnet_head_supported(Cin, Cout));

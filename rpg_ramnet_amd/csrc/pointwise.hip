@@ -125,6 +125,43 @@ __global__ void reflect_pad_kernel(const float *__restrict__ src, float *__restr
     }
 }
 
+// Backward of nchw_to_nhwc_pad_kernel: the first C of Cpad NHWC lanes back to NCHW, a copy.
+__global__ void nhwc_unpad_to_nchw_kernel(const float *__restrict__ src, float *__restrict__ dst, int B, int C, int HW, int Cpad) {
+    const size_t npix = (size_t)B * HW;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = i / HW, s = i - b * HW;
+        const float *in = src + i * Cpad;
+        float *out = dst + b * C * HW + s;
+        for (int c = 0; c < C; ++c) out[(size_t)c * HW] = in[c];
+    }
+}
+
+// Backward of reflect_pad_kernel, as a gather: frame pixel (sy, sx) sums the gradients of the padded positions that mirror onto it — per
+// axis the position top - sy above (1 <= sy <= top), its own top + sy, and top + 2 (H - 1) - sy below (sy <= H - 2, inside Hc) — in
+// ONE order: padded rows ascending, inside a row padded columns ascending, each term added to a sum that starts at zero.
+__global__ void reflect_pad_bwd_kernel(const float *__restrict__ g, float *__restrict__ dx, int B, int C, int H, int W, int Cpad, int top, int left,
+                                       int Hc, int Wc, int nhwc) {
+    const size_t npix = (size_t)B * H * W;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
+        const int sx = (int)(i % W), sy = (int)((i / W) % H);
+        const size_t b = i / ((size_t)W * H);
+        int ys[3], xs[3], ny = 0, nx = 0;
+        if (sy >= 1 && sy <= top) ys[ny++] = top - sy;
+        ys[ny++] = top + sy;
+        if (sy <= H - 2 && top + 2 * (H - 1) - sy < Hc) ys[ny++] = top + 2 * (H - 1) - sy;
+        if (sx >= 1 && sx <= left) xs[nx++] = left - sx;
+        xs[nx++] = left + sx;
+        if (sx <= W - 2 && left + 2 * (W - 1) - sx < Wc) xs[nx++] = left + 2 * (W - 1) - sx;
+        for (int c = 0; c < C; ++c) {
+            float acc = 0.f;
+            for (int a = 0; a < ny; ++a)
+                for (int e = 0; e < nx; ++e)
+                    acc += nhwc ? g[((b * Hc + ys[a]) * (size_t)Wc + xs[e]) * Cpad + c] : g[((b * C + c) * Hc + ys[a]) * (size_t)Wc + xs[e]];
+            dx[((b * C + c) * H + sy) * (size_t)W + sx] = acc;
+        }
+    }
+}
+
 // OIHW -> [tap][chunk][n][16].  transposed: reduce over O (backward-data), outputs = I.
 __global__ void pack_weight_kernel(const float *__restrict__ w, float *__restrict__ wp, int Cout, int Cin, int T,
                                    int transposed, int gates, int R, int N, int nchunks, int NPad, size_t total) {
@@ -1103,6 +1140,25 @@ extern "C" int ramnet_reflect_pad(const float *src, float *dst, int B, int C, in
     RAMNET_CHECK_ARG(!nhwc || (Cpad >= C && Cpad % 4 == 0));
     const size_t npix = (size_t)B * Hc * Wc;
     hipLaunchKernelGGL(reflect_pad_kernel, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, src, dst, B, C, H, W, Cpad, top, left, Hc, Wc, nhwc);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ramnet_nhwc_unpad_to_nchw(const float *src, float *dst, int B, int C, int H, int W, int Cpad, void *stream) {
+    RAMNET_CHECK_ARG(src && dst && B > 0 && C > 0 && H > 0 && W > 0 && Cpad >= C && Cpad % 4 == 0);
+    const size_t npix = (size_t)B * H * W;
+    hipLaunchKernelGGL(nhwc_unpad_to_nchw_kernel, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, src, dst, B, C, H * W, Cpad);
+    RAMNET_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ramnet_reflect_pad_bwd(const float *g, float *dx, int B, int C, int H, int W, int Cpad, int top, int left, int Hc, int Wc, int nhwc,
+                                      void *stream) {
+    RAMNET_CHECK_ARG(g && dx && B > 0 && C > 0 && H > 0 && W > 0 && top >= 0 && left >= 0 && Hc >= H + top && Wc >= W + left);
+    RAMNET_CHECK_ARG(top < H && Hc - H - top < H && left < W && Wc - W - left < W);          // reflection needs pad < extent
+    RAMNET_CHECK_ARG(!nhwc || (Cpad >= C && Cpad % 4 == 0));
+    const size_t npix = (size_t)B * H * W;
+    hipLaunchKernelGGL(reflect_pad_bwd_kernel, dim3(grid_for(npix)), dim3(256), 0, (hipStream_t)stream, g, dx, B, C, H, W, Cpad, top, left, Hc, Wc, nhwc);
     RAMNET_LAUNCH_CHECK();
     return 0;
 }

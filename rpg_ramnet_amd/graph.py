@@ -18,6 +18,9 @@ replays them with one host call:
 
 Replays are bit-identical to the eager path for forward results; gradients differ only by the order of the atomic partial sums
 (as between two eager runs).  Static input buffers are filled with ``copy_`` (device-to-device or pinned host-to-device).
+
+Input gradients (INTEGRATION.md "Input gradients") are not part of the captured runtimes: every one of them feeds static buffers that
+require no gradient, so a replay forms none for the event grids and frames copied into them.  Use the eager model for that.
 """
 import torch
 
@@ -480,7 +483,7 @@ class TimeBatchedStream:
 
 class GraphedPackage:
     """One data package through ``model.forward`` (K event grids + 1 frame -> K+1 predictions), state carried in static
-    buffers across calls; ``reset()`` starts a new recording."""
+    buffers across calls; ``reset()`` starts a new recording.  Inference only: the static inputs carry no gradient."""
 
     def __init__(self, model, example_item):
         self.model = model
@@ -522,7 +525,8 @@ class GraphedTrainStep:
     the gradients land in the parameters' ``.grad`` (the flat buffer of ``parallel.FlatGradReducer`` when one is attached).  The
     gradient tensors of the capture are owned by this object and re-installed as ``.grad`` at every call, so an
     ``optimizer.zero_grad()`` (set_to_none=True) between replays is harmless; do not REPLACE ``.grad`` by other tensors and expect
-    the replay to fill those."""
+    the replay to fill those.  The static input buffers are plain data: gradients with respect to the event grids and frames are
+    formed by the eager path alone (``inference.input_gradients``), not by a replay."""
 
     def __init__(self, model, sequence, loss_composition, loss_weights, reducer=None, grad_loss_weight=None, warmup=2):
         self.model, self.reducer = model, reducer

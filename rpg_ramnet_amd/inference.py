@@ -38,6 +38,44 @@ def empty_states(every_x_rgb_frame):
     return {'image': None}, lstm
 
 
+def _is_model_input(key, value):
+    return torch.is_tensor(value) and value.is_floating_point() and (key == "image" or (key.startswith("events") and key[6:].isdigit()))
+
+
+def input_gradients(model, sequence, loss_composition, loss_weights=None, **loss_kwargs):
+    """Attribution: the gradient of trainer.sequence_loss with respect to every event grid and frame of `sequence` (a list of packages
+    as the trainers feed them, 'depth_<key>' targets included), with the weights held fixed.
+
+    Every parameter's requires_grad is switched off for the call and restored afterwards (also when the loss raises), every
+    `events<k>` / `image` tensor enters as a leaf of its own (the caller's tensors are not touched), and one backward pass runs: no
+    parameter's .grad is read or written and no backward-weights kernel is launched — the backward-data launches alone, down to the
+    head layers (ramnet_head_dgrad) and the input repack.  loss_weights: one weight per key of loss_composition (default: ones);
+    loss_kwargs: the further arguments of trainer.sequence_loss (loss_params, grad_loss_weight, loss_type, mse_loss).
+    Returns (loss, [{key: gradient} per package]): the detached loss and NCHW gradients of the shape, dtype and device of what was
+    passed (zeros for an input the model did not read).  First derivatives only; captured graphs are not involved."""
+    from .trainer import sequence_loss
+    if loss_weights is None:
+        loss_weights = [1.0] * len(loss_composition or ())
+    params = [p for p in model.parameters()]
+    flags = [p.requires_grad for p in params]
+    try:
+        for p in params:
+            p.requires_grad_(False)
+        leaves, seq = [], []
+        for item in sequence:
+            mine = {k: v.detach().requires_grad_(True) for k, v in item.items() if _is_model_input(k, v)}
+            leaves.append(mine)
+            seq.append(dict(item, **mine))
+        with torch.enable_grad():
+            total, _ = sequence_loss(model, seq, loss_composition, loss_weights, **loss_kwargs)
+            total.backward()
+        grads = [{k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in mine.items()} for mine in leaves]
+        return total.detach(), grads
+    finally:
+        for p, f in zip(params, flags):
+            p.requires_grad_(f)
+
+
 def _time_batched_ok(model):
     return (type(model).__name__ == "ERGB2DepthRecurrent" and not bool(model.baseline) and model.recurrent_block_type == "conv"
             and torch.device(model.gpu).type == "cuda")

@@ -15,6 +15,7 @@ import weakref
 
 import torch
 from torch.autograd import Function
+from torch.autograd.function import once_differentiable
 
 from . import _hip as H
 
@@ -1662,8 +1663,18 @@ def _state_half_ok(want_x, npix, Cc):
 def pack_input(x, device, crop=None):
     """Model input NCHW (any device) -> NHWC with channels zero-padded to a multiple of 4 (model.py:177,200).
     crop: a CropParameters (full-frame mode, utils/inference_utils.py:287-314) — the frame is reflect-padded to crop.height_crop_size x
-    crop.width_crop_size inside the same launch."""
+    crop.width_crop_size inside the same launch.
+    An input that requires a gradient gets one (PackInput): the cast and the move are torch's own, differentiated by torch — a CPU or
+    float64 leaf receives its gradient in its own dtype and place —, the repack's backward is a HIP launch.  Any other input takes the bare
+    launch: no grad_fn, no extra launch, nothing kept."""
     x = x.to(device=device, dtype=torch.float32).contiguous()
+    if x.requires_grad and torch.is_grad_enabled():
+        return PackInput.apply(x, crop)
+    return _pack_input_launch(x, crop)
+
+
+def _pack_input_launch(x, crop):
+    device = x.device
     B, Cc, Hh, W = x.shape
     cp = (Cc + 3) // 4 * 4
     if crop is not None and (crop.height_crop_size, crop.width_crop_size) != (Hh, W):
@@ -1675,6 +1686,30 @@ def pack_input(x, device, crop=None):
     out = torch.empty(B, Hh, W, cp, device=device)
     H.check(H.lib().ramnet_nchw_to_nhwc_pad(_p(x), _p(out), B, Cc, Hh, W, cp, _st()), "ramnet_nchw_to_nhwc_pad")
     return out
+
+
+class PackInput(Function):
+    """pack_input for an input that requires a gradient: the same launch forward; backward is ramnet_nhwc_unpad_to_nchw, or
+    ramnet_reflect_pad_bwd in full-frame mode (a gather in one fixed order: deterministic as it stands).  No second derivative."""
+
+    @staticmethod
+    def forward(ctx, x, crop):
+        ctx.xshape, ctx.crop = tuple(x.shape), crop
+        return _pack_input_launch(x, crop)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        B, Cc, Hh, W = ctx.xshape
+        crop = ctx.crop
+        g = g.contiguous().float()
+        dx = torch.empty(B, Cc, Hh, W, device=g.device)
+        if tuple(g.shape[1:3]) != (Hh, W):
+            H.check(H.lib().ramnet_reflect_pad_bwd(_p(g), _p(dx), B, Cc, Hh, W, g.shape[3], crop.padding_top, crop.padding_left, crop.height_crop_size,
+                                                   crop.width_crop_size, 1, _st()), "ramnet_reflect_pad_bwd")
+        else:
+            H.check(H.lib().ramnet_nhwc_unpad_to_nchw(_p(g), _p(dx), B, Cc, Hh, W, g.shape[3], _st()), "ramnet_nhwc_unpad_to_nchw")
+        return dx, None
 
 
 class CropParameters:
@@ -1933,6 +1968,7 @@ class ConvAct(Function):
         mode = (H.IN_UP2X_SKIP if skip is not None else H.IN_UP2X) if up else H.IN_PLAIN
         epi = H.EPI_RELU if relu else H.EPI_LINEAR
         xpad = None
+        ctx.head = False
         ctx.s2d = _s2d_eligible(x, cp, k, stride, up)
         # (the fused view exists on the Winograd kernels alone: where a weight gradient is wanted and their backward-weights cannot address
         # x and y — whole tensors of 2 GB — the layer takes the materialised view, whose backward-weights the direct kernel can run)
@@ -1949,6 +1985,8 @@ class ConvAct(Function):
         else:
             conv_launch(x, Taps.get("conv", k, pad), cp.fwd(), y, cp.Cout, stride=stride, x1=skip, in_mode=mode,
                         Hin=Hin, Win=Win, bias=cp.bias(), epi=epi)
+            # a head layer whose input wants a gradient: backward-data runs the head kernel's own form where this launch ran the head kernel
+            ctx.head = bool(ctx.needs_input_grad[0]) and uses_head(Taps.get("conv", k, pad), cp.fwd(), stride, epi, mode)
         ctx.cp, ctx.stride, ctx.relu, ctx.up, ctx.mode = cp, stride, relu, up, mode
         # premask_ok: a caller that routes EVERY gradient of y through one fan-in (ops.TimeSplit / TimeFan) may have that fan-in apply the ReLU
         # mask and set premasked (premask_relu_feature): backward then reads dy as a plain operand
@@ -2013,17 +2051,24 @@ class ConvAct(Function):
             dx = _folded_upsample_dgrad(xs, dy, y if relu else None, cp)
             return dx, (dx if has_skip else None), None, None, None, None, None, None
         if ctx.needs_input_grad[0] or (has_skip and ctx.needs_input_grad[1]):
-            gin = torch.empty(B, Hin, Win, cp.Cin, device=xs.device)
+            # the gradient has the input's own padded width (a head layer: 1, 3, 5, 6, 10 channels in 4, 8 or 12 lanes); the packed
+            # backward-data weights are zero beyond Cin, so a launch over Cw outputs writes the pad lanes as zero
+            Cw = xs.shape[3]
+            gin = torch.empty(B, Hin, Win, Cw, device=xs.device)
             gmode = H.IN_RELUMASK if relu else H.IN_PLAIN
-            if stride == 1:
-                conv_launch(dy, Taps.get("dgrad1", k, pad), cp.bwd(), gin, cp.Cin, xm=y if relu else None, in_mode=gmode)
+            if ctx.head and ld(dy) % 4 == 0:        # the forward ran the head kernel: its backward-data kernel (csrc/conv_head.hip), weights as they are
+                ym = y if relu else None
+                H.check(H.lib().ramnet_head_dgrad(_p(dy), ld(dy), _p(ym), ld(ym) if relu else 0, _p(cp._cat_w()), _p(gin), Cw, B, Hin, Win,
+                                                  cp.Cin, cp.Cout, _st()), "ramnet_head_dgrad")
+            elif stride == 1:
+                conv_launch(dy, Taps.get("dgrad1", k, pad), cp.bwd(), gin, Cw, xm=y if relu else None, in_mode=gmode)
             else:
-                conv_launch_multi(dy, cp.bwd(), gin, cp.Cin,
+                conv_launch_multi(dy, cp.bwd(), gin, Cw,
                                   [(Taps.get("dgrad2", k, pad, py, px), (Hin - py + 1) // 2, (Win - px + 1) // 2, (2, 2, py, px))
                                    for py in range(2) for px in range(2)], xm=y if relu else None, in_mode=gmode)
             if up:
-                dx = torch.empty(B, Hh, W, cp.Cin, device=xs.device)
-                H.check(H.lib().ramnet_upsample2x_bwd(_p(gin), _p(dx), B, Hh, W, cp.Cin, _st()), "ramnet_upsample2x_bwd")
+                dx = torch.empty(B, Hh, W, Cw, device=xs.device)
+                H.check(H.lib().ramnet_upsample2x_bwd(_p(gin), _p(dx), B, Hh, W, Cw, _st()), "ramnet_upsample2x_bwd")
             else:
                 dx = gin
             dskip = dx if has_skip else None
